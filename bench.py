@@ -21,17 +21,24 @@ every rank (inside the timed region):
 --scaling weak (default): --batch utterances per GPU;  --scaling strong: --global-batch utterances split over the ranks.
 Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times --steps steps and prints the headline line (plus `clock_ghz`, the average shader clock
+of the timed region).  --dump-outputs DIR then also writes what the last timed step returned as DIR/<name>.npy (float32; a
+fixed, seeded sample of rows when the states exceed DUMP_BUDGET_BYTES), so that two builds can be compared output for output.
+
+--full adds everything else the benchmark measures or checks: HIP events around the dominant kernel inside the timed region,
+untimed per-kernel profiling steps, and the extra objects below.
   roofline     — the dominant kernel (the MFMA GEMM that serves conv1-6 and every linear layer): algorithmic FLOPs /
                  summed HIP-event time of its launches inside the timed region vs the dense MFMA peak of the compute
                  dtype (MI355X_MICROARCH.md: 157.3 TF fp32-in, 2500 TF bf16/f16).
+  kernels_ms_per_step — every kernel kind, from the untimed all-kernel profiling steps after the timed region.
   cpu_baseline — oracle/torch_oracle.py (the reference forward restated on the reference's own ATen call sites, PyTorch
-                 CPU fp32 — /root/reference itself does not exist on the GPU box) timed on this box's host cores on a
-                 bounded sample of the same workload (N = 1, rank 0 only).
+                 CPU fp32; the reference itself is not needed) timed on the host cores on a bounded sample of the same
+                 workload (N = 1, rank 0 only).
   parity       — max per-layer relative error of the HIP path on a sample of THIS workload's shapes (for mixed-length
                  batches the longest + shortest utterance padded to the batch n_max), against the torch restatement and
-                 the independent numpy oracle.  Every timed configuration carries one.
+                 the independent numpy oracle.  Every --full configuration carries one.
   comm         — (N > 1) bytes each GPU receives per step, the step time without the exchange and the exposed part.
+  other_modes  — (default workload, fp32) a short side measurement of the fp32x3 / fp16x2 / bf16 operand modes.
 """
 
 from __future__ import annotations
@@ -57,6 +64,42 @@ DTYPE_NAMES = {"fp32": "f32", "bf16": "bf16", "fp16": "f16", "fp32x3": "bf16x3 (
                "fp16x2": "f16x2 (fp16 activations x two-term weights: fp16 + fp16, or fp16 + MX-fp4 on the scaled-MFMA pipe for q|k|v / fc1 / fc2; fp32 accumulate)"}
 # default timed region >= 5 s of GPU work at the default workload (HuBERT-base 32 x 10 s): steps per dtype
 DEFAULT_STEPS = {"fp32": 150, "fp32x3": 330, "bf16": 700, "fp16": 700, "fp16x2": 500}
+# --dump-outputs writes at most this many bytes of arrays (below a 64 MB cap); larger states are sampled by rows
+DUMP_BUDGET_BYTES = 60_000_000
+DUMP_SEED = 0
+
+
+def output_arrays(out):
+    """name -> tensor of what one timed step returned: the hidden_states of the UpstreamExpert dict (`hidden_state_{i}`, the
+    dict's own keys; `last_hidden_state` is the last of them), or the (NS, B, T, D) / (B, T, D) tensor of an N-rank step."""
+    if isinstance(out, dict):
+        return {f"hidden_state_{i}": h for i, h in enumerate(out["hidden_states"])}
+    if out.dim() == 4:
+        return {f"hidden_state_{i}": out[i] for i in range(out.shape[0])}
+    return {"featurized": out}
+
+
+def dump_outputs(out, directory):
+    """Writes the arrays of `out` (output_arrays) as float32 `<name>.npy`.  When they exceed DUMP_BUDGET_BYTES every (B, T, D)
+    array is cut to the same fixed, seeded sample of (utterance, frame) rows, in ascending order; `sampled_rows.npy` holds those
+    (utterance, frame) pairs.  Returns the names written."""
+    import numpy as np
+    import torch
+
+    arrays = output_arrays(out)
+    B, T, D = next(iter(arrays.values())).shape
+    os.makedirs(directory, exist_ok=True)
+    rows = None
+    if len(arrays) * B * T * D * 4 > DUMP_BUDGET_BYTES:
+        n_rows = max(1, (DUMP_BUDGET_BYTES - 2 * 8 * B * T) // (len(arrays) * D * 4))
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B * T, size=min(n_rows, B * T), replace=False))
+        np.save(os.path.join(directory, "sampled_rows.npy"), np.stack([rows // T, rows % T], 1).astype(np.float64))
+    for name, h in arrays.items():
+        h = h.float()
+        if rows is not None:
+            h = h.reshape(B * T, D).index_select(0, torch.from_numpy(rows).to(h.device))
+        np.save(os.path.join(directory, f"{name}.npy"), h.cpu().numpy())
+    return sorted(arrays) + ([] if rows is None else ["sampled_rows"])
 
 
 def csrc_sha16():
@@ -193,13 +236,24 @@ def parse_args(argv=None):
                     help="launcher / process-group / exchange plumbing only, on CPU tensors (no GPU, no encoder): what the "
                          "CPU-box test of `--gpus N` runs")
     ap.add_argument("--no-other-modes", action="store_true",
-                    help="skip the short side measurement of the other operand modes (fp32x3, bf16) in the default run")
+                    help="skip the short side measurement of the other operand modes (fp32x3, fp16x2, bf16) in a --full run")
     ap.add_argument("--no-profile", action="store_true", help="no per-kernel HIP events in the timed region (A/B of their cost)")
     ap.add_argument("--cpu-sample", type=int, default=None, help="utterances of the workload timed on the CPU oracle")
     ap.add_argument("--parity-sample", type=int, default=2, help="utterances checked against the numpy oracle")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="per-kernel HBM-side bytes from the committed rocprofv3 PMC passes (tools/pmc.sh)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: kernel events in the timed region, per-kernel breakdown, roofline, "
+                         "comm (N > 1), parity, CPU baseline, other operand modes (the --no-* options above trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, at most "
+                         f"{DUMP_BUDGET_BYTES // 1_000_000} MB: a fixed, seeded sample of rows for larger states)")
+    args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def self_launch(args):
@@ -308,7 +362,7 @@ def main():
     enc = expert._encoder_for(dev)
     n = int(args.secs * 16000)
     B = args.batch if args.scaling == "weak" else -(-args.global_batch // world)
-    steps = args.steps or DEFAULT_STEPS[args.dtype]
+    steps = args.steps if args.steps is not None else DEFAULT_STEPS[args.dtype]
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
     lens = [n] * B
     if args.mixed:
@@ -389,9 +443,12 @@ def main():
     # slow box and not as a regression (round 5: the driver's box ran every kernel 2.0-3.5 % slower than the builder's lease)
     clock = {"buf": torch.zeros((2, 3), dtype=torch.int64, device=dev), "ghz": None}
 
+    last = {}  # what the last step of the latest timed region returned (--dump-outputs)
+
     def timed(k, exchange=True, profile=False):
         """k steps bracketed by barrier + synchronize on both sides; max over ranks."""
         prof_steps = 0
+        last.clear()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -405,7 +462,10 @@ def main():
                 enc.profile_enable(2 if on else 0)
             prof_steps += int(on)
             occupy()
-            step(exchange)
+            if i == k - 1:
+                last["out"] = step(exchange)
+            else:
+                step(exchange)
         if clk is not None:  # ... and behind the last one: enqueued, not waited for — nothing is added to the timed region but two
             # one-wave launches; read after the region's own synchronize
             _lib.check(_lib.load().s3enc_debug_clock_sample(clk[1].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
@@ -445,13 +505,17 @@ def main():
         # timed region: HIP events only around the launches of the dominant kernel (the GEMM), and only on every 4th
         # step — an event pair costs a ~5 us bubble on the stream: around all ~290 launches of a forward that is 0.8 ms
         # per batch (2 % fp32, 10 % bf16), around the 55 GEMM launches 0.6 ms.  The full per-kernel breakdown is measured
-        # in extra, untimed steps after the timed region.
+        # in extra, untimed steps after the timed region.  Both only with --full: a plain run times the steps alone.
         PROF_EVERY = 4
-        elapsed, prof_steps = timed(steps, True, not args.no_profile)
+        profile = args.full and not args.no_profile
+        elapsed, prof_steps = timed(steps, True, profile)
         headline_clock = clock["ghz"]
-        prof = enc.profile_read()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(last["out"], args.dump_outputs)
+        last.clear()
+        prof = enc.profile_read() if profile else []
         comm = None
-        if world > 1:  # always reported for N > 1: what the exchange moves and how much of it the compute does not hide
+        if world > 1 and args.full:  # for N > 1: what the exchange moves and how much of it the compute does not hide
             k2 = max(3, min(steps, 30))
             el2 = elapsed / steps * k2
             if gather != "none":
@@ -467,7 +531,7 @@ def main():
                     "exposed_ms_per_step": round((elapsed / steps - el2 / k2) * 1e3, 3),
                     "steps_without_exchange": k2 if gather != "none" else 0}
         breakdown, bd_steps = [], 3
-        if not args.no_profile:
+        if profile:
             enc.profile_reset()
             enc.profile_enable(1)
             for _ in range(bd_steps):
@@ -524,28 +588,31 @@ def main():
             },
             # the reference computes padded frames too, so the path's work is B x F_utt(n_max)
             "path_tflops": round(world * B * flops_per_utt(cfg, n) / (ms_per_step * 1e-3) / 1e12, 2),
-            "roofline": {
-                "kernel": ({"fp32": "gemm_tile_kernel<float> (gemmt.hip)", "fp32x3": "gemm_x3_kernel (gemm_x3.hip)"}.get(args.dtype, "gemm16_big_kernel (gemm16.hip)"))
-                          + ": conv1-6 implicit GEMM + proj/qkv/out_proj/fc1/fc2 (+ heads / adapter convolutions where the model has them)",
-                "bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4), "traffic": None, "algorithmic_bytes": round(g_by / max(g_n, 1)),
-                "launches_per_step": g_n // max(prof_steps, 1), "avg_launch_ms": round(g_ms / max(g_n, 1), 4),
-                "timed_steps_with_events": prof_steps,
-                # share of the summed kernel time of a forward, from the all-kernel profiling steps (same steps for both)
-                "share_of_kernel_time": round(bd_gemm / bd_all, 3) if bd_all else None,
-            },
-            # every kernel kind, from the untimed all-kernel profiling steps after the timed region
-            "kernels_ms_per_step": {p["name"]: round(p["ms"] / bd_steps, 4) for p in sorted(breakdown, key=lambda p: -p["ms"])},
         }
+        if args.full:
+            line.update({
+                "roofline": {
+                    "kernel": ({"fp32": "gemm_tile_kernel<float> (gemmt.hip)", "fp32x3": "gemm_x3_kernel (gemm_x3.hip)"}.get(args.dtype, "gemm16_big_kernel (gemm16.hip)"))
+                              + ": conv1-6 implicit GEMM + proj/qkv/out_proj/fc1/fc2 (+ heads / adapter convolutions where the model has them)",
+                    "bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4), "traffic": None, "algorithmic_bytes": round(g_by / max(g_n, 1)),
+                    "launches_per_step": g_n // max(prof_steps, 1), "avg_launch_ms": round(g_ms / max(g_n, 1), 4),
+                    "timed_steps_with_events": prof_steps,
+                    # share of the summed kernel time of a forward, from the all-kernel profiling steps (same steps for both)
+                    "share_of_kernel_time": round(bd_gemm / bd_all, 3) if bd_all else None,
+                },
+                # every kernel kind, from the untimed all-kernel profiling steps after the timed region
+                "kernels_ms_per_step": {p["name"]: round(p["ms"] / bd_steps, 4) for p in sorted(breakdown, key=lambda p: -p["ms"])},
+            })
         if comm:
             line["comm"] = comm
-        tr, tr_note = pmc_traffic(args.traffic, args.model, args.dtype, B, args.secs)
+        tr, tr_note = pmc_traffic(args.traffic, args.model, args.dtype, B, args.secs) if args.full else (None, None)
         if tr is not None:
             line["roofline"]["traffic"] = tr["gemm_bytes_per_launch"]
             line["roofline"]["traffic_source"] = tr["source"] + f"; kernels {tr['csrc_sha16']}" + (f", commit {tr['commit']}" if tr.get("commit") else "")
         elif tr_note:
             line["roofline"]["traffic_note"] = tr_note
-        if world == 1 and not args.no_parity and cfg.family != "distiller":
+        if args.full and world == 1 and not args.no_parity and cfg.family != "distiller":
             # checkers + CPU baseline only; never on the product path
             from oracle import encoder_oracle as O
             from oracle import torch_oracle as TO

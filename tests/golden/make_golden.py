@@ -413,9 +413,51 @@ def make_hf_case(name: str):
     print(f"{name}: {len(hs)} x {hs[0].shape} -> {os.path.getsize(path) / 1e3:.0f} kB")
 
 
+# The reference's hub surface (tests/test_hub_reference_cpu.py): the names ``s3prl.hub.options()`` lists, every entry of the
+# hubconfs of the families this package serves with its signature (parameter name, kind, repr of the default), and the cache
+# file name ``util/download.py:_urls_to_filepaths`` gives three URLs.  Names and signatures only, recorded by introspection.
+HUB_FAMILIES = ("hubert", "wav2vec2", "wavlm", "unispeech_sat", "data2vec", "distiller", "multires_hubert", "hf_hubert", "hf_wav2vec2")
+
+
+def make_reference_hub():
+    import importlib
+    import inspect
+
+    import s3prl_amd.hub as amd
+
+    _import_reference()
+    import s3prl.hub as ref_hub
+    from s3prl.util import download as ref_dl
+
+    hubconfs = {}
+    for family in HUB_FAMILIES:
+        conf = importlib.import_module(f"s3prl.upstream.{family}.hubconf")
+        entries = []
+        for name, fn in vars(conf).items():
+            if name.startswith("_") or not inspect.isfunction(fn) or fn.__module__ != conf.__name__:
+                continue
+            assert getattr(ref_hub, name) is fn, name
+            entries.append([name, [[k, v.kind.name, repr(v.default)] for k, v in inspect.signature(fn).parameters.items()]])
+        hubconfs[family] = entries
+    with tempfile.TemporaryDirectory() as tmp:
+        ref_dl.set_dir(tmp)
+        root = str(ref_dl.get_dir().resolve())
+        cache = {url: os.path.relpath(ref_dl._urls_to_filepaths(url, download=False), root) for url in (amd.hubert_base.url, amd.wavlm_large.url, amd.xlsr_53.legacy_url)}
+    out = dict(reference="s3prl 0.4.18: s3prl.hub, s3prl.upstream.<family>.hubconf, s3prl.util.download",
+               options=sorted(ref_hub.options()), registered_ckpt_options=sorted(ref_hub.options(only_registered_ckpt=True)),
+               hubconfs=hubconfs, cache_file_names=cache)
+    with open(os.path.join(HERE, "reference_hub.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("reference_hub.json", sum(len(v) for v in hubconfs.values()), "hubconf entries")
+
+
 if __name__ == "__main__":
-    names = sys.argv[1:] or (list(CASES) + list(FEAT_CASES) + list(LEGACY_FEAT_CASES) + list(HF_CASES))
+    names = sys.argv[1:] or (list(CASES) + list(FEAT_CASES) + list(LEGACY_FEAT_CASES) + list(HF_CASES) + ["reference_hub"])
     for n in names:
+        if n == "reference_hub":
+            make_reference_hub()
+            continue
         if n in LEGACY_FEAT_CASES:
             make_legacy_feat_case(n)
             continue

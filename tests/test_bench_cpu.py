@@ -84,7 +84,7 @@ def test_stale_traffic_record_is_not_quoted(tmp_path):
 
 
 def test_committed_traffic_records_of_the_headline_workload_are_current():
-    """The default bench line quotes roofline.traffic from profiles/traffic.json: the committed record of the metric's workload must
+    """The `--full` bench line quotes roofline.traffic from profiles/traffic.json: the committed record of the metric's workload must
     match this tree (by source stamp or by device code), else the driver's line says `traffic: null`."""
     import importlib.util
 
@@ -160,3 +160,46 @@ def test_mx4_quantiser_of_the_emulation_is_the_documented_format():
         nearest = np.abs(blk[..., None] - grid * s[..., None]).min(-1)
         assert (np.abs(qb - blk) <= nearest + 1e-15).all()
     assert (FB.mx4(np.zeros((2, 32))) == 0).all()
+
+
+def test_dump_outputs_writes_a_fixed_sample_under_the_budget(tmp_path):
+    """--dump-outputs: the arrays of the last timed step as float32 .npy, the same seeded rows of every state when they exceed the
+    budget (the headline workload's 13 x 32 x 499 x 768 fp32 states are 637 MB), whole when they fit — identical from run to run."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    NS, B, T, D = 13, 32, 499, 768
+    hs = torch.randn((NS, B, T, D), generator=torch.Generator().manual_seed(5))
+    out = {"hidden_states": tuple(hs[l] for l in range(NS)), "last_hidden_state": hs[-1]}
+    names = bench.dump_outputs(out, str(tmp_path / "a"))
+    assert names == sorted(f"hidden_state_{l}" for l in range(NS)) + ["sampled_rows"]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BUDGET_BYTES < 64 * 10**6
+    rows = np.load(tmp_path / "a" / "sampled_rows.npy").astype(np.int64)
+    assert rows.shape[1] == 2 and rows.shape[0] > 1000 and (rows[:, 0] < B).all() and (rows[:, 1] < T).all()
+    for l in (0, 7, NS - 1):
+        got = np.load(tmp_path / "a" / f"hidden_state_{l}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, hs[l].numpy()[rows[:, 0], rows[:, 1]])
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    assert all(np.array_equal(np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")) for n in names)
+    small = hs[:3, :2, :10].to(torch.bfloat16)  # an N-rank step's (NS, B, T, D) 16-bit states fit whole
+    assert bench.dump_outputs(small, str(tmp_path / "c")) == ["hidden_state_0", "hidden_state_1", "hidden_state_2"]
+    got = np.load(tmp_path / "c" / "hidden_state_1.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small[1].float().numpy())
+
+
+def test_plain_run_and_full_options():
+    """A plain run times the steps alone; --full carries the rest.  --steps is taken as given."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and a.steps is None

@@ -1,33 +1,55 @@
-"""The registration promise of INTEGRATION.md §1 against the REAL reference ``s3prl.hub`` / ``s3prl.nn`` (imported from
-/root/reference behind placeholder torchaudio / omegaconf modules — build container only; skipped where the reference
-tree is absent, e.g. on the GPU box): ``register_into_s3prl`` installs our entries without clobbering the reference's,
-and the hub-entry signatures / the expert attributes are what ``S3PRLUpstream.__init__`` (nn/upstream.py:102-140) uses."""
+"""The registration promise of INTEGRATION.md §1 against the reference's ``s3prl.hub`` / hubconf surface, as recorded in
+``tests/golden/reference_hub.json`` (``make_golden.py reference_hub``: the names ``s3prl.hub.options()`` lists, every hubconf
+entry of the served families with its signature, the reference's cache file names): ``register_into_s3prl`` installs our
+entries without clobbering the reference's, and the hub-entry signatures / the expert attributes are what
+``S3PRLUpstream.__init__`` (nn/upstream.py:102-140) uses."""
 
+import json
 import os
 import sys
 
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree not present")
+REFERENCE_HUB = os.path.join(HERE, "golden", "reference_hub.json")
+
+
+def _stand_in_s3prl(tmp_path):
+    """A package ``s3prl`` whose ``hub`` module defines every name the reference's ``s3prl.hub.options()`` lists (placeholder
+    callables) and an ``options()`` with the reference hub's rule (hub.py:40-54: the public callables of the module)."""
+    ref = json.load(open(REFERENCE_HUB))
+    pkg = tmp_path / "stand_in" / "s3prl"
+    pkg.mkdir(parents=True)
+    (pkg / "__init__.py").write_text("")
+    body = ["def _placeholder(name):", "    def entry(*args, **kwargs):", "        raise NotImplementedError(name)",
+            "    entry.__name__ = name", "    return entry", ""]
+    body += [f"{name} = _placeholder({name!r})" for name in ref["options"]]
+    body += ["", "def options(only_registered_ckpt=False):",
+             "    suffixes = ('_local', '_url', '_gdriveid', '_custom')",
+             "    return [n for n, v in list(globals().items()) if not n.startswith('_') and callable(v) and n != 'options'",
+             "            and not (only_registered_ckpt and n.endswith(suffixes))]", ""]
+    (pkg / "hub.py").write_text("\n".join(body))
+    return str(tmp_path / "stand_in")
 
 
 _SCRIPT = r"""
-import inspect, os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests", "golden"))
-import ref_shim
-ref_shim.import_reference()
-import s3prl.hub as ref_hub          # the REAL reference hub
+import inspect, json, os, sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[3])
+ref = json.load(open(sys.argv[4]))
+import s3prl.hub as ref_hub          # the stand-in of the reference hub: the names it lists
 import s3prl_amd.hub as amd
 from s3prl_amd.ckpt import save_checkpoint
 from s3prl_amd.synth import named_config, synth_weights
 
-before = {n: getattr(ref_hub, n) for n in ("hubert_local", "wavlm_local", "wav2vec2_custom", "fbank")}
+assert sorted(ref_hub.options()) == ref["options"]
+before = {n: getattr(ref_hub, n) for n in ref["options"]}
+assert {"hubert_local", "wavlm_local", "wav2vec2_custom", "fbank"} <= set(before)
 installed = amd.register_into_s3prl(prefix="amd_")
 assert {"amd_hubert_local", "amd_distiller_local", "amd_unispeech_sat_local", "amd_wav2vec2_custom"} <= set(installed)
-amd.register_into_s3prl()            # default: override=False -> same-named reference entries are left alone
+added = amd.register_into_s3prl()    # default: override=False -> same-named reference entries are left alone
 for n, f in before.items():
     assert getattr(ref_hub, n) is f, n
+assert set(added) == set(amd.options()) - set(before), sorted(set(added) ^ (set(amd.options()) - set(before)))
 assert "amd_hubert_local" in ref_hub.options()
 cfg = named_config("tiny_hubert")
 path = os.path.join(sys.argv[2], "c.pt")
@@ -35,41 +57,38 @@ save_checkpoint(path, cfg, synth_weights(cfg, 0))
 expert = getattr(ref_hub, "amd_hubert_local")(ckpt=path, refresh=False)
 assert expert.get_downsample_rates("hidden_states") == 320
 assert expert.num_layers == cfg.encoder_layers + 1 and expert.hidden_sizes == [cfg.encoder_embed_dim] * expert.num_layers
+sigs = {name: params for entries in ref["hubconfs"].values() for name, params in entries}
 for name in ("hubert_custom", "wav2vec2_custom"):   # hubert/hubconf.py:29-66, wav2vec2/hubconf.py:28-66
-    ref, ours = inspect.signature(getattr(ref_hub, name)), inspect.signature(getattr(amd, name))
-    assert list(ref.parameters) == list(ours.parameters), name
+    ours = inspect.signature(getattr(amd, name))
+    assert [k for k, _, _ in sigs[name]] == list(ours.parameters), name
     assert all(ours.parameters[k].default is False for k in ("legacy", "fairseq", "refresh"))
 print("REFERENCE_HUB_OK")
 """
 
 
 def test_register_into_the_real_hub_and_signatures(tmp_path):
-    """Runs in a subprocess: importing the reference installs placeholder torchaudio / omegaconf modules process-wide."""
+    """Runs in a subprocess: the stand-in ``s3prl`` package and the registration stay out of the test process."""
     import subprocess
 
     root = os.path.dirname(HERE)
-    out = subprocess.run([sys.executable, "-c", _SCRIPT, root, str(tmp_path)], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, "-c", _SCRIPT, root, str(tmp_path), _stand_in_s3prl(tmp_path), REFERENCE_HUB],
+                         capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "REFERENCE_HUB_OK" in out.stdout, out.stderr[-3000:]
 
 
 _NAMES_SCRIPT = r"""
-import importlib, inspect, os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests", "golden"))
-import ref_shim
-ref_shim.import_reference()
-import s3prl.hub as ref_hub          # the REAL reference hub
+import inspect, json, os, sys
+sys.path.insert(0, sys.argv[1])
+ref = json.load(open(sys.argv[3]))
 import s3prl_amd.hub as amd
 checked = 0
-for family in ("hubert", "wav2vec2", "wavlm", "unispeech_sat", "data2vec", "distiller", "multires_hubert", "hf_hubert", "hf_wav2vec2"):
-    ref_conf = importlib.import_module(f"s3prl.upstream.{family}.hubconf")
-    for name, fn in vars(ref_conf).items():
-        if name.startswith("_") or not inspect.isfunction(fn) or fn.__module__ != ref_conf.__name__:
-            continue
-        assert getattr(ref_hub, name) is fn, name                   # it IS a name the reference hub serves
+for family, entries in ref["hubconfs"].items():
+    for name, params in entries:
+        assert name in ref["options"], name                        # it IS a name the reference hub serves
         assert hasattr(amd, name), f"{family}: s3prl_amd.hub lacks {name}"
-        ref, ours = inspect.signature(fn), inspect.signature(getattr(amd, name))
-        assert [(k, v.kind, v.default) for k, v in ref.parameters.items()] == \
-               [(k, v.kind, v.default) for k, v in ours.parameters.items()], (name, str(ref), str(ours))
+        ours = inspect.signature(getattr(amd, name))
+        assert [list(p) for p in params] == [[k, v.kind.name, repr(v.default)] for k, v in ours.parameters.items()], \
+               (name, params, str(ours))
         assert name in amd.options(), name
         checked += 1
 assert checked >= 60, checked
@@ -77,12 +96,15 @@ assert checked >= 60, checked
 reg = set(amd.options(only_registered_ckpt=True))
 assert {"hubert_base", "hubert_large_ll60k", "wav2vec2_large_ll60k", "xls_r_300m", "wavlm_large", "wavlm_base_plus",
         "unispeech_sat_large", "data2vec_large_ll60k", "contentvec"} <= reg
+assert all(n in ref["registered_ckpt_options"] for _, entries in ref["hubconfs"].items() for n, _ in entries if n in reg)
 # cache naming rule = the reference's (util/download.py:186-208)
-from s3prl.util import download as ref_dl
 from s3prl_amd import download as our_dl
-ref_dl.set_dir(sys.argv[2]); our_dl.set_dir(sys.argv[2])
-for url in (amd.hubert_base.url, amd.wavlm_large.url, amd.xlsr_53.legacy_url):
-    assert ref_dl._urls_to_filepaths(url, download=False) == our_dl.urls_to_filepaths(url, download=False), url
+our_dl.set_dir(sys.argv[2])
+urls = (amd.hubert_base.url, amd.wavlm_large.url, amd.xlsr_53.legacy_url)
+assert set(urls) == set(ref["cache_file_names"])
+for url in urls:
+    want = os.path.join(os.path.realpath(sys.argv[2]), ref["cache_file_names"][url])
+    assert our_dl.urls_to_filepaths(url, download=False) == want, url
 print("REFERENCE_NAMES_OK", checked)
 """
 
@@ -92,7 +114,8 @@ def test_every_released_name_of_the_reference_hubconfs_exists_with_the_same_sign
     import subprocess
 
     root = os.path.dirname(HERE)
-    out = subprocess.run([sys.executable, "-c", _NAMES_SCRIPT, root, str(tmp_path)], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, "-c", _NAMES_SCRIPT, root, str(tmp_path), REFERENCE_HUB], capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0 and "REFERENCE_NAMES_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
 
 

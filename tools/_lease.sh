@@ -19,7 +19,7 @@ done; done
 { grep -E "passed|failed|error" gpurun_out/r06d/gputests_full_raw.log | tail -3; cat gpurun_out/r06d/gputests_time.log; } > gpurun_out/r06d/gputests_final.log
 cat gpurun_out/r06d/gputests_final.log | tee -a $L
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1 | tee -a $L
-Q="--no-cpu-baseline --no-other-modes"
+Q="--full --no-cpu-baseline --no-other-modes"
 for cfg in "fp32 gemm hubert_base fp32" "bf16 gemm16 hubert_base bf16" "fp16x2 gemm16 hubert_base fp16x2"; do
   set -- $cfg
   name=$1; sub=$2; model=$3; dtype=$4
@@ -29,7 +29,7 @@ for cfg in "fp32 gemm hubert_base fp32" "bf16 gemm16 hubert_base bf16" "fp16x2 g
   rm -rf gpurun_out/pmc_r06d_$name gpurun_out/pmc_r06d_$name.md
 done
 cp profiles/traffic.json gpurun_out/r06d/traffic.json
-timeout 900 python bench.py > gpurun_out/r06d/bench_default_final.json 2> gpurun_out/r06d/bench_default_final.err
+timeout 900 python bench.py --full > ${L%/*}/bench_default_final.json 2> ${L%/*}/bench_default_final.err
 python -c "
 import json; d=json.loads(open('gpurun_out/r06d/bench_default_final.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['clock_ghz'], d['roofline']['frac'], d['roofline']['traffic'], {k: v['ms_per_step'] for k, v in d['other_modes'].items()})" | tee -a $L
 for d in bf16 fp16x2; do python bench.py --dtype $d $Q --steps 100 --warmup 3 > gpurun_out/r06d/bench_$d.json 2>/dev/null; python -c "

@@ -1,7 +1,7 @@
 """Host-side cost of one forward (time for the asynchronous s3enc_forward call to return on an empty queue) next to the
 steady-state GPU time per forward."""
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from s3prl_amd.encoder import HipEncoder
 from s3prl_amd.synth import named_config, synth_weights
 for model, dtype in (("hubert_base", "bf16"), ("hubert_large", "bf16")):

@@ -10,7 +10,7 @@ tag=${1:-r06}
 export TMPDIR=/tmp
 out=gpurun_out/$tag
 mkdir -p $out
-Q="--no-cpu-baseline --no-other-modes"
+Q="--full --no-cpu-baseline --no-other-modes"
 
 # one configuration: name, kernel substring of its dominant GEMM, model, dtype, batch, secs, extra bench flags, steps
 profile_cfg() {
@@ -35,7 +35,7 @@ profile_cfg() {
 
 # 1. the metric's workload (HuBERT-base 32 x 10 s, fp32): PMC + traffic first so that the default bench line carries it
 profile_cfg fp32 gemm hubert_base fp32 32 10 "" 60
-python bench.py > $out/bench_fp32.json 2> $out/bench_fp32.err          # the default run: >= 5 s timed, CPU baseline, other modes
+python bench.py --full > $out/bench_fp32.json 2> $out/bench_fp32.err   # the default workload: >= 5 s timed, CPU baseline, other modes
 # 2. the in-tolerance throughput mode of the same workload, then BASELINE configs[2] / [3] / [4]: every config's fp16x2 line
 #    (parity < 1e-3) first, its bf16 line (the dtype BASELINE names; parity 1e-2) second
 profile_cfg fp16x2 gemm16 hubert_base fp16x2 32 10 "" 200
@@ -67,6 +67,6 @@ tools/micro/mx_probe > $out/mx_probe.md 2>&1
 python tools/parity_table.py > $out/parity.md 2> $out/parity.err
 # 6. a sibling model and the N-rank path, functionally (two ranks share this box's single GPU over a gloo rendezvous)
 python bench.py --model multires_hubert_base $Q --steps 40 --warmup 3 > $out/bench_multires_hubert_base_fp32.json 2>/dev/null
-python bench.py --gpus 2 --backend gloo --gather layers --steps 5 --warmup 1 --no-profile > $out/bench_2rank_gloo_layers.json 2>/dev/null
-python bench.py --gpus 2 --backend gloo --dtype fp16x2 --exchange-algo direct --steps 5 --warmup 1 --no-profile > $out/bench_2rank_gloo_fp16x2_direct.json 2>/dev/null
+python bench.py --full --gpus 2 --backend gloo --gather layers --steps 5 --warmup 1 --no-profile > $out/bench_2rank_gloo_layers.json 2>/dev/null
+python bench.py --full --gpus 2 --backend gloo --dtype fp16x2 --exchange-algo direct --steps 5 --warmup 1 --no-profile > $out/bench_2rank_gloo_fp16x2_direct.json 2>/dev/null
 ls $out

@@ -13,7 +13,7 @@ maxn=${2:-8}
 out=gpurun_out/${tag}_scale
 mkdir -p $out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-Q="--no-cpu-baseline --no-other-modes --no-parity"
+Q="--full --no-cpu-baseline --no-other-modes --no-parity"
 ns="1"; for n in 2 4 8; do [ $n -le $maxn ] && ns="$ns $n"; done
 
 run() {  # name, N, bench flags...
