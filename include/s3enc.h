@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define S3ENC_VERSION 7
+#define S3ENC_VERSION 8
 #define S3ENC_MAX_CONV 16
 #define S3ENC_MAX_RES 4 /* resolutions of a multires-HuBERT U-net: up to 3 rate pairs, 7 encoder blocks */
 
@@ -107,6 +107,20 @@ typedef struct s3enc_config {
     int32_t mr_layers[2 * S3ENC_MAX_RES - 1];       /* layers per block in execution order: encoders..., middle, decoders... */
     int32_t mr_kernel;                              /* conv_adapator_kernal (7): odd, every rate divides mr_kernel - 1 */
     int32_t mr_plain;                               /* use_plain_updownsample: ConvDownsampler / ConvUpsampler, else ConvAdapter */
+    /* ABI 8: wav2vec 2.0 Conformer encoders (ConformerEncoder / ConformerEncoderLayer, wav2vec2_model.py:440-578,3132-3211),
+     * family S3ENC_WAV2VEC2 only, compute_dtype S3ENC_F32 only (s3enc_create refuses the other modes by name).  Per layer:
+     *   x += 0.5 * FFN1(x);  x += MHA(LN(x));  x += Conv(x);  x += 0.5 * FFN2(x);  x = LN_final(x)
+     * FFN(x) = w_2 . swish(w_1 . LN(x) + b_1) + b_2;  Conv(x) = PW2 . swish(BN(DW(GLU(PW1 . LN(x)))));  no positional conv (its
+     * checkpoint weights are accepted and ignored).  Checkpoint tensors per layer "encoder.layers.N." + the reference state_dict
+     * names: ffn1.layer_norm.{weight,bias}, ffn1.w_1.{weight,bias}, ffn1.w_2.{weight,bias}, self_attn_layer_norm.{weight,bias},
+     * self_attn.linear_{q,k,v,out}.{weight,bias}, [rel_pos: self_attn.linear_pos.weight, self_attn.pos_bias_u, self_attn.pos_bias_v
+     * (H, 64)], conv_module.layer_norm.{weight,bias}, conv_module.pointwise_conv1.weight (2D, D, 1),
+     * conv_module.depthwise_conv.weight (D, 1, dw_kernel), conv_module.batch_norm.{weight,bias,running_mean,running_var},
+     * conv_module.pointwise_conv2.weight (D, D, 1), ffn2.* as ffn1, final_layer_norm.{weight,bias}; plus encoder.layer_norm.
+     * Measured (Conformer-large, 32 x 10 s, one MI355X): 157.8 ms per batch with rope, 162.1 ms with rel_pos. */
+    int32_t layer_type;                             /* 0 transformer, 1 conformer */
+    int32_t pos_enc_type;                           /* conformer: 1 rel_pos (Transformer-XL relative attention), 2 rope */
+    int32_t dw_kernel;                              /* conformer: depthwise_conv_kernel_size (odd, <= 63; 31) */
 } s3enc_config;
 
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
@@ -271,7 +285,9 @@ int s3enc_profile_read(s3enc_handle h, s3enc_profile_entry* entries, int32_t max
  * Diagnostic (tools/two_stream_probe.py --taps): with the environment variable S3ENC_DEBUG_STOP = k set when the library loads, every
  * forward ends behind stage k — 1 + i: conv layer i, 20: the feature LayerNorm, 21: post_extract_proj, 22: the positional conv, 30 .. 34:
  * layer 0's q|k|v / attention / out_proj / LayerNorm / fc1, 40 + l: in front of layer l — writes NO states, and keeps "conv0" .. as taps
- * too (a conv tap is whole only for the last two conv layers that ran: the stack ping-pongs between two buffers). */
+ * too (a conv tap is whole only for the last two conv layers that ran: the stack ping-pongs between two buffers).  Conformer
+ * handles: "ffn1_0" (layer 0 after x + 0.5 FFN1), "attn0", "conv0_mod" (the conv module's pointwise_conv2 operand), "ffn2_0"
+ * (before final_layer_norm) — buffers later layers reuse: whole for a one-layer model or with S3ENC_DEBUG_STOP = 41. */
 int s3enc_debug_tap(s3enc_handle h, const char* name, float* host_out, int64_t max_elems, int64_t* n_elems);
 /* Measurement hook (no reference counterpart): `workgroups` x `threads` idle threads that hold their CU slots for `milliseconds` on
  * `stream` — a stand-in for a collective's channel kernels running beside the encoder (bench.py --steal-cus). */
@@ -386,6 +402,22 @@ int s3enc_op_layernorm(int32_t dtype, const float* x, const float* gamma, const 
  * R = max_distance serves every T). */
 int s3enc_op_attention(int32_t dtype, const void* qkv, void* out, const int32_t* valid, int32_t B, int32_t T,
                        int32_t H, const float* bias_table, int32_t table_R, const float* gate, void* stream);
+
+/* Conformer convolution module after pointwise_conv1 (wav2vec2_model.py:313-393): out = swish(DW(GLU(x)) * scale + shift) with
+ * GLU(a | g) = a * sigmoid(g) over the channel halves of x, DW the depthwise Conv1d of kernel K (odd, <= 63) with zero padding
+ * (K-1)/2 inside each utterance's T-row block (the batch-padded time axis), scale / shift the eval BatchNorm folded by the caller.
+ * x: device fp32 (B*T, 2D); taps: device fp32 (D, K) (depthwise weight already times scale); shift: device fp32 (D);
+ * out: device fp32 (B*T, D).  D % 64 == 0. */
+/* (measured 51.5 us at B*T = 32 x 499, D = 1024: 196 MB at 3.81 TB/s) */
+int s3enc_op_conformer_conv(const float* x, const float* taps, const float* shift, int32_t B, int32_t T, int32_t D, int32_t K,
+                            float* out, void* stream);
+/* Conformer rel_pos self-attention (RelPositionMultiHeadedAttention, wav2vec2_model.py:165-252), fp32, head_dim 64, keys >=
+ * valid[b] masked:  score(i, j) = q_i . k_j + (q_i + qadd_h) . P[(j - i) + T - 1][h*64 ...]  with q the (B*T, 3D) buffer's q
+ * columns (the engine passes (q + pos_bias_u) / 8), P (2T-1, D) = linear_pos(pe) for this T, qadd (H, 64) = (pos_bias_v -
+ * pos_bias_u) / 8.  Neither a (B, H, T, 2T-1) tensor nor the score matrix is stored.  (1.62x the plain fp32 attention's time at
+ * B = 32, H = 16, T = 499.) */
+int s3enc_op_relpos_attention(const float* qkv, float* out, const int32_t* valid, int32_t B, int32_t T, int32_t H, const float* P,
+                              const float* qadd, void* stream);
 
 /* Convolutional position embedding + residual: out = x + GELU(SamePad(Conv1d(D, D, K, padding=K/2, groups=G)(x)) + bias)
  * (make_conv_pos / SamePad, wav2vec2_model.py:2937-2953,1797-1808).  x, out: device fp32 (B, T, D); w_host: HOST fp32

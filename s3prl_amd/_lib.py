@@ -23,7 +23,8 @@ FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hube
 SEL_HIDDEN, SEL_LAYER_OUT, SEL_FFN_OUT = 0, 1, 2
 SELECTIONS = {None: SEL_HIDDEN, "hidden_states": SEL_HIDDEN, "fairseq_layers": SEL_LAYER_OUT,
               "fairseq_layers_before_residual": SEL_FFN_OUT}
-ABI_VERSION = 7
+ABI_VERSION = 8
+POS_ENC = {"rel_pos": 1, "rope": 2}  # s3enc_config.pos_enc_type of a Conformer encoder
 EXCHANGE_COLLECTIVE, EXCHANGE_DIRECT, EXCHANGE_COPY = 0, 1, 2   # S3ENC_EXCHANGE_*
 COPY_HANDLE_BYTES = 256                                         # S3ENC_COPY_HANDLE_BYTES
 
@@ -39,6 +40,7 @@ class S3Config(C.Structure):
         ("compute_dtype", C.c_int32), ("no_feature_layer_norm", C.c_int32), ("pos_conv_depth", C.c_int32), ("wav_norm_eps", C.c_float), ("pred_heads", C.c_int32),
         ("mr_pairs", C.c_int32), ("mr_ratios", C.c_int32 * (2 * (S3ENC_MAX_RES - 1))),
         ("mr_layers", C.c_int32 * (2 * S3ENC_MAX_RES - 1)), ("mr_kernel", C.c_int32), ("mr_plain", C.c_int32),
+        ("layer_type", C.c_int32), ("pos_enc_type", C.c_int32), ("dw_kernel", C.c_int32),
     ]
 
 
@@ -106,6 +108,8 @@ _PROTOS = {
     "s3enc_op_conv0": (C.c_int, [_I32, C.POINTER(_VP), C.POINTER(_I64), _I32, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I32,
                                  _I32, _VP, _VP]),
     "s3enc_op_wavlm_gate": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP]),
+    "s3enc_op_conformer_conv": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP]),
+    "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "s3enc_weighted_sum": (C.c_int, [_VP, _I64, _I32, C.POINTER(C.c_float), _I32, _I64, _I32, _VP, _VP]),
     "s3enc_weighted_sum_backward_scratch": (_I64, [_I64, _I32]),
@@ -185,6 +189,10 @@ def make_config(cfg, dtype: str) -> S3Config:
     c.pos_conv_depth = int(cfg.pos_conv_depth)
     c.wav_norm_eps = float(cfg.wav_norm_eps)
     c.pred_heads = int(cfg.pred_heads)
+    if cfg.layer_type == "conformer":
+        c.layer_type = 1
+        c.pos_enc_type = POS_ENC[cfg.pos_enc_type]
+        c.dw_kernel = int(cfg.depthwise_conv_kernel_size)
     if cfg.family == "multires_hubert":
         pairs = cfg.rate_pairs
         if len(pairs) > S3ENC_MAX_RES - 1:

@@ -86,6 +86,9 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
         conv_pos=cfg.conv_pos, conv_pos_groups=cfg.conv_pos_groups, activation_fn="gelu", pos_conv_depth=cfg.pos_conv_depth,
         conv_feature_layers=str([tuple(t) for t in cfg.conv_layers]),
     )
+    if cfg.layer_type == "conformer":
+        model_cfg.update(layer_type="conformer", pos_enc_type=cfg.pos_enc_type, attn_type=cfg.attn_type,
+                         depthwise_conv_kernel_size=cfg.depthwise_conv_kernel_size)
     if cfg.family == "distiller":
         d = dict(extractor_mode=cfg.extractor_mode, extractor_conv_feature_layers=model_cfg["conv_feature_layers"],
                  conv_pos=cfg.conv_pos, conv_pos_groups=cfg.conv_pos_groups, encoder_layers=cfg.encoder_layers,

@@ -94,6 +94,13 @@ class EncoderConfig:
     block_layers: List[int] = field(default_factory=list)
     conv_adapter_kernel: int = 7          # the reference spells it ``conv_adapator_kernal``
     use_plain_updownsample: bool = False  # ConvDownsampler / ConvUpsampler instead of the two-conv ConvAdapter
+    # wav2vec 2.0 Conformer (family "wav2vec2", ConformerEncoder, wav2vec2_model.py:440-578,3132-3211): layer_type "conformer"
+    # replaces the Transformer block by FFN/2 -> MHA -> conv module -> FFN/2 -> LayerNorm and drops the positional conv;
+    # pos_enc_type "rel_pos" (Transformer-XL relative attention) or "rope" (rotary), attn_type "espnet" only
+    layer_type: str = "transformer"
+    pos_enc_type: str = "abs"
+    attn_type: str = ""
+    depthwise_conv_kernel_size: int = 31
 
     # ---- derived -------------------------------------------------------------------------
     @property
@@ -242,6 +249,20 @@ class EncoderConfig:
                     if s < 1 or s > 4 or (k - 1) % s:
                         raise ValueError("multires_hubert: every rate must divide conv_adapter_kernel - 1 (the transposed "
                                          "conv is run as `rate` interleaved stride-1 convs)")
+        if self.layer_type not in ("transformer", "conformer"):
+            raise ValueError(f"unknown layer_type {self.layer_type!r}")
+        if self.layer_type == "conformer":
+            if self.family != "wav2vec2" or self.pos_conv_depth > 1:
+                raise ValueError("conformer layers are a wav2vec2-family encoder")
+            if self.pos_enc_type not in ("rel_pos", "rope"):
+                # ConformerEncoder is selected only for these two (wav2vec2_model.py:2447-2449); "abs" builds a Transformer
+                # encoder whose layers are ConformerWav2Vec2EncoderLayer with absolute positions
+                raise ValueError(f"conformer pos_enc_type={self.pos_enc_type!r} is not built: only 'rel_pos' and 'rope'")
+            if self.attn_type != "espnet":
+                raise ValueError(f"conformer attn_type={self.attn_type!r} is not built: only 'espnet' (the released models)")
+            k = self.depthwise_conv_kernel_size
+            if k < 1 or k % 2 == 0 or k > 63:
+                raise ValueError("conformer depthwise_conv_kernel_size must be odd and <= 63")
         if self.extractor_mode not in ("default", "layer_norm"):
             raise ValueError(f"unknown extractor_mode {self.extractor_mode!r}")
         dims = {d for d, _, _ in self.conv_layers}
@@ -275,10 +296,16 @@ def config_from_dicts(family: str, model_cfg: Dict, task_cfg: Dict | None = None
         cfg.conv_layers = parse_conv_layers(model_cfg["conv_feature_layers"])
     act = model_cfg.get("activation_fn", "gelu")
     act = getattr(act, "name", act)
-    if str(act) != "gelu":
+    if str(act) != "gelu" and not str(model_cfg.get("layer_type", "")).endswith("conformer"):
         raise ValueError(f"only activation_fn='gelu' is on the hot path, got {act!r}")
-    if str(model_cfg.get("layer_type", "transformer")).endswith("conformer"):
-        raise ValueError("conformer layers are out of scope (SURVEY §2.1)")
+    layer_type = str(getattr(model_cfg.get("layer_type", "transformer"), "name", model_cfg.get("layer_type", "transformer")))
+    if layer_type.endswith("conformer"):  # a str, or a fairseq ChoiceEnum member whose str() is "LAYER_TYPE_CHOICES.conformer"
+        if family != "wav2vec2":
+            raise ValueError("conformer layers are a wav2vec2-family encoder")
+        cfg.layer_type = "conformer"
+        cfg.pos_enc_type = str(model_cfg.get("pos_enc_type", "abs"))
+        cfg.attn_type = str(model_cfg.get("attn_type", "") or "")
+        cfg.depthwise_conv_kernel_size = int(model_cfg.get("depthwise_conv_kernel_size", 31))
     cfg.pos_conv_depth = int(model_cfg.get("pos_conv_depth", 1) or 1)
     if cfg.pos_conv_depth > 1 and family != "wav2vec2":
         raise ValueError("pos_conv_depth > 1 is the data2vec-audio encoder (wav2vec2 family)")

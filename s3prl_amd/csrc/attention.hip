@@ -229,6 +229,181 @@ __global__ __launch_bounds__(256, 3) void attn_f32_kernel(AttnParams p) {
     }
 }
 
+// ---- Conformer rel_pos: Transformer-XL relative attention (wav2vec2_model.py:165-252), exact fp32 -----------------------------
+// score(i, j) = q'_i . k_j + (q'_i + qadd_h) . P_h[(j - i) + T - 1]   (q' = (q + pos_bias_u) / 8 folded into W_q, b_q; qadd =
+// (pos_bias_v - pos_bias_u) / 8; P = linear_pos(pe) of this T: rel_shift maps key j of query i to row (j - i) + T - 1).  The
+// (B, H, T, 2T-1) matrix_bd of the reference is never formed: a wave's 32 queries x 32 keys tile needs the 63 P rows
+// [k0 - q0 + T - 32, k0 - q0 + T + 31), and the next key tile the 63 rows 32 further on — so the wave keeps S_rel = (q + qadd) . P
+// for two 32-row CHUNKS of that window in LDS (a ring of two), and per key tile computes ONE new chunk with the same transposed
+// 32x32 MFMA chain as q . k (P rows as the A operand, straight from global memory / L2: P is (2T-1) x 64 floats per head).
+// The score of (query c, key t) is then S_rel[chunk][w & 31][c], w = 31 + t - c: an LDS gather whose 32 lanes of a half-wave
+// read 32 different banks (row stride 32 floats: bank = c).  Otherwise attn_f32_kernel's loop (no WavLM bias / gate).
+constexpr int RP_CH = 32 * 32;  // floats of one S_rel chunk: [window row (32)][query (32)]
+__global__ __launch_bounds__(256, 2) void attn_relpos_f32_kernel(AttnParams p) {
+    __shared__ __attribute__((aligned(16))) float Ks[2 * KT * KS32];
+    __shared__ __attribute__((aligned(16))) float Vs[2 * KT * KS32];
+    extern __shared__ __attribute__((aligned(16))) float Sr[];  // dynamic (static + this exceed 64 KiB): per wave two chunks
+    const AttnWork wk = attn_work(p);
+    if (!wk.live) return;
+    const int b = wk.b, head = wk.head;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = lane >> 5, l31 = lane & 31;
+    const int D = p.H * HD;
+    const long ld = 3L * D;
+    const float* base = (const float*)p.qkv + (long)b * p.T * ld + head * HD;
+    const int qw = wk.qb * QT + wave * 32;  // the wave's first query
+    const int q_g = qw + l31;
+    const int q_c = q_g < p.T ? q_g : p.T - 1;
+    float* sr = Sr + wave * 2 * RP_CH;
+
+    float qf[32], q2[32];  // B operands: q' for the content-key product, q' + qadd for the position product
+    {
+        const float* qp = base + (long)q_c * ld + half * 32;
+        const float* qa = p.rel_qadd + head * HD + half * 32;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float4 t = *(const float4*)(qp + 4 * i);
+            const float4 a = *(const float4*)(qa + 4 * i);
+            qf[4 * i] = t.x;
+            qf[4 * i + 1] = t.y;
+            qf[4 * i + 2] = t.z;
+            qf[4 * i + 3] = t.w;
+            q2[4 * i] = t.x + a.x;
+            q2[4 * i + 1] = t.y + a.y;
+            q2[4 * i + 2] = t.z + a.z;
+            q2[4 * i + 3] = t.w + a.w;
+        }
+    }
+    // P rows of chunk n: g0 + 32 n + (0..31), g0 = T - 32 - qw; rows outside [0, 2T - 2] only meet padded queries or masked keys
+    // (clamped for the address, their scores never count)
+    const int g0 = p.T - 32 - qw, pmax = 2 * p.T - 2;
+    const float* pbase = p.rel_P + head * HD + half * 32;
+    f32x4 preg[8];
+    auto p_load = [&](int n) {
+        int r = g0 + 32 * n + l31;
+        r = r < 0 ? 0 : (r > pmax ? pmax : r);
+        const float* src = pbase + (long)r * D;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) preg[i] = *(const f32x4*)(src + 4 * i);
+    };
+    auto p_chunk = [&](int n) {  // S_rel chunk n from preg into its ring slot
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(preg[i][0], q2[4 * i], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(preg[i][1], q2[4 * i + 1], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(preg[i][2], q2[4 * i + 2], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(preg[i][3], q2[4 * i + 3], s, 0, 0, 0);
+        }
+        float* dst = sr + (n & 1) * RP_CH + l31;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dst[crow(r, half) * 32] = s[r];
+    };
+
+    f32x16 o0, o1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o0[r] = o1[r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+
+    const int valid = p.valid[b];
+    const int ntiles = (valid + KT - 1) / KT;
+    f32x4 kreg[2], vreg[2];
+    const int srow = tid >> 4, sc4 = tid & 15;
+#define A32_LOAD(kt_)                                                                        \
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                       \
+        int kr_ = (kt_) * KT + srow + 16 * i_;                                               \
+        kr_ = kr_ < p.T ? kr_ : p.T - 1;                                                     \
+        const float* src_ = base + (long)kr_ * ld + sc4 * 4;                                 \
+        kreg[i_] = *(const f32x4*)(src_ + D);                                                \
+        vreg[i_] = *(const f32x4*)(src_ + 2 * D);                                            \
+    }
+#define A32_STORE(buf_)                                                                      \
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                       \
+        *(f32x4*)(Ks + (buf_) * KT * KS32 + (srow + 16 * i_) * KS32 + sc4 * 4) = kreg[i_];   \
+        *(f32x4*)(Vs + (buf_) * KT * KS32 + (srow + 16 * i_) * KS32 + sc4 * 4) = vreg[i_];   \
+    }
+    A32_LOAD(0)
+    A32_STORE(0)
+    p_load(0);
+    p_chunk(0);
+    p_load(1);
+    __syncthreads();
+    for (int kt = 0; kt < ntiles; ++kt) {
+        if (kt + 1 < ntiles) { A32_LOAD(kt + 1) }
+        const float* Kb = Ks + (kt & 1) * KT * KS32;
+        const float* Vb = Vs + (kt & 1) * KT * KS32;
+        p_chunk(kt + 1);  // the window's second half for this tile (chunk kt + 1 replaces chunk kt - 1)
+        if (kt + 1 < ntiles) p_load(kt + 2);
+
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        const float* kp = Kb + l31 * KS32 + half * 32;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float4 kf = *(const float4*)(kp + 4 * i);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[4 * i], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[4 * i + 1], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[4 * i + 2], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[4 * i + 3], s, 0, 0, 0);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's S_rel stores before its gathers
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int w = 31 + crow(r, half) - l31;  // 0 .. 62
+            s[r] += sr[((kt + (w >> 5)) & 1) * RP_CH + (w & 31) * 32 + l31];
+        }
+        if (kt * KT + KT > valid) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = kt * KT + crow(r, half) < valid ? s[r] : -INFINITY;
+        }
+        float mx = s[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
+        mx = xhalf_max(mx);
+        if (__any(mx > m_run + 8.f)) {
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = __expf(m_run - m_new);
+            l_run *= alpha;
+            m_run = m_new;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                o0[r] *= alpha;
+                o1[r] *= alpha;
+            }
+        }
+        float ps = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] = __expf(s[r] - m_run);
+            ps += s[r];
+        }
+        l_run += ps;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float* vp = Vb + crow(r, half) * KS32 + l31;
+            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[0], s[r], o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32], s[r], o1, 0, 0, 0);
+        }
+        if (kt + 1 < ntiles) { A32_STORE((kt + 1) & 1) }
+        __syncthreads();
+    }
+#undef A32_LOAD
+#undef A32_STORE
+    const float l_tot = xhalf_sum(l_run);
+    const float inv = 1.f / l_tot;
+    if (q_g < p.T) {
+        float* op = (float*)p.out + ((long)b * p.T + q_g) * D + head * HD + 4 * half;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            *(float4*)(op + 8 * g) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
+            *(float4*)(op + 32 + 8 * g) = make_float4(o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
+        }
+    }
+}
+
 // ---- round 6: the persistent form of the fp32 kernel (the headline mode's attention) ---------------------------------------------
 // Same arithmetic in the same order as attn_f32_kernel (bit-identical), the life cycle of attn_h16p_kernel below: 3 resident
 // workgroups per CU walk the (batch, head, query block) items of their XCD; the next item's first K / V tile rides in the staging
@@ -1348,6 +1523,15 @@ hipError_t launch_attention(int dtype, const AttnParams& p, hipStream_t s) {
     dim3 grid((unsigned)(8 * units8 * ((p.T + QT - 1) / QT))), block(256);  // XCD-aware 1-D work map (attn_work)
     const size_t dyn = p.bias_table ? (size_t)(p.T + QT - 1 + BIAS_PAD) * sizeof(float) : 0;  // the workgroup's table window
     if (dyn > 24 * 1024) return hipErrorInvalidValue;  // T <= 6017 frames (120 s): the window must fit beside K/V (engine checks)
+    if (p.rel_P) {  // Conformer rel_pos: exact fp32 only, no WavLM bias / gate beside it
+        if (dtype != F32 || !p.rel_qadd || p.bias_table || p.gate || (((uintptr_t)p.rel_P | (uintptr_t)p.rel_qadd) & 15))
+            return hipErrorInvalidValue;
+        const int lds = 4 * 2 * RP_CH * (int)sizeof(float);
+        hipError_t e = ensure_dynamic_lds<attn_relpos_f32_kernel>(lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(attn_relpos_f32_kernel, grid, block, lds, s, p);
+        return hipGetLastError();
+    }
     switch (dtype) {
         case F32:
             if (tuning().attn_persist) {

@@ -102,6 +102,14 @@ __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + e
 #define S3_GELU_Q5 -9.987915400e-04f
 #define S3_GELU_Q6 3.023426980e-04f
 #define S3_GELU_Q7 -2.878726809e-05f
+// swish / SiLU x * sigmoid(x) (the Conformer FFNs, wav2vec2_model.py:396-438): GemmParams::act == 3
+__device__ __forceinline__ float swish_f(float x) { return x / (1.f + __expf(-x)); }
+__device__ __forceinline__ void swish4(float4& v) {
+    v.x = swish_f(v.x);
+    v.y = swish_f(v.y);
+    v.z = swish_f(v.z);
+    v.w = swish_f(v.w);
+}
 __device__ __forceinline__ float gelu_fast(float x) {
     const float ax = fabsf(x);
     const float z = fminf(ax * 0.70710678118654752440f, 16.0f);

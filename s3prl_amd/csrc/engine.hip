@@ -130,6 +130,17 @@ int check_config(const s3enc_config& c) {
     if (c.pos_conv_depth < 0 || c.pos_conv_depth > 16) return fail("config: pos_conv_depth out of range");
     if (!(c.wav_norm_eps >= 0.f) || c.wav_norm_eps > 1.f) return fail("config: wav_norm_eps out of range");
     if (c.pos_conv_depth > 1 && c.family != S3ENC_WAV2VEC2) return fail("config: pos_conv_depth > 1 is the data2vec-audio encoder (wav2vec2 family)");
+    if (c.layer_type < 0 || c.layer_type > 1) return fail("config: unknown layer_type (0 transformer, 1 conformer)");
+    if (c.layer_type == 1) {
+        if (c.family != S3ENC_WAV2VEC2 || c.pos_conv_depth > 1) return fail("config: conformer layers are a wav2vec2-family encoder");
+        if (c.pos_enc_type != 1 && c.pos_enc_type != 2) return fail("config: conformer pos_enc_type must be 1 (rel_pos) or 2 (rope)");
+        if (c.dw_kernel < 1 || c.dw_kernel > 63 || !(c.dw_kernel & 1)) return fail("config: conformer dw_kernel must be odd and <= 63");
+        if (c.compute_dtype != S3ENC_F32)
+            return fail(std::string("config: conformer layers (") + (c.pos_enc_type == 1 ? "rel_pos" : "rope") +
+                        ") are built for compute dtype fp32 only; " +
+                        (c.compute_dtype == 1 ? "bf16" : c.compute_dtype == 2 ? "fp16" : c.compute_dtype == 3 ? "fp32x3" : "fp16x2") +
+                        " is not built");
+    }
     return 0;
 }
 }  // namespace
@@ -267,7 +278,10 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
     UP(upload_f32(e->proj_b, t));
 
     // ---- positional conv: fold weight_norm(dim=2), then pack for the kernel of the compute dtype ----
-    if (c.pos_conv_depth > 1) {
+    // (a Conformer encoder never calls its pos_conv, ConformerEncoder.extract_features: the checkpoint's weights are ignored)
+    const bool conf = c.layer_type == 1;
+    if (conf) {
+    } else if (c.pos_conv_depth > 1) {
         // data2vec (wav2vec2_model.py:2995-3023): plain grouped convs of width max(3, conv_pos / depth), no weight_norm
         const int G = c.conv_pos_groups, Dg = D / G;
         int k = c.conv_pos / c.pos_conv_depth;
@@ -387,7 +401,94 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
         }
         return 0;
     };
-    if (!multires) {
+    // one ConformerEncoderLayer (wav2vec2_model.py:440-578) named `p`; returns non-zero after fail() (e is already deleted)
+    auto load_conformer = [&](const std::string& p, ConformerLayerW& L) -> int {
+        const int K = c.dw_kernel;
+        auto ffn = [&](const std::string& f, DevBuf& lng, DevBuf& lnb, DevBuf& w1, DevBuf& b1, DevBuf& w2, DevBuf& b2) -> int {
+            GET(f + ".layer_norm.weight", D, t);
+            UP(upload_f32(lng, t));
+            GET(f + ".layer_norm.bias", D, t);
+            UP(upload_f32(lnb, t));
+            GET(f + ".w_1.weight", (long)F * D, t);
+            UP(upload_f32(w1, t));
+            GET(f + ".w_1.bias", F, t);
+            UP(upload_f32(b1, t));
+            GET(f + ".w_2.weight", (long)D * F, t);
+            for (auto& x : t) x *= 0.5f;  // x * 0.5 + residual: the half-step folded (exact)
+            UP(upload_f32(w2, t));
+            GET(f + ".w_2.bias", D, t);
+            for (auto& x : t) x *= 0.5f;
+            UP(upload_f32(b2, t));
+            return 0;
+        };
+        if (ffn(p + ".ffn1", L.f1_lng, L.f1_lnb, L.f1_w1, L.f1_b1, L.f1_w2, L.f1_b2)) return 1;
+        if (ffn(p + ".ffn2", L.f2_lng, L.f2_lnb, L.f2_w1, L.f2_b1, L.f2_w2, L.f2_b2)) return 1;
+        GET(p + ".self_attn_layer_norm.weight", D, t);
+        UP(upload_f32(L.at_lng, t));
+        GET(p + ".self_attn_layer_norm.bias", D, t);
+        UP(upload_f32(L.at_lnb, t));
+        const bool relpos = c.pos_enc_type == 1;
+        std::vector<float> pu, pv;
+        if (relpos) {
+            GET(p + ".self_attn.pos_bias_u", D, pu);
+            GET(p + ".self_attn.pos_bias_v", D, pv);
+        }
+        const float qs = 1.0f / std::sqrt((float)(D / H));
+        std::vector<float> w(3L * D * D), bb(3L * D);
+        const char* names[3] = {"linear_q", "linear_k", "linear_v"};
+        for (int s = 0; s < 3; ++s) {
+            GET(p + ".self_attn." + names[s] + ".weight", (long)D * D, t);
+            GET(p + ".self_attn." + names[s] + ".bias", D, t2);
+            const float sc = s == 0 ? qs : 1.f;
+            for (long i = 0; i < (long)D * D; ++i) w[(long)s * D * D + i] = t[i] * sc;
+            for (int i = 0; i < D; ++i) bb[(long)s * D + i] = (s == 0 && relpos ? t2[i] + pu[i] : t2[i]) * sc;
+        }
+        UP(upload_f32(L.wqkv, w));
+        UP(upload_f32(L.bqkv, bb));
+        GET(p + ".self_attn.linear_out.weight", (long)D * D, t);
+        UP(upload_f32(L.wo, t));
+        GET(p + ".self_attn.linear_out.bias", D, t);
+        UP(upload_f32(L.bo, t));
+        if (relpos) {
+            GET(p + ".self_attn.linear_pos.weight", (long)D * D, t);
+            UP(upload_f32(L.wpos, t));
+            for (int i = 0; i < D; ++i) t2[i] = (pv[i] - pu[i]) * qs;
+            t2.resize(D);
+            UP(upload_f32(L.qadd, t2));
+        }
+        GET(p + ".conv_module.layer_norm.weight", D, t);
+        UP(upload_f32(L.cv_lng, t));
+        GET(p + ".conv_module.layer_norm.bias", D, t);
+        UP(upload_f32(L.cv_lnb, t));
+        GET(p + ".conv_module.pointwise_conv1.weight", 2L * D * D, t);
+        UP(upload_f32(L.pw1, t));
+        GET(p + ".conv_module.pointwise_conv2.weight", (long)D * D, t);
+        UP(upload_f32(L.pw2, t));
+        std::vector<float> dw, g, bt, mu, var;
+        GET(p + ".conv_module.depthwise_conv.weight", (long)D * K, dw);
+        GET(p + ".conv_module.batch_norm.weight", D, g);
+        GET(p + ".conv_module.batch_norm.bias", D, bt);
+        GET(p + ".conv_module.batch_norm.running_mean", D, mu);
+        GET(p + ".conv_module.batch_norm.running_var", D, var);
+        std::vector<float> sh(D);
+        for (int ch = 0; ch < D; ++ch) {  // BatchNorm1d eval (eps 1e-5): y = (x - mean) * gamma / sqrt(var + eps) + beta
+            const double sc = (double)g[ch] / std::sqrt((double)var[ch] + 1e-5);
+            for (int k = 0; k < K; ++k) dw[(long)ch * K + k] = (float)(dw[(long)ch * K + k] * sc);
+            sh[ch] = (float)((double)bt[ch] - (double)mu[ch] * sc);
+        }
+        UP(upload_f32(L.taps, dw));
+        UP(upload_f32(L.shift, sh));
+        GET(p + ".final_layer_norm.weight", D, t);
+        UP(upload_f32(L.fin_g, t));
+        GET(p + ".final_layer_norm.bias", D, t);
+        UP(upload_f32(L.fin_b, t));
+        return 0;
+    };
+    if (conf) {
+        e->cf_layers.resize(c.encoder_layers);
+        for (int l = 0; l < c.encoder_layers; ++l)
+            if (load_conformer("encoder.layers." + std::to_string(l), e->cf_layers[l])) return 1;
+    } else if (!multires) {
         e->layers.resize(c.encoder_layers);
         for (int l = 0; l < c.encoder_layers; ++l)
             if (load_layer("encoder.layers." + std::to_string(l), e->layers[l])) return 1;
@@ -595,6 +696,198 @@ struct Sink {
 int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                  const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
+// ---- Conformer position tables (host, the reference's fp32 formulas), grown to the largest T seen --------------------------------
+// rope: inv_freq = 1 / 10000^(2i / 64), angle = t * inv_freq in fp32 (RotaryPositionalEmbedding, wav2vec2_model.py:40-71)
+// rel_pos: div_term = exp(2i * -(ln 10000 / D)), pe[r] = {sin, cos}(p * div_term) of position p = (Tm - 1) - r (RelPositionalEncoding,
+//   :1525-1588: flipped positive half, then the negative half without its 0).  A growth waits for the device (the old table may be in
+//   use by forwards in flight): once per new longest batch.
+int ensure_conformer_tables(s3enc_handle e, hipStream_t st, long T) {
+    const s3enc_config& c = e->cfg;
+    const int D = c.embed_dim;
+    if (c.pos_enc_type == 2 && T > e->rope_T) {
+        std::vector<float> tab((size_t)T * 64);
+        float inv[32];
+        for (int i = 0; i < 32; ++i) inv[i] = 1.0f / std::pow(10000.0f, (float)(2 * i) / 64.0f);
+        for (long t = 0; t < T; ++t)
+            for (int i = 0; i < 32; ++i) {
+                const float a = (float)t * inv[i];
+                tab[(size_t)t * 64 + i] = (float)std::cos((double)a);
+                tab[(size_t)t * 64 + 32 + i] = (float)std::sin((double)a);
+            }
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(upload_f32(e->rope_tab, tab));
+        e->rope_T = (int)T;
+    }
+    if (c.pos_enc_type == 1 && T > e->pe_T) {
+        const long R = 2 * T - 1;
+        std::vector<float> pe((size_t)R * D);
+        const float k = (float)(-(std::log(10000.0) / D));
+        std::vector<float> div(D / 2);
+        for (int i = 0; i < D / 2; ++i) div[i] = std::exp((float)(2 * i) * k);
+        for (long r = 0; r < R; ++r) {
+            const long pos = (T - 1) - r;  // the reference evaluates -1 * position * div_term for the negative half
+            for (int i = 0; i < D / 2; ++i) {
+                const float a = (float)(pos < 0 ? -pos : pos) * div[i];
+                const float x = pos < 0 ? -a : a;
+                pe[(size_t)r * D + 2 * i] = (float)std::sin((double)x);
+                pe[(size_t)r * D + 2 * i + 1] = (float)std::cos((double)x);
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(upload_f32(e->pe_tab, pe));
+        e->pe_T = (int)T;
+    }
+    return 0;
+}
+
+struct ConformerBufs {
+    void *x32, *xpc, *xT, *qkv, *attn, *tmp1, *tmp2, *hbuf, *cbuf, *pbuf;
+};
+
+// The Conformer stack behind post_extract_proj (ConformerEncoder.extract_features, wav2vec2_model.py:3170-3211; layer :523-578),
+// exact fp32.  xproj: (B, T, D) with padded frames zero.  States: the input of every layer and the encoder output.
+int conformer_tail(s3enc_handle e, hipStream_t st, Sink& sink, int B, long T, const int* d_valid, float* xproj, const ConformerBufs& w) {
+    const s3enc_config& c = e->cfg;
+    const int D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
+    const long M = (long)B * T;
+    const double gM = (double)M;
+    const bool prel = c.layer_norm_first != 0, relpos = c.pos_enc_type == 1;
+    static const int dbg_stop = getenv("S3ENC_DEBUG_STOP") ? atoi(getenv("S3ENC_DEBUG_STOP")) : 0;
+    if (ensure_conformer_tables(e, st, T)) return 1;
+    float *xT = (float*)w.xT, *qkv = (float*)w.qkv, *attn = (float*)w.attn, *tmp1 = (float*)w.tmp1, *tmp2 = (float*)w.tmp2;
+    float *hbuf = (float*)w.hbuf, *cbuf = (float*)w.cbuf, *pbuf = (float*)w.pbuf;
+    auto other = [&](const float* busy) { return busy == (const float*)w.x32 ? (float*)w.xpc : (float*)w.x32; };
+    auto gemm = [&](const char* kind, const float* A, const DevBuf& W, const DevBuf* bias, int M_, int N, int K, int act,
+                    const float* res, float* out, long ldo) -> hipError_t {
+        GemmParams g{};
+        g.A = A;
+        g.lda = K;
+        g.W = W.p;
+        g.bias = bias ? (const float*)bias->p : nullptr;
+        g.M = M_;
+        g.N = N;
+        g.K = K;
+        g.batches = 1;
+        g.act = act;
+        g.residual = res;
+        g.out32 = out;
+        g.ldo = ldo;
+        Prof pr(e, st, kind, 2.0 * M_ * N * K, ((double)M_ * K + (double)N * K + (double)M_ * N * (res ? 2 : 1)) * 4);
+        return launch_gemm(F32, g, st);
+    };
+    auto ln = [&](const char* kind, const float* x, const DevBuf& g, const DevBuf& b, float* y, const LnAcc& fa) -> hipError_t {
+        Prof pr(e, st, kind, 0, gM * D * 8);
+        return launch_layernorm(F32, x, (const float*)g.p, (const float*)b.p, M, D, 0, y, nullptr, st, fa);
+    };
+
+    // hidden_states[0]: the layer-0 input — pre-LN: xproj itself (post_extract_proj wrote it into its slot), post-LN:
+    // encoder.layer_norm(xproj) (applied before layer 0, wav2vec2_model.py:3182-3183)
+    float* x_cur;
+    if (prel) {
+        x_cur = xproj;
+    } else {
+        x_cur = sink.slot32(0) ? sink.slot32(0) : other(xproj);
+        HIP_TRY(ln("layernorm:enc", xproj, e->eln_g, e->eln_b, x_cur, sink.acc(0, 2)));
+        HIP_TRY(sink.done(0));
+    }
+    for (int l = 0; l < NL; ++l) {
+        const ConformerLayerW& L = e->cf_layers[l];
+        if (dbg_stop == 40 + l) return 0;
+        // x + 0.5 FFN1(x): swish in fc1's epilogue, the 0.5 in w_2 / b_2, the residual in fc2's epilogue
+        HIP_TRY(ln("layernorm:ffn", x_cur, L.f1_lng, L.f1_lnb, xT, LnAcc()));
+        HIP_TRY(gemm("gemm:ffn_w1", xT, L.f1_w1, &L.f1_b1, (int)M, F, D, 3, nullptr, hbuf, F));
+        HIP_TRY(gemm("gemm:ffn_w2", hbuf, L.f1_w2, &L.f1_b2, (int)M, D, F, 0, x_cur, tmp1, D));
+        if (l == 0) e->taps["ffn1_0"] = {tmp1, M * D, F32};
+        // x + MHA(LN(x))
+        HIP_TRY(ln("layernorm:attn", tmp1, L.at_lng, L.at_lnb, xT, LnAcc()));
+        if (relpos) {
+            HIP_TRY(gemm("gemm:qkv", xT, L.wqkv, &L.bqkv, (int)M, 3 * D, D, 0, nullptr, qkv, 3L * D));
+            // P = linear_pos(pe) for this T: the centre 2T - 1 rows of the table (depends on T and the layer only)
+            GemmParams g{};
+            g.A = (const float*)e->pe_tab.p + (long)(e->pe_T - T) * D;
+            g.lda = D;
+            g.W = L.wpos.p;
+            g.M = (int)(2 * T - 1);
+            g.N = D;
+            g.K = D;
+            g.batches = 1;
+            g.out32 = pbuf;
+            g.ldo = D;
+            Prof pr(e, st, "gemm:linear_pos", 2.0 * g.M * D * D, ((double)g.M * D * 2 + (double)D * D) * 4);
+            HIP_TRY(launch_gemm(F32, g, st));
+        } else {
+            // rope: q, k from rot(LN(x)), v from LN(x) (RotaryPositionMultiHeadedAttention, wav2vec2_model.py:275-310)
+            {
+                Prof pr(e, st, "rope", 0, gM * D * 8);
+                HIP_TRY(launch_rope(xT, (const float*)e->rope_tab.p, M, (int)T, D, tmp2, st));
+            }
+            HIP_TRY(gemm("gemm:qk", tmp2, L.wqkv, &L.bqkv, (int)M, 2 * D, D, 0, nullptr, qkv, 3L * D));
+            GemmParams g{};
+            g.A = xT;
+            g.lda = D;
+            g.W = (const float*)L.wqkv.p + 2L * D * D;
+            g.bias = (const float*)L.bqkv.p + 2L * D;
+            g.M = (int)M;
+            g.N = D;
+            g.K = D;
+            g.batches = 1;
+            g.out32 = qkv + 2L * D;
+            g.ldo = 3L * D;
+            Prof pr(e, st, "gemm:v", 2.0 * gM * D * D, (gM * D * 2 + (double)D * D) * 4);
+            HIP_TRY(launch_gemm(F32, g, st));
+        }
+        {
+            AttnParams a{};
+            a.qkv = qkv;
+            a.out = attn;
+            a.valid = d_valid;
+            a.B = B;
+            a.T = (int)T;
+            a.H = H;
+            a.rel_P = relpos ? pbuf : nullptr;
+            a.rel_qadd = relpos ? (const float*)L.qadd.p : nullptr;
+            Prof pr(e, st, relpos ? "attention:relpos" : "attention", (relpos ? 6.0 : 4.0) * B * H * (double)T * T * 64, gM * 4 * D * 4);
+            HIP_TRY(launch_attention(F32, a, st));
+        }
+        if (l == 0) e->taps["attn0"] = {attn, M * D, F32};
+        HIP_TRY(gemm("gemm:out_proj", attn, L.wo, &L.bo, (int)M, D, D, 0, tmp1, tmp2, D));
+        // x + Conv(x): LN -> pointwise_conv1 -> [GLU, depthwise conv, BatchNorm, swish] -> pointwise_conv2 + residual
+        HIP_TRY(ln("layernorm:conv", tmp2, L.cv_lng, L.cv_lnb, xT, LnAcc()));
+        HIP_TRY(gemm("gemm:pw1", xT, L.pw1, nullptr, (int)M, 2 * D, D, 0, nullptr, cbuf, 2L * D));
+        {
+            ConformerConvParams p{};
+            p.x = cbuf;
+            p.taps = (const float*)L.taps.p;
+            p.shift = (const float*)L.shift.p;
+            p.out = attn;
+            p.B = B;
+            p.T = (int)T;
+            p.D = D;
+            p.K = c.dw_kernel;
+            Prof pr(e, st, "conformer_conv", 2.0 * gM * D * c.dw_kernel, gM * D * 12);
+            HIP_TRY(launch_conformer_conv(p, st));
+        }
+        if (l == 0) e->taps["conv0_mod"] = {attn, M * D, F32};
+        HIP_TRY(gemm("gemm:pw2", attn, L.pw2, nullptr, (int)M, D, D, 0, tmp2, tmp1, D));
+        // x + 0.5 FFN2(x), then final_layer_norm: the next layer's input (a state, except behind a pre-LN stack's last layer)
+        HIP_TRY(ln("layernorm:ffn", tmp1, L.f2_lng, L.f2_lnb, xT, LnAcc()));
+        HIP_TRY(gemm("gemm:ffn_w1", xT, L.f2_w1, &L.f2_b1, (int)M, F, D, 3, nullptr, hbuf, F));
+        HIP_TRY(gemm("gemm:ffn_w2", hbuf, L.f2_w2, &L.f2_b2, (int)M, D, F, 0, tmp1, tmp2, D));
+        if (l == 0) e->taps["ffn2_0"] = {tmp2, M * D, F32};
+        const int si_next = (l + 1 < NL || !prel) ? l + 1 : -1;
+        float* x_next = sink.slot32(si_next) ? sink.slot32(si_next) : other(x_cur);
+        HIP_TRY(ln("layernorm:final", tmp2, L.fin_g, L.fin_b, x_next, sink.acc(si_next, 2)));
+        HIP_TRY(sink.done(si_next));
+        x_cur = x_next;
+    }
+    if (prel) {  // encoder.layer_norm on the output (TransformerEncoder.forward, wav2vec2_model.py:3046-3052)
+        float* y = sink.slot32(NL) ? sink.slot32(NL) : other(x_cur);
+        HIP_TRY(ln("layernorm:enc", x_cur, e->eln_g, e->eln_b, y, sink.acc(NL, 2)));
+        HIP_TRY(sink.done(NL));
+    }
+    return 0;
+}
+
 // ---- forward chain: one event per device, re-recorded behind every forward; the next forward (any handle, any stream) waits for it on
 // the device.  hipStreamWaitEvent captures the record that is current when it is called, so re-using one event is safe; a stream that
 // waits for an event recorded on itself waits for nothing new.  Host cost: two runtime calls per forward under one mutex.
@@ -670,6 +963,10 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     if (fo.selection < 0 || fo.selection > 2) return fail("s3enc_forward: unknown selection");
     if ((dist || mr) && fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: DistilHuBERT / multires-HuBERT have one selection (their hidden_states list)");
+    const bool conf = c.layer_type == 1;
+    if (conf && fo.selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_forward: feature_selection is not defined for a Conformer encoder (the reference's ConformerEncoder records "
+                    "layer results only for a target layer and returns an empty list)");
     const int NS = num_states(c, fo.selection);
     if (fo.featurize && !fo.w) return fail("s3enc_forward: featurize needs feat_w");
     if (!fo.featurize && fo.out_dtype != F32 && (fo.out_dtype != dt || dt == F32))
@@ -700,6 +997,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     }
     if ((uintptr_t)out & 15) return fail("s3enc_forward: out must be 16-byte aligned");
     if (c.rel_pos && T > 6000) return fail("s3enc_forward: WavLM relative-position window limited to 6000 frames (120 s) per batch");
+    if (conf && T > 100000) return fail("s3enc_forward: Conformer position tables are limited to 100000 frames (max_source_positions)");
     std::vector<int> valid(B);
     for (int b = 0; b < B; ++b) {
         valid[b] = valid_frames(c, lengths[b], n_max);
@@ -773,7 +1071,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     const bool featln = !c.no_feature_layer_norm;
     const bool ffn_tap = fo.selection == S3ENC_SEL_FFN_OUT;
     const long HW = std::max<long>(F, (long)NH * D);  // widest row of the FFN / prediction-head intermediate
-    void *actA, *actB, *tmp32, *feat32, *featT, *x32, *xpc, *xT, *qkv, *attn, *tmp1, *tmp2, *hbuf, *gate, *ffnbuf, *lnst;
+    void *actA, *actB, *tmp32, *feat32, *featT, *x32, *xpc, *xT, *qkv, *attn, *tmp1, *tmp2, *hbuf, *gate, *ffnbuf, *lnst, *cbuf, *pbuf;
     for (int pass = 0; pass < 2; ++pass) {
         Bump wb(pass ? e->ws.p : nullptr);
         // conv0's output in the compute dtype; in the fp16x2 hybrid conv2, conv4, ... write fp32 rows back here: L[2] <= L[0] / 2
@@ -795,6 +1093,8 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         hbuf = wb.take((size_t)M * HW * es);
         gate = gated ? wb.take((size_t)B * H * T * 4) : nullptr;
         ffnbuf = (ffn_tap && (fo.featurize || fo.out_dtype != F32)) ? wb.take((size_t)M * D * 4) : nullptr;
+        cbuf = conf ? wb.take((size_t)M * 2 * D * 4) : nullptr;                                   // Conformer: pointwise_conv1 output
+        pbuf = (conf && c.pos_enc_type == 1) ? wb.take((size_t)(2 * T - 1) * D * 4) : nullptr;    // rel_pos: linear_pos(pe) of this T
         if (!pass) HIP_TRY(e->ws.ensure_on_stream(wb.off + 4096, st));
         // (diagnostic, profiles/r06d_concurrent_forwards_exclusions.md: S3ENC_DEBUG_POISON=1 fills the workspace with NaN patterns in front of
         //  every forward — every buffer is written before it is read, so a correct forward does not change; a read that overtakes its
@@ -948,7 +1248,9 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         e->taps["feat_ln"] = {featT, M * C, proj32 ? (int)F32 : dt};
         if (dbg_stop == 20) return 0;
     }
-    const int si_proj = dist ? 0 : -1;  // DistilHuBERT: hidden_states[0] = feat_final, padded frames zeroed in place
+    // DistilHuBERT: hidden_states[0] = feat_final, padded frames zeroed in place; a pre-LN Conformer's hidden_states[0] is the same
+    // tensor (ConformerEncoder has no positional conv and zeroes the padded frames, wav2vec2_model.py:3170-3175)
+    const int si_proj = (dist || (conf && c.layer_norm_first)) ? 0 : -1;
     float* xproj = sink.slot32(si_proj) ? sink.slot32(si_proj) : (float*)x32;
     {
         GemmParams g{};
@@ -985,6 +1287,10 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         std::vector<const int*> dv(plan.blocks.size(), d_valid);
         for (size_t bi = 1; bi < plan.blocks.size(); ++bi) dv[bi] = (const int*)(d_tbl + (size_t)B * 20) + (bi - 1) * (size_t)B;
         return multires_tail(e, st, B, plan, dv, xproj, out, (long)layer_stride, fo) ? 1 : 0;
+    }
+    if (conf) {
+        ConformerBufs cb{x32, xpc, xT, qkv, attn, tmp1, tmp2, hbuf, cbuf, pbuf};
+        return conformer_tail(e, st, sink, B, T, d_valid, xproj, cb);
     }
     // positional conv + residual; hidden_states[0]
     float* x_cur;          // the fp32 residual stream entering the layer loop
@@ -1381,6 +1687,8 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
     if (selection < 0 || selection > 2) return fail("s3enc_num_states: unknown selection");
     if ((h->cfg.family == S3ENC_DISTILLER || h->cfg.family == S3ENC_MULTIRES) && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: DistilHuBERT / multires-HuBERT have one selection (their hidden_states list)");
+    if (h->cfg.layer_type == 1 && selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_num_states: feature_selection is not defined for a Conformer encoder");
     *n = num_states(h->cfg, selection);
     return 0;
 }

@@ -322,6 +322,19 @@ struct LayerW {
     DevBuf wqkv3, wo3, w13, w23;  // S3ENC_F32X3: pair-packed bf16 hi / lo images of the four weight matrices
     DevBuf grep_w, grep_b, grep_a;
 };
+// wav2vec 2.0 Conformer layer (ConformerEncoderLayer, wav2vec2_model.py:440-578), exact fp32.  Packed at s3enc_create:
+//   FFN1 / FFN2: the 0.5 of `x * 0.5 + residual` folded into w_2 and its bias (a power of two: exact);
+//   q | k | v: one (3D, D) matrix with head_dim^-0.5 folded into the q rows and bias, rel_pos: (b_q + pos_bias_u) * head_dim^-0.5;
+//   rel_pos: linear_pos (D, D) and qadd = (pos_bias_v - pos_bias_u) * head_dim^-0.5 (the attention kernel's position term);
+//   conv module: pointwise_conv1 (2D, D), the depthwise taps (D, K) times BatchNorm's gamma / sqrt(var + eps) and the shift
+//   beta - mean * gamma / sqrt(var + eps), pointwise_conv2 (D, D).
+struct ConformerLayerW {
+    DevBuf f1_lng, f1_lnb, f1_w1, f1_b1, f1_w2, f1_b2;
+    DevBuf at_lng, at_lnb, wqkv, bqkv, wo, bo, wpos, qadd;
+    DevBuf cv_lng, cv_lnb, pw1, taps, shift, pw2;
+    DevBuf f2_lng, f2_lnb, f2_w1, f2_b1, f2_w2, f2_b2;
+    DevBuf fin_g, fin_b;
+};
 struct ConvW {
     DevBuf w, bias, lng, lnb;  // w: conv0 fp32 [C][k]; conv>=1 compute dtype [C][k*Cin]
     DevBuf w3;                 // S3ENC_F32X3: pair-packed image of w (conv >= 1)
@@ -377,6 +390,13 @@ struct s3enc_encoder {
     DevBuf fln_g, fln_b, proj_w, proj_b, pos_w, pos_b, eln_g, eln_b;
     DevBuf proj_w3, pos_w3;  // S3ENC_F32X3
     std::vector<LayerW> layers;
+    std::vector<ConformerLayerW> cf_layers;  // cfg.layer_type == 1 (then `layers` is empty)
+    // Conformer position tables, built on the host with the reference's fp32 formulas for the largest T seen and grown on demand
+    // (rows for a smaller T are a window: every entry depends on its position only):
+    //   rope:    (rope_T, 64) rows {cos[32], sin[32]} of t * inv_freq (RotaryPositionalEmbedding, wav2vec2_model.py:40-71)
+    //   rel_pos: (2 pe_T - 1, D) sin / cos of relative positions pe_T - 1 ... -(pe_T - 1) (RelPositionalEncoding, :1525-1588)
+    DevBuf rope_tab, pe_tab;
+    int rope_T = 0, pe_T = 0;
     DevBuf rel_table;  // WavLM: [H][2R+1], entry (h, rel + R), R = max_distance (the bucket saturates there)
     int rel_R = 0;
     // data2vec positional-conv stack (cfg.pos_conv_depth > 1): per block the packed conv weight + bias; pos_k = the kernel

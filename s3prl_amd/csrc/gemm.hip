@@ -247,7 +247,9 @@ __global__ __launch_bounds__(256, ROWB == 128 ? 2 : (GLDS ? 5 : 3)) void gemm_ke
                 const int m = m0 + wr * 64 + i * 32 + row;
                 if (m < p.M && n_ok) {
                     v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-                    if (p.act) {
+                    if (p.act == 3) {
+                        swish4(v);
+                    } else if (p.act) {
                         if (!std::is_same<T, float>::value || p.act == 2) {
                             gelu_fast4(v);
                         } else {
@@ -283,7 +285,7 @@ __global__ __launch_bounds__(256, ROWB == 128 ? 2 : (GLDS ? 5 : 3)) void gemm_ke
                 const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                 if (m >= p.M) continue;
                 float v = acc[i][j][r] + bias;
-                if (p.act) v = (p.act == 2) ? gelu_fast(v) : gelu_mode<T>(v);
+                if (p.act) v = p.act == 3 ? swish_f(v) : (p.act == 2) ? gelu_fast(v) : gelu_mode<T>(v);
                 const long o = ob + (long)m * p.ldo + n;
                 if (p.residual) v += p.residual[o];
                 if (m >= limit) v = 0.f;
@@ -333,6 +335,7 @@ hipError_t launch_gemm(int dtype, const GemmParams& p0, hipStream_t stream) {
     if (p.variant < 0) p.variant = tuning().gemm_variant;  // default 3: 64-byte stages + LDS-DMA (register staging for a ragged K)
     if (p.M <= 0 || p.N <= 0 || p.batches <= 0) return hipSuccess;
     if (dtype == F32 && p.act == 1 && tuning().gelu32 == 1) p.act = 2;  // fp32 products, the one-transcendental GELU
+    if (p.act == 3 && dtype != F32) return hipErrorInvalidValue;  // swish: the exact-fp32 kernels only (Conformer handles)
     if (p.res_ln_stats && (dtype == F32 || !p.res_ln_g || !p.res_ln_b || !gemm16_res_ln_ok(dtype, p))) return hipErrorInvalidValue;
     if (p.wsplit) {
         if (dtype == F32) return hipErrorInvalidValue;
@@ -345,7 +348,7 @@ hipError_t launch_gemm(int dtype, const GemmParams& p0, hipStream_t stream) {
         }
     }
     p.mxw = 0;
-    if (dtype == F32 && gemm_x3_eligible(p)) {
+    if (dtype == F32 && p.act != 3 && gemm_x3_eligible(p)) {
         if (gemm_tile_eligible(3, p)) return launch_gemm_tile(3, p, stream);
         return launch_gemm_x3(p, stream);
     }

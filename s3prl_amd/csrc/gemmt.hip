@@ -270,7 +270,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
                 const int m = m0 + wr * (TM * 32) + i * 32 + row;
                 if (m < p.M && n_ok) {
                     v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-                    if (p.act) {
+                    if (p.act == 3) {
+                        swish4(v);
+                    } else if (p.act) {
                         if (X3 || p.act == 2) {
                             gelu_fast4(v);  // the packed one-transcendental form (act 2: asked for in fp32 too)
                         } else {

@@ -117,7 +117,8 @@ struct GemmParams {
     const void* W_x3 = nullptr;  // fp32 mode only: the same matrix pair-packed as bf16 hi / lo (gemm_x3.hip), or null
     const float* bias;
     int M, N, K, batches;
-    int act;                // 0 none, 1 erf-GELU
+    int act;                // 0 none, 1 erf-GELU (2: its one-transcendental form, set by launch_gemm), 3 swish x*sigmoid(x)
+                            // (Conformer FFNs; the fp32 kernels of gemm.hip / gemmt.hip only)
     const float* residual;  // fp32, indexed like out32; added after the activation
     const int* row_limit;   // per batch: rows >= row_limit[b] are written as 0
     // round 6 (second session): the residual is NOT read as stored — `residual` holds the INPUT rows t of a LayerNorm and the epilogue
@@ -235,11 +236,28 @@ struct AttnParams {
     int out_f32 = 0;          // 16-bit kernels only: write the (B*T, D) result as fp32 (S3ENC_F16X2: out_proj then reads it
                               // through the three-term GEMM — its operand's rounding is the largest non-conv term of the mode's error)
     int probe = 0;            // timing probes (tools/micro/attn_lab.hip builds the kernels with S3_ATTN_PROBE; ignored otherwise)
+    // Conformer rel_pos (Transformer-XL relative attention, wav2vec2_model.py:165-252), fp32 only: score(i, j) += (q_i + qadd_h) .
+    // rel_P[(j - i) + T - 1][h*64 .. h*64+63] with rel_P = linear_pos(pe) for THIS T ((2T-1, D) rows, row stride D) and
+    // qadd = (pos_bias_v - pos_bias_u) * head_dim^-0.5 (q arrives as (q + pos_bias_u) * head_dim^-0.5).  No bias table / gate.
+    const float* rel_P = nullptr;
+    const float* rel_qadd = nullptr;  // (H, 64)
 };
 hipError_t launch_attention(int dtype, const AttnParams& p, hipStream_t s);
 // WavLM gate (wavlm/modules.py:535-549) from the layer input x (fp32 rows of D): gate[b][h][t]
 hipError_t launch_wavlm_gate(const float* x, const float* grep_w /*[8][64]*/, const float* grep_b /*[8]*/,
                              const float* grep_a /*[H]*/, int B, int T, int H, float* gate, hipStream_t s);
+
+// ---- conformer.hip (wav2vec 2.0 Conformer block, wav2vec2_model.py:313-393,25-71) ------------------------------------
+struct ConformerConvParams {
+    const float* x;      // (B*T, 2D) fp32: pointwise_conv1's output (a | g halves of the GLU)
+    const float* taps;   // (D, K) depthwise taps with BatchNorm's scale folded in
+    const float* shift;  // (D) BatchNorm's folded shift
+    float* out;          // (B*T, D) fp32 = swish(BN(DW(GLU(x))))
+    int B, T, D, K;      // K odd, <= 63; zero padding (K-1)/2 inside each utterance's T-row block
+};
+hipError_t launch_conformer_conv(const ConformerConvParams& p, hipStream_t s);
+// rot(x) per 64-wide head chunk; table: (>= T, 64) fp32 rows {cos[32], sin[32]} of position t = row % T
+hipError_t launch_rope(const float* x, const float* table, long rows, int T, int D, float* out, hipStream_t s);
 
 // ---- posconv.hip --------------------------------------------------------------------------------------------
 struct PosConvParams {

@@ -219,6 +219,41 @@ int s3enc_op_attention(int32_t dtype, const void* qkv, void* out, const int32_t*
     return 0;
 }
 
+int s3enc_op_conformer_conv(const float* x, const float* taps, const float* shift, int32_t B, int32_t T, int32_t D, int32_t K,
+                            float* out, void* stream) {
+    if (!x || !taps || !shift || !out) return fail("s3enc_op_conformer_conv: null argument");
+    if (B <= 0 || T <= 0 || D <= 0 || D % 64) return fail("s3enc_op_conformer_conv: bad shape (D % 64 == 0)");
+    if (K < 1 || K > 63 || !(K & 1)) return fail("s3enc_op_conformer_conv: K must be odd and <= 63");
+    ConformerConvParams p{};
+    p.x = x;
+    p.taps = taps;
+    p.shift = shift;
+    p.out = out;
+    p.B = B;
+    p.T = T;
+    p.D = D;
+    p.K = K;
+    HIP_TRY(launch_conformer_conv(p, (hipStream_t)stream));
+    return 0;
+}
+
+int s3enc_op_relpos_attention(const float* qkv, float* out, const int32_t* valid, int32_t B, int32_t T, int32_t H, const float* P,
+                              const float* qadd, void* stream) {
+    if (!qkv || !out || !valid || !P || !qadd) return fail("s3enc_op_relpos_attention: null argument");
+    if (B <= 0 || T <= 0 || H <= 0) return fail("s3enc_op_relpos_attention: bad shape");
+    AttnParams a{};
+    a.qkv = qkv;
+    a.out = out;
+    a.valid = valid;
+    a.B = B;
+    a.T = T;
+    a.H = H;
+    a.rel_P = P;
+    a.rel_qadd = qadd;
+    HIP_TRY(launch_attention(F32, a, (hipStream_t)stream));
+    return 0;
+}
+
 int s3enc_op_conv0(int32_t dtype, const float* const* wavs, const int64_t* lengths, int32_t B, int64_t n_max, int32_t normalize,
                    const float* w0, const float* bias, const float* gn_gamma, const float* gn_beta, const float* ln_gamma,
                    const float* ln_beta, int32_t C, int32_t stride, void* out, void* stream) {

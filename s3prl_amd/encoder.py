@@ -25,6 +25,9 @@ class HipEncoder:
         import torch
 
         cfg.validate()
+        if cfg.layer_type == "conformer" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            # s3enc_create refuses it with this message too; raised here as the configuration error it is
+            raise ValueError(f"conformer layers ({cfg.pos_enc_type}) are built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")

@@ -52,6 +52,10 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         s["encoder.pos_conv.0.weight_v"] = (D, D // cfg.conv_pos_groups, cfg.conv_pos)
     s["encoder.layer_norm.weight"] = (D,)
     s["encoder.layer_norm.bias"] = (D,)
+    if cfg.layer_type == "conformer":  # (the pos_conv above is in every checkpoint, ConformerEncoder never calls it)
+        for l in range(cfg.encoder_layers):
+            _conformer_shapes(s, f"encoder.layers.{l}", cfg)
+        return s
     for l in range(cfg.encoder_layers):
         p = f"encoder.layers.{l}"
         _layer_shapes(s, p, D, F)
@@ -81,6 +85,36 @@ def _layer_shapes(s: Dict[str, tuple], p: str, D: int, F: int) -> None:
     s[f"{p}.fc1.bias"] = (F,)
     s[f"{p}.fc2.weight"] = (D, F)
     s[f"{p}.fc2.bias"] = (D,)
+    s[f"{p}.final_layer_norm.weight"] = (D,)
+    s[f"{p}.final_layer_norm.bias"] = (D,)
+
+
+def _conformer_shapes(s: Dict[str, tuple], p: str, cfg: EncoderConfig) -> None:
+    """ConformerWav2Vec2EncoderLayer (wav2vec2_model.py:440-578) parameters, reference state_dict names."""
+    D, F, H, K = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.encoder_attention_heads, cfg.depthwise_conv_kernel_size
+    for f in ("ffn1", "ffn2"):
+        s[f"{p}.{f}.layer_norm.weight"] = (D,)
+        s[f"{p}.{f}.layer_norm.bias"] = (D,)
+        s[f"{p}.{f}.w_1.weight"] = (F, D)
+        s[f"{p}.{f}.w_1.bias"] = (F,)
+        s[f"{p}.{f}.w_2.weight"] = (D, F)
+        s[f"{p}.{f}.w_2.bias"] = (D,)
+    s[f"{p}.self_attn_layer_norm.weight"] = (D,)
+    s[f"{p}.self_attn_layer_norm.bias"] = (D,)
+    for n in ("linear_q", "linear_k", "linear_v", "linear_out"):
+        s[f"{p}.self_attn.{n}.weight"] = (D, D)
+        s[f"{p}.self_attn.{n}.bias"] = (D,)
+    if cfg.pos_enc_type == "rel_pos":
+        s[f"{p}.self_attn.linear_pos.weight"] = (D, D)
+        s[f"{p}.self_attn.pos_bias_u"] = (H, D // H)
+        s[f"{p}.self_attn.pos_bias_v"] = (H, D // H)
+    s[f"{p}.conv_module.layer_norm.weight"] = (D,)
+    s[f"{p}.conv_module.layer_norm.bias"] = (D,)
+    s[f"{p}.conv_module.pointwise_conv1.weight"] = (2 * D, D, 1)
+    s[f"{p}.conv_module.depthwise_conv.weight"] = (D, 1, K)
+    for n in ("weight", "bias", "running_mean", "running_var"):
+        s[f"{p}.conv_module.batch_norm.{n}"] = (D,)
+    s[f"{p}.conv_module.pointwise_conv2.weight"] = (D, D, 1)
     s[f"{p}.final_layer_norm.weight"] = (D,)
     s[f"{p}.final_layer_norm.bias"] = (D,)
 
@@ -211,6 +245,16 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
         leaf = name.rsplit(".", 1)[-1]
         if name.endswith("relative_attention_bias.weight"):
             w = rng.standard_normal(shape) * 0.5
+        elif name.endswith("batch_norm.running_mean"):  # non-trivial eval statistics: the BatchNorm fold is exercised
+            w = 0.2 * rng.standard_normal(shape)
+        elif name.endswith("batch_norm.running_var"):
+            w = rng.uniform(0.5, 2.0, size=shape)
+        elif name.endswith(("pos_bias_u", "pos_bias_v")):
+            w = 0.3 * rng.standard_normal(shape)
+        elif name.endswith("depthwise_conv.weight"):  # (D, 1, K)
+            w = rng.standard_normal(shape) * np.sqrt(1.0 / shape[-1])
+        elif name.endswith(("pointwise_conv1.weight", "pointwise_conv2.weight")):  # (out, in, 1)
+            w = rng.standard_normal(shape) * np.sqrt(1.0 / shape[1])
         elif name.endswith("grep_a"):
             w = 1.0 + 0.3 * rng.standard_normal(shape)
         elif name.endswith("weight_g"):
@@ -301,6 +345,18 @@ def named_config(name: str) -> EncoderConfig:
         "tiny_multires_plain": dict(family="multires_hubert", label_rate_ratios=[1, 2], block_layers=[1, 1, 1],
                                     use_plain_updownsample=True, **{**tiny, "encoder_layers": 3}),
         "tiny_wav2vec2": dict(family="wav2vec2", **tiny),
+        # wav2vec 2.0 Conformer (ConformerEncoder): rel_pos / rope, post-LN tiny and the large released shape (pre-LN,
+        # layer-norm extractor; a released checkpoint's own config decides at load time)
+        "tiny_conformer_relpos": dict(family="wav2vec2", layer_type="conformer", pos_enc_type="rel_pos", attn_type="espnet",
+                                      **{**tiny, "extractor_mode": "layer_norm", "layer_norm_first": True, "normalize": True}),
+        "tiny_conformer_rope": dict(family="wav2vec2", layer_type="conformer", pos_enc_type="rope", attn_type="espnet",
+                                    **{**tiny, "extractor_mode": "layer_norm", "layer_norm_first": True, "normalize": True}),
+        "tiny_conformer_rope_postln": dict(family="wav2vec2", layer_type="conformer", pos_enc_type="rope", attn_type="espnet",
+                                           **tiny),
+        "wav2vec2_conformer_large_relpos": dict(family="wav2vec2", conv_bias=True, layer_type="conformer", pos_enc_type="rel_pos",
+                                                attn_type="espnet", **large),
+        "wav2vec2_conformer_large_rope": dict(family="wav2vec2", conv_bias=True, layer_type="conformer", pos_enc_type="rope",
+                                              attn_type="espnet", **large),
         "tiny_hubert_large": dict(family="hubert", **{**tiny, "extractor_mode": "layer_norm",
                                                       "layer_norm_first": True, "normalize": True,
                                                       "conv_bias": True}),

@@ -17,6 +17,11 @@ class UpstreamExpert(HipUpstreamExpert):
     def __init__(self, ckpt: str = None, model_config: str = None, feature_selection: str = None, **kwargs):
         assert feature_selection is None or feature_selection in ["fairseq_layers", "fairseq_layers_before_residual"]
         super().__init__(ckpt, model_config, **kwargs)
+        if feature_selection is not None and self.cfg.layer_type == "conformer":
+            # ConformerEncoder.extract_features records layer_results only when a target layer is set
+            # (wav2vec2_model.py:3199), so the reference returns an EMPTY list for either selection
+            raise ValueError(f"feature_selection={feature_selection!r} on a Conformer encoder: the reference returns an empty "
+                             "list there (ConformerEncoder records layer results only for a target layer); not built")
         self.feature_selection = feature_selection
 
     @property

@@ -3,8 +3,8 @@
 **kwargs)``, ``wav2vec2_local`` / ``wav2vec2_url``, and every released model (``wav2vec2``, ``wav2vec2_base_960``,
 ``wav2vec2_large_960``, ``wav2vec2_large_ll60k``, ``wav2vec2_large_lv60_cv_swbd_fsh``, ``xlsr_53``, ``xls_r_300m/1b/2b``,
 the VoxPopuli / S2ST transformer models).  ``http`` checkpoints resolve to the reference's cache file
-(``s3prl_amd.download``).  The conformer-typed names (``layer_type="conformer"``, wav2vec2_model.py:2100,2958) are
-registered and raise ``NotImplementedError``: the MI355X path builds the Transformer block only."""
+(``s3prl_amd.download``).  The conformer-typed names (``layer_type="conformer"``, wav2vec2_model.py:440-578,3132-3211) load
+from the download cache only: a cache miss raises ``NotImplementedError`` naming the entry and the file."""
 
 import os
 
@@ -60,9 +60,35 @@ _TRANSFORMER_MODELS = {
 for _name, (_file, _legacy_url) in _TRANSFORMER_MODELS.items():
     globals()[_name] = _released.with_legacy(_name, wav2vec2_custom, _CONVERTED + _file, _legacy_url)
 
-_CONFORMER = ("conformer encoder layers (layer_type='conformer': depthwise-conv module + relative / rotary attention, "
-              "wav2vec2_model.py:2100,2958) are outside the MI355X hot path, which builds the Transformer block")
-for _name in ("wav2vec2_conformer_relpos", "wav2vec2_conformer_rope", "wav2vec2_conformer_large_s2st_es_voxpopuli",
-              "wav2vec2_conformer_large_s2st_en_librilight"):
-    globals()[_name] = _released.unsupported(_name, _CONFORMER)
+# Conformer encoders (layer_type="conformer", rel_pos / rope): served from the download cache only — a cache miss raises
+# NotImplementedError (a RuntimeError, like every other cache miss) naming the entry and the file; nothing is fetched
+_CONFORMER_MODELS = {
+    "wav2vec2_conformer_relpos": ("LL_relpos_PT_no_FT.pt", _FAIRSEQ + "conformer/wav2vec2/librilight/LL_relpos_PT_no_FT"),
+    "wav2vec2_conformer_rope": ("LL_rope_PT_no_FT.pt", _FAIRSEQ + "conformer/wav2vec2/librilight/LL_rope_PT_no_FT"),
+    "wav2vec2_conformer_large_s2st_es_voxpopuli": ("wav2vec2_conformer_large_s2st_es_voxpopuli.pt",
+                                                   _FAIRSEQ + "speech_to_speech/s2st_finetuning/w2v2/es/conformer_L.pt"),
+    "wav2vec2_conformer_large_s2st_en_librilight": ("wav2vec2_conformer_large_s2st_en_librilight.pt",
+                                                    _FAIRSEQ + "speech_to_speech/s2st_finetuning/w2v2/en/conformer_L.pt"),
+}
+
+
+def _cached_only(name, url, legacy_url):
+    from ...download import cache_path
+
+    def entry(refresh=False, legacy=False, **kwargs):
+        u = legacy_url if legacy else url
+        path = cache_path(u)
+        if not path.is_file():
+            raise NotImplementedError(f"{name}: {os.path.basename(u)} is not in the download cache ({path}); this build does "
+                                      "not download the conformer checkpoints — place the file there or use wav2vec2_local")
+        return wav2vec2_custom(str(path), legacy=legacy, **kwargs)
+
+    entry.__name__ = entry.__qualname__ = name
+    entry.__doc__ = f"released conformer checkpoint {url} (from the download cache)"
+    entry.url, entry.legacy_url = url, legacy_url
+    return entry
+
+
+for _name, (_file, _legacy_url) in _CONFORMER_MODELS.items():
+    globals()[_name] = _cached_only(_name, _CONVERTED + _file, _legacy_url)
 del _name, _file, _legacy_url
