@@ -680,6 +680,16 @@ __global__ __launch_bounds__(128 * WN, WPE) void gemm16_big_kernel(GemmParams p)
                     const int row = t * RPS + lane / LPR;
                     float4 v = *(const float4*)(stg + row * SW + c4);
                     const int m = m0 + wr * WTM + i * 32 + row;
+                    // this pass's row statistics, fetched with the WHOLE wave active: ds_bpermute reads 0 from a lane whose EXEC bit is
+                    // off, and lane r (the holder of row r's pair) stores row t * RPS + r / LPR in pass t — past M in the last block
+                    // while row r is not (SW = 64: M % 32 in {17, 21, 25, 29}; SW = 32: {9, 17, 18, 25, 26, 27}).  Every lane's
+                    // rst_cur is valid: st_load clamps to row M - 1
+                    float mu = 0.f, rr = 0.f;
+                    if constexpr (RESLN) {
+                        const int src = row * 4;  // (byte address of the lane that holds this row's pair)
+                        mu = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(rst_cur.x)));
+                        rr = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(rst_cur.y)));
+                    }
                     if (FULL || (m < p.M && n_ok)) {
                         v.x += bias4[jb].x; v.y += bias4[jb].y; v.z += bias4[jb].z; v.w += bias4[jb].w;
                         if (act) {
@@ -691,9 +701,6 @@ __global__ __launch_bounds__(128 * WN, WPE) void gemm16_big_kernel(GemmParams p)
                             if constexpr (RESPF) rs = rsb[t];
                             else rs = *(const float4*)(p.residual + o);
                             if constexpr (RESLN) {  // the LayerNorm output of the stored row (norm.hip evaluates the same ln_affine)
-                                const int src = (t * RPS + lane / LPR) * 4;  // (byte address of the lane that holds this row's pair)
-                                const float mu = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(rst_cur.x)));
-                                const float rr = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(rst_cur.y)));
                                 rs.x = ln_affine(rs.x, mu, rr, lg.x, lb.x);
                                 rs.y = ln_affine(rs.y, mu, rr, lg.y, lb.y);
                                 rs.z = ln_affine(rs.z, mu, rr, lg.z, lb.z);

@@ -290,20 +290,31 @@ def test_one_utterance_alone_equals_its_rows_in_a_batch_bit_for_bit(dtype):
     full batch): one 2 s utterance alone is M = 99 rows — below every large tile's row count — and the same utterance among five
     is M = 495; the GEMM dispatch (tile heights, the two-term fp16x2 kernel that stages both weight terms, the 128x128 fallback)
     must give it the same bits both ways, in every operand mode."""
+    _alone_equals_batch(dtype, (32000, 32000, 20000, 32000, 9000))
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "fp32x3", "fp16x2", "bf16"])
+def test_one_second_utterance_alone_equals_its_rows_in_a_batch_bit_for_bit(dtype):
+    """The same at T = 49 (16 000 samples): alone, M = 49 = 32 + 17 — a last 32-row block of 17 rows, where the post-LN layers' fc2
+    rebuilds LayerNorm 1 from row statistics read across lanes (ln1_fold) — and among five, M = 245."""
+    _alone_equals_batch(dtype, (16000, 16000, 12000, 16000, 9000))
+
+
+def _alone_equals_batch(dtype, lengths):
     import torch
     from s3prl_amd.synth import named_config, synth_weights
 
     cfg = named_config("hubert_base")
     enc = _encoder(cfg, synth_weights(cfg, 0), dtype=dtype)
     gen = torch.Generator(device="cuda").manual_seed(11)
-    wavs = [torch.randn(n, device="cuda", generator=gen) for n in (32000, 32000, 20000, 32000, 9000)]
+    wavs = [torch.randn(n, device="cuda", generator=gen) for n in lengths]
     full = enc.forward(wavs).clone()
     torch.cuda.synchronize()
     assert torch.isfinite(full.float()).all()
     for i in (0, 2, 4):
-        alone = enc.forward([wavs[i]], n_max=32000)
+        alone = enc.forward([wavs[i]], n_max=max(lengths))
         torch.cuda.synchronize()
-        assert torch.equal(alone[:, 0], full[:, i]), f"utterance {i} differs between B = 1 and B = 5 ({dtype})"
+        assert torch.equal(alone[:, 0], full[:, i]), f"utterance {i} differs between B = 1 and B = 5 ({dtype}, n_max = {max(lengths)})"
     enc.close()
 
 

@@ -707,6 +707,10 @@ def test_wavlm_gate_kernel():
     (1, 257, 256, 64, 64, None, 0, True, True),          # one row into the second 256-row tile
     (1, 193, 132, 16, 16, None, 1, True, True),          # a single K step, ragged N (clamped W rows), one row past 192
     (2, 99, 2304, 768, 768, None, 0, False, False),      # a short utterance: the 64-row tile's home shape
+    (1, 1000, 768, 3072, 3072, None, 3, True, False),    # act 3 = swish (the Conformer FFN) ...
+    (2, 499, 768, 512, 512, None, 3, False, True),
+    (1, 193, 132, 16, 16, None, 3, True, True),
+    (1, 257, 256, 64, 64, None, 3, False, False),
 ])
 def test_gemm32_big_tile_is_bit_identical_to_the_default_kernel(shape):
     """The fp32 path's default GEMM (gemmt.hip: 256 / 192 / 128 / 64 x 128 tiles, tuning key gemm32_big = 2..5, 1 = chosen

@@ -11,12 +11,14 @@ import pytest
 torch = pytest.importorskip("torch")
 transformers = pytest.importorskip("transformers")
 
+# (the modeling modules, and accelerate behind them, load here at collection: on a busy host that import alone has outlasted a
+#  test's deadline when it ran inside the first test)
+from transformers import HubertConfig, HubertModel, WavLMConfig, WavLMModel  # noqa: E402
+
 from oracle import encoder_oracle as O  # noqa: E402
 
 
 def _hf_model(cfg, weights):
-    from transformers import HubertConfig, HubertModel
-
     hc = HubertConfig(
         hidden_size=cfg.encoder_embed_dim, num_hidden_layers=cfg.encoder_layers,
         num_attention_heads=cfg.encoder_attention_heads, intermediate_size=cfg.encoder_ffn_embed_dim,
@@ -87,8 +89,6 @@ def test_oracle_matches_huggingface_hubert(name):
 # A.10: relative_attention_bias -> rel_attn_embed, grep_linear -> gru_rel_pos_linear, grep_a -> gru_rel_pos_const.
 
 def _hf_wavlm(cfg, weights):
-    from transformers import WavLMConfig, WavLMModel
-
     hc = WavLMConfig(
         hidden_size=cfg.encoder_embed_dim, num_hidden_layers=cfg.encoder_layers,
         num_attention_heads=cfg.encoder_attention_heads, intermediate_size=cfg.encoder_ffn_embed_dim,

@@ -144,7 +144,8 @@ def _worker_16(rank, world, port, ret):
     for dt in (torch.bfloat16, torch.float16):
         hs = (torch.arange(3 * 2 * 4 * 8, dtype=torch.float32).reshape(3, 2, 4, 8) * (rank + 1) / 64).to(dt)
         g = gather_layers(hs)
-        out[str(dt)] = (g.dtype == dt, tuple(g.shape), g.float())
+        out[str(dt)] = (g.dtype == dt, tuple(g.shape), g.float().numpy())  # (numpy: pickled by value — a tensor would be fetched from
+        # this process's shared-memory fd server on unpickling, which is gone once the worker has exited)
     ret.put((rank, out))
     dist.barrier()
     dist.destroy_process_group()
@@ -169,4 +170,5 @@ def test_gloo_gather_of_16bit_states_moves_bytes():
         for dt in (torch.bfloat16, torch.float16):
             ok, shape, g = results[r][str(dt)]
             assert ok and shape == (3, 4, 4, 8)
+            g = torch.from_numpy(g)
             assert torch.equal(g[:, :2], base.to(dt).float()) and torch.equal(g[:, 2:], (base * 2).to(dt).float())
