@@ -344,6 +344,9 @@ int s3enc_debug_clock_sample(uint64_t* out3_device, void* stream);
  *                   prototype that lost (profiles/r06_attention_persist.md), kept for re-measurement;
  *   "reserve_cus":  CUs the persistent one-workgroup-per-CU GEMM of the 16-bit modes leaves out of its grid (default 0; a measurement
  *                   knob — leaving CUs to a collective's channel kernels costs more than sharing them: profiles/r05_cu_contention.md);
+ *   "conv_f22":     S3ENC_F32: 1 (default) = conv layers 1.. with kernel 3 and stride 2 (conv1-4 of every extractor) run in the
+ *                   two-output form (convf22.hip: 5 block products per pair of outputs instead of 6, fp32 operands and accumulation,
+ *                   a different association — results differ in the last bits), 0 = the implicit GEMM;
  *   "conv0_nt":     1 (default) = the fp32 conv0 kernel writes its activation with non-temporal stores, 0 = plain stores;
  *   "ws_inplace":   1 (default) = post-LN layers run LayerNorm 1 and fc2 in place on one fp32 workspace buffer, 0 = two buffers;
  *   "ln1_fold":     16-bit modes, post-LN layers: 1 (default) = LayerNorm 1 writes its 16-bit output and the rows' (mean, rstd) only and

@@ -246,6 +246,12 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
                 UPW(e->conv[i].w, t2, C, (long)k * cin, 1);
             }
             if (e->x3 || (e->x2_conv_f32_from && i >= e->x2_conv_f32_from)) UP(upload_x3(e->conv[i].w3, t2, C, (long)k * cin));
+            if (e->dtype == F32 && !e->x3 && k == 3 && c.conv_stride[i] == 2) {  // convf22.hip's WP = fl(W0 + W2)
+                std::vector<float> wp((size_t)C * cin);
+                for (int co = 0; co < C; ++co)
+                    for (int ci = 0; ci < cin; ++ci) wp[(size_t)co * cin + ci] = t2[(long)co * 3 * cin + ci] + t2[(long)co * 3 * cin + 2 * cin + ci];
+                UP(upload_f32(e->conv[i].wp, wp));
+            }
         }
         if (c.conv_bias) {
             GET(p + ".0.bias", C, t);
@@ -1206,11 +1212,30 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         const double by = ((double)B * L[i - 1] * C + (double)C * g.K) * (x3in ? 4 : es) + (double)B * L[i] * C * (f32out ? 4 : es);
         char kind[32];
         snprintf(kind, sizeof(kind), "gemm:conv%d", i);
+        // S3ENC_F32, k = 3, stride 2: the two-output form (convf22.hip); eligibility depends on C and the buffers, never on B or L
+        ConvF22Params f22{};
+        bool use_f22 = false;
+        if (dt == F32 && !e->x3 && !x3in && c.conv_kernel[i] == 3 && c.conv_stride[i] == 2 && e->conv[i].wp.p) {
+            f22.x = (const float*)cur;
+            f22.x_bs = L[i - 1] * C;
+            f22.W = (const float*)e->conv[i].w.p;
+            f22.WP = (const float*)e->conv[i].wp.p;
+            f22.bias = g.bias;
+            f22.M = (int)L[i];
+            f22.C = C;
+            f22.batches = B;
+            f22.act = lnmode ? 0 : 1;
+            f22.out = (float*)(lnmode ? tmp32 : dst);
+            f22.o_bs = L[i] * C;
+            use_f22 = conv_f22_eligible(f22);
+        }
         if (!lnmode) {
             g.act = 1;
             if (f32out) g.out32 = (float*)dst; else g.out16 = dst;
             Prof pr(e, st, kind, fl, by);
-            if (x3in) {
+            if (use_f22) {
+                HIP_TRY(launch_conv_f22(f22, st));
+            } else if (x3in) {
                 if (!gemm_x3_eligible(g)) return fail("conv layer is not a shape of the three-term GEMM (internal)");
                 HIP_TRY(launch_gemm(F32, g, st));
             } else {
@@ -1221,7 +1246,9 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
             g.out32 = (float*)tmp32;
             {
                 Prof pr(e, st, kind, fl, by);
-                if (x3in) {  // fp32 LayerNorm output of the previous conv -> three-term GEMM (S3ENC_F16X2, see x2_conv_f32_from)
+                if (use_f22) {
+                    HIP_TRY(launch_conv_f22(f22, st));
+                } else if (x3in) {  // fp32 LayerNorm output of the previous conv -> three-term GEMM (S3ENC_F16X2, see x2_conv_f32_from)
                     if (!gemm_x3_eligible(g)) return fail("conv layer is not a shape of the three-term GEMM (internal)");
                     HIP_TRY(launch_gemm(F32, g, st));
                 } else {

@@ -338,6 +338,7 @@ struct ConformerLayerW {
 struct ConvW {
     DevBuf w, bias, lng, lnb;  // w: conv0 fp32 [C][k]; conv>=1 compute dtype [C][k*Cin]
     DevBuf w3;                 // S3ENC_F32X3: pair-packed image of w (conv >= 1)
+    DevBuf wp;                 // S3ENC_F32, k = 3: fp32 (C, C) image of tap 0 + tap 2 (convf22.hip)
     bool has_bias = false;
 };
 

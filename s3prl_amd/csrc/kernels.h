@@ -53,6 +53,8 @@ struct Tuning {
                            // 110 vs 107 / 130 vs 121 WavLM-large (profiles/r06b_attn_lab_variants.md)
     int conv0_nt = 1;      // frontend.hip, fp32 output: 1 = non-temporal row stores (the 2 GB activation streams past the caches:
                            // 0.578 -> 0.436 ms on HuBERT-base 32 x 10 s, round 4), 0 = plain stores
+    int conv_f22 = 1;      // convf22.hip, S3ENC_F32: 1 = conv layers with k = 3, stride 2 in the two-output form (a sixth fewer MFMAs;
+                           // different association, same fp32 operands), 0 = the implicit GEMM of gemmt.hip
     int conv0_fast = 1;    // frontend.hip, 16-bit outputs (S3ENC_BF16 / F16 / F16X2) and the split-precision modes' fp32 output: 1 = packed fp32 taps + the packed one-transcendental GELU,
                            // 0 = scalar taps + libm erff (the FAST = false instantiation: ~2x the kernel's time, results a few 16-bit ulps
                            // apart).  Round 6, fourth session: the rows that differ when >= 4 handles' forwards overlap ORIGINATE in
@@ -161,6 +163,22 @@ hipError_t launch_gemm16_big(int dtype, const GemmParams& p, hipStream_t stream)
 bool gemm_tile_eligible(int dtype, const GemmParams& p);
 hipError_t launch_gemm_tile(int dtype, const GemmParams& p, hipStream_t stream);
 hipError_t launch_gemm(int dtype, const GemmParams& p, hipStream_t stream);
+// convf22.hip: exact-fp32 Conv1d(C, C, k = 3, stride = 2) on channel-last rows in the two-output form (5 block products per
+// pair of outputs instead of 6).  out[b][t] = act(W0 x[2t] + W1 x[2t+1] + W2 x[2t+2] + bias), W = (C, 3C) tap-major, WP = W0 + W2
+struct ConvF22Params {
+    const float* x;     // (batches, L_in, C) rows, utterance b at x + b * x_bs
+    long x_bs;          // elements per utterance (L_in * C)
+    const float* W;     // (C, 3C) [n][j*C + c]
+    const float* WP;    // (C, C) fl(W0 + W2)
+    const float* bias;  // [C] or null
+    int M, C, batches;  // M = output frames per utterance
+    int act;            // 0 none, 1 erf-GELU (the launcher maps it like launch_gemm)
+    const int* row_limit;
+    float* out;         // (batches, M, C), utterance b at out + b * o_bs
+    long o_bs;
+};
+bool conv_f22_eligible(const ConvF22Params& p);  // tuning().conv_f22, C a multiple of 32, alignment, 32-bit offsets
+hipError_t launch_conv_f22(const ConvF22Params& p, hipStream_t stream);
 
 // ---- frontend.hip ---------------------------------------------------------------------------------------
 // Waveform table: wav b is `ptrs[b]` with `lens[b]` valid samples; reads beyond are zeros (the padding).
