@@ -40,7 +40,12 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * (encoders[i] -> conv adapter -> ... middle_encoder ... -> conv adapter -> decoders[i] + skip) over the frame rates
         * of mr_ratios; HuBERT's frame mask; the states are every block's layer inputs and output, repeated to the
         * finest rate and cut to their common length (multires_hubert/expert.py:26-27,49-101) */
-       S3ENC_MULTIRES = 4 };
+       S3ENC_MULTIRES = 4,
+       /* wav2vec / vq-wav2vec (upstream/wav2vec/wav2vec_model.py:59-286,565-700, expert.py:15-62): a convolutional feature
+        * extractor, an optional vector quantizer and a causal convolutional aggregator — no Transformer, no frame mask.  The
+        * states are z (the extractor output) and every aggregator layer's output: n_agg + 1 states of (B, T, conv_dim).
+        * compute_dtype S3ENC_F32 only. */
+       S3ENC_WAV2VEC = 5 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -123,6 +128,39 @@ typedef struct s3enc_config {
     int32_t dw_kernel;                              /* conformer: depthwise_conv_kernel_size (odd, <= 63; 31) */
 } s3enc_config;
 
+/* S3ENC_WAV2VEC only (Wav2VecConfig, upstream/wav2vec/wav2vec_model.py:289-410): the second configuration block of
+ * s3enc_create_ex.  s3enc_config and S3ENC_VERSION stay what ABI 8 binders were built against: the extractor is its n_conv / conv_dim /
+ * conv_kernel / conv_stride (conv0: kernel 10); encoder_layers = n_agg and embed_dim = conv_dim; its Transformer fields
+ * are ignored.  Every block is Conv1d -> Fp32GroupNorm(1, C) over all C x L values of the utterance, the zero-padded time
+ * included -> ReLU (:235-286, :59-114).  Checkpoint tensors, reference state_dict names: feature_extractor.conv_layers.N.0.weight,
+ * .N.2.{weight,bias}; feature_aggregator.conv_layers.N.1.{weight,bias}, .N.3.{weight,bias}; gumbel: vector_quantizer.vars (1, Gt * V, Dv),
+ * vector_quantizer.weight_proj.{weight,bias} (vq_depth 1) or .weight_proj.I.0.{weight,bias} and .weight_proj.<depth-1>.{weight,bias};
+ * k-means: vector_quantizer.embedding (V, Gt, Dv), .projection.0.weight (C, C / G, 1), .projection.1.{weight,bias}; Gt = 1 with
+ * combine_groups, else G; wav2vec_predictions.* and project_features.* are not read.  s3enc_create_ex refuses by name what is not
+ * built: every compute dtype but fp32, the GRU aggregator, activation gelu, skip_connections_feat, layers of unequal width
+ * (residual_proj), aggregator strides other than 1, vq_dim != conv_dim. */
+typedef struct s3enc_wav2vec_config {
+    int32_t n_agg;                                  /* aggregator layers (12) */
+    int32_t agg_dim[S3ENC_MAX_CONV];                /* their widths: all equal to conv_dim */
+    int32_t agg_kernel[S3ENC_MAX_CONV];             /* (2..13); each layer pads kernel - 1 frames on the left */
+    int32_t agg_stride[S3ENC_MAX_CONV];             /* all 1 */
+    int32_t w2v_aggregator;                         /* 0 "cnn", 1 "gru" (refused) */
+    int32_t w2v_activation;                         /* 0 "relu", 1 "gelu" (refused) */
+    int32_t w2v_skip_feat;                          /* skip_connections_feat (refused) */
+    int32_t log_compression;                        /* log(|x| + 1) behind the extractor */
+    int32_t skip_connections_agg;                   /* x = (block(x) + x) * sqrt(residual_scale) */
+    float residual_scale;
+    int32_t non_affine_group_norm;
+    int32_t no_conv_bias;                           /* the aggregator's convolutions have no bias */
+    int32_t agg_zero_pad;                           /* ZeroPad1d instead of ReplicationPad1d */
+    int32_t vq_type;                                /* 0 none, 1 gumbel (wav2vec2_model.py:1591-1782, eval: argmax), 2 kmeans (:117-232) */
+    int32_t vq_vars;                                /* V: variables per group (320) */
+    int32_t vq_groups;                              /* G (2) */
+    int32_t vq_dim;                                 /* width of the codewords: conv_dim */
+    int32_t vq_depth;                               /* gumbel: Linear layers of weight_proj (inner width 2 C, ReLU between) */
+    int32_t combine_groups;                         /* the groups share one set of variables */
+} s3enc_wav2vec_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -141,6 +179,11 @@ const char* s3enc_last_error(void);
  * Replaces UpstreamExpert.__init__ (hubert/expert.py:27-51, wav2vec2/expert.py:21-56, wavlm/expert.py:34-54). */
 int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device,
                  s3enc_handle* out);
+/* s3enc_create with the family's second configuration block: `w2v` is required for S3ENC_WAV2VEC (s3enc_create refuses that family:
+ * it has no place for the aggregator / quantizer parameters) and must be NULL for every other family.
+ * Replaces UpstreamExpert.__init__ of upstream/wav2vec/expert.py:16-34 (load_converted_model, wav2vec/convert.py:24-37). */
+int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
+                    int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -190,6 +233,14 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n);
  * out + i*layer_stride ELEMENTS of out_dtype (featurize: one fp32 (B, T, D) block, layer_stride ignored). */
 int s3enc_forward_ex(s3enc_handle h, const float* const* wavs, const int64_t* lengths, int32_t B, int64_t n_max,
                      const s3enc_forward_opts* opts, void* out, int64_t layer_stride, void* stream);
+
+/* s3enc_forward_ex plus the quantizer's outputs of an S3ENC_WAV2VEC handle with vq_type != 0 (wav2vec family).  Replaces result["codewords"]
+ * and result["codeids"] of wav2vec/expert.py:49-53 (vector_quantizer(features, produce_targets=True)): codewords: device fp32
+ * (B, T, vq_dim), 16-byte aligned; codeids: device int64 (B, T, vq_groups), per (frame, group) the index of the chosen variable
+ * (ties: the lowest index); either may be NULL.  Other handles: both must be NULL. */
+int s3enc_forward_aux(s3enc_handle h, const float* const* wavs, const int64_t* lengths, int32_t B, int64_t n_max,
+                      const s3enc_forward_opts* opts, void* out, int64_t layer_stride, float* codewords, int64_t* codeids,
+                      void* stream);
 
 /* Numerical health of the forwards of this handle (ABI 6).  Replaces: nothing the reference has as a call — its
  * experts return whatever ATen computed and the regression test inspects the tensors (test/test_upstream.py:118-136);
@@ -421,6 +472,22 @@ int s3enc_op_conformer_conv(const float* x, const float* taps, const float* shif
  * B = 32, H = 16, T = 499.) */
 int s3enc_op_relpos_attention(const float* qkv, float* out, const int32_t* valid, int32_t B, int32_t T, int32_t H, const float* P,
                               const float* qadd, void* stream);
+
+/* wav2vec: the row pass behind a convolution (wav2vec_model.py:25-56,83-113,248-286): Fp32GroupNorm(1, C) over the `rows` x C values
+ * of each utterance (biased variance, eps 1e-5; statistics in double) -> ReLU -> [(y + res) * scale] -> [log(|y| + 1)].
+ * x: device fp32 (B, rows, C); gamma / beta: device (C) or NULL (non_affine_group_norm); res: device (B, rows, C) or NULL.
+ * dst: device (B, pad + rows, C) or NULL: the next convolution's operand, its `pad` leading rows of every utterance filled with
+ * frame 0 (ReplicationPad1d) or zeros (pad_zero); state: device (B, rows, C) or NULL; acc: device (B, rows, C) or NULL — the
+ * Featurizer term acc (+)= acc_w * (acc_norm ? layer_norm(y) : y), written instead of added when acc_init.  Synchronises. */
+int s3enc_op_gn1_apply(const float* x, const float* gamma, const float* beta, const float* res, float scale, int32_t log_compress,
+                       int32_t B, int32_t rows, int32_t C, int32_t pad, int32_t pad_zero, float* dst, float* state, float* acc,
+                       float acc_w, int32_t acc_norm, int32_t acc_init, void* stream);
+/* Hard selection of a quantizer (GumbelVectorQuantizer in eval, wav2vec2_model.py:1733-1775; KmeansVectorQuantizer's argmin on
+ * negated distances, wav2vec_model.py:193-204): per (row, group) the index of the largest of V scores (ties: the lowest index),
+ * and the gathered variables.  scores: device fp32 (rows, G, V); table: device fp32 (shared ? 1 : G, V, Dv); ids: device int64
+ * (rows, G) or NULL; out: device fp32 (rows, G * Dv) or NULL. */
+int s3enc_op_argmax_gather(const float* scores, const float* table, int32_t shared, int64_t rows, int32_t G, int32_t V, int32_t Dv,
+                           int64_t* ids, float* out, void* stream);
 
 /* Convolutional position embedding + residual: out = x + GELU(SamePad(Conv1d(D, D, K, padding=K/2, groups=G)(x)) + bias)
  * (make_conv_pos / SamePad, wav2vec2_model.py:2937-2953,1797-1808).  x, out: device fp32 (B, T, D); w_host: HOST fp32

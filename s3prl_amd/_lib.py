@@ -19,7 +19,8 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5}
+VQ_TYPE = {"none": 0, "gumbel": 1, "kmeans": 2}  # s3enc_config.vq_type
 SEL_HIDDEN, SEL_LAYER_OUT, SEL_FFN_OUT = 0, 1, 2
 SELECTIONS = {None: SEL_HIDDEN, "hidden_states": SEL_HIDDEN, "fairseq_layers": SEL_LAYER_OUT,
               "fairseq_layers_before_residual": SEL_FFN_OUT}
@@ -41,6 +42,18 @@ class S3Config(C.Structure):
         ("mr_pairs", C.c_int32), ("mr_ratios", C.c_int32 * (2 * (S3ENC_MAX_RES - 1))),
         ("mr_layers", C.c_int32 * (2 * S3ENC_MAX_RES - 1)), ("mr_kernel", C.c_int32), ("mr_plain", C.c_int32),
         ("layer_type", C.c_int32), ("pos_enc_type", C.c_int32), ("dw_kernel", C.c_int32),
+    ]
+
+
+class S3Wav2vecConfig(C.Structure):
+    """s3enc_wav2vec_config: the aggregator / quantizer block of a wav2vec handle (s3enc_create_ex)."""
+    _fields_ = [
+        ("n_agg", C.c_int32), ("agg_dim", C.c_int32 * S3ENC_MAX_CONV), ("agg_kernel", C.c_int32 * S3ENC_MAX_CONV),
+        ("agg_stride", C.c_int32 * S3ENC_MAX_CONV), ("w2v_aggregator", C.c_int32), ("w2v_activation", C.c_int32),
+        ("w2v_skip_feat", C.c_int32), ("log_compression", C.c_int32), ("skip_connections_agg", C.c_int32),
+        ("residual_scale", C.c_float), ("non_affine_group_norm", C.c_int32), ("no_conv_bias", C.c_int32),
+        ("agg_zero_pad", C.c_int32), ("vq_type", C.c_int32), ("vq_vars", C.c_int32), ("vq_groups", C.c_int32),
+        ("vq_dim", C.c_int32), ("vq_depth", C.c_int32), ("combine_groups", C.c_int32),
     ]
 
 
@@ -70,6 +83,7 @@ _PROTOS = {
     "s3enc_version": (C.c_int, []),
     "s3enc_last_error": (C.c_char_p, []),
     "s3enc_create": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    "s3enc_create_ex": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Wav2vecConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -78,6 +92,7 @@ _PROTOS = {
     "s3enc_forward": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_I64), _I32, _I64, _VP, _I64, _VP]),
     "s3enc_forward_status": (C.c_int, [_VP, _I32, C.POINTER(_I32)]),
     "s3enc_forward_ex": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_I64), _I32, _I64, C.POINTER(S3ForwardOpts), _VP, _I64, _VP]),
+    "s3enc_forward_aux": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_I64), _I32, _I64, C.POINTER(S3ForwardOpts), _VP, _I64, _VP, _VP, _VP]),
     "s3enc_num_states": (C.c_int, [_VP, _I32, C.POINTER(_I32)]),
     "s3enc_forward_padded": (C.c_int, [_VP, _VP, _I64, C.POINTER(_I64), _I32, _I64, _VP, _I64, _VP]),
     "s3enc_set_layer_events": (C.c_int, [_VP, C.POINTER(_VP), _I32]),
@@ -109,6 +124,9 @@ _PROTOS = {
                                  _I32, _VP, _VP]),
     "s3enc_op_wavlm_gate": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP]),
     "s3enc_op_conformer_conv": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP]),
+    "s3enc_op_gn1_apply": (C.c_int, [_VP, _VP, _VP, _VP, C.c_float, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, C.c_float,
+                                     _I32, _I32, _VP]),
+    "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "s3enc_weighted_sum": (C.c_int, [_VP, _I64, _I32, C.POINTER(C.c_float), _I32, _I64, _I32, _VP, _VP]),
@@ -204,4 +222,30 @@ def make_config(cfg, dtype: str) -> S3Config:
             c.mr_layers[i] = int(n)
         c.mr_kernel = int(cfg.conv_adapter_kernel)
         c.mr_plain = int(cfg.use_plain_updownsample)
+    return c
+
+
+def make_wav2vec_config(cfg) -> S3Wav2vecConfig:
+    """The second configuration block of a ``family="wav2vec"`` EncoderConfig (``s3enc_create_ex``)."""
+    if cfg.family != "wav2vec":
+        raise S3EncError("make_wav2vec_config needs a wav2vec configuration")
+    c = S3Wav2vecConfig()
+    if len(cfg.agg_layers) > S3ENC_MAX_CONV:
+        raise S3EncError("too many aggregator layers")
+    c.n_agg = len(cfg.agg_layers)
+    for i, (d, k, s) in enumerate(cfg.agg_layers):
+        c.agg_dim[i], c.agg_kernel[i], c.agg_stride[i] = d, k, s
+    c.w2v_aggregator = int(cfg.aggregator != "cnn")
+    c.w2v_activation = int(cfg.activation != "relu")
+    c.w2v_skip_feat = int(cfg.skip_connections_feat)
+    c.log_compression = int(cfg.log_compression)
+    c.skip_connections_agg = int(cfg.skip_connections_agg)
+    c.residual_scale = float(cfg.residual_scale)
+    c.non_affine_group_norm = int(cfg.non_affine_group_norm)
+    c.no_conv_bias = int(cfg.no_conv_bias)
+    c.agg_zero_pad = int(cfg.agg_zero_pad)
+    c.vq_type = VQ_TYPE[cfg.vq_type]
+    c.vq_vars, c.vq_groups, c.vq_depth = int(cfg.vq_vars), int(cfg.vq_groups), int(cfg.vq_depth)
+    c.vq_dim = int(cfg.vq_dim) or cfg.conv_dim
+    c.combine_groups = int(cfg.combine_groups)
     return c

@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, config_from_dicts, config_from_distiller, config_from_multires
+from .config import EncoderConfig, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -28,6 +28,7 @@ _REQUIRED = {
     "wavlm": ["cfg", "model"],
     "distiller": ["Config", "Distiller"],
     "multires_hubert": ["task_cfg", "model_cfg", "model_weight", "dictionaries_symbols"],
+    "wav2vec": ["task_cfg", "model_cfg", "model_weight"],  # wav2vec/convert.py:24-37
 }
 
 
@@ -46,6 +47,15 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
     import torch
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
+        # the original fairseq layout ({"cfg": {"task", "model"}, "model"}; before fairseq 0.10.2 {"args": Namespace, "model"}),
+        # what wav2vec/convert.py:11-17 turns into the converted format
+        cfg_ = state.get("cfg")
+        if cfg_ is None:
+            state = {"task_cfg": {}, "model_cfg": _plain(state["args"]), "model_weight": state["model"]}
+        else:
+            cfg_ = _plain(cfg_)
+            state = {"task_cfg": _plain(cfg_.get("task") or {}), "model_cfg": _plain(cfg_["model"]), "model_weight": state["model"]}
     for key in _REQUIRED[family]:
         if key not in state:
             # same message shape as hubert/convert.py:46-49
@@ -58,6 +68,9 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         sd = state["Distiller"]
     elif family == "multires_hubert":
         cfg = config_from_multires(_plain(state["model_cfg"]), _plain(state["task_cfg"]))
+        sd = state["model_weight"]
+    elif family == "wav2vec":  # (wav2vec_predictions.* / project_features.* are training-only: param_shapes does not name them)
+        cfg = config_from_wav2vec(_plain(state["model_cfg"]), _plain(state["task_cfg"]))
         sd = state["model_weight"]
     else:
         cfg = config_from_dicts(family, _plain(state["model_cfg"]), _plain(state["task_cfg"]))
@@ -79,6 +92,16 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
     import torch
 
     sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.items()}
+    if cfg.family == "wav2vec":
+        w2v = dict(conv_feature_layers=str([tuple(t) for t in cfg.conv_layers]),
+                   conv_aggregator_layers=str([tuple(t) for t in cfg.agg_layers]), aggregator=cfg.aggregator,
+                   activation=cfg.activation, log_compression=cfg.log_compression, skip_connections_feat=cfg.skip_connections_feat,
+                   skip_connections_agg=cfg.skip_connections_agg, residual_scale=cfg.residual_scale,
+                   non_affine_group_norm=cfg.non_affine_group_norm, no_conv_bias=cfg.no_conv_bias, agg_zero_pad=cfg.agg_zero_pad,
+                   vq_type=cfg.vq_type, vq_vars=cfg.vq_vars, vq_groups=cfg.vq_groups, vq_dim=cfg.vq_dim, vq_depth=cfg.vq_depth,
+                   combine_groups=cfg.combine_groups, infonce=False)
+        torch.save({"task_cfg": {"normalize": False}, "model_cfg": w2v, "model_weight": sd}, path)
+        return
     model_cfg = dict(
         extractor_mode=cfg.extractor_mode, conv_bias=cfg.conv_bias, encoder_layers=cfg.encoder_layers,
         encoder_embed_dim=cfg.encoder_embed_dim, encoder_ffn_embed_dim=cfg.encoder_ffn_embed_dim,

@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -101,6 +101,26 @@ class EncoderConfig:
     pos_enc_type: str = "abs"
     attn_type: str = ""
     depthwise_conv_kernel_size: int = 31
+    # wav2vec / vq-wav2vec (family "wav2vec", Wav2VecConfig, upstream/wav2vec/wav2vec_model.py:289-410): ``conv_layers`` is the
+    # extractor, ``agg_layers`` the causal convolutional aggregator; every block is Conv1d -> GroupNorm(1, C) -> ReLU.  There is no
+    # Transformer: ``encoder_layers`` = len(agg_layers) and ``encoder_embed_dim`` = the conv width, so the states are
+    # (encoder_layers + 1) x (B, T, C): z and every aggregator layer's output
+    agg_layers: List[Tuple[int, int, int]] = field(default_factory=list)
+    aggregator: str = "cnn"
+    activation: str = "relu"
+    log_compression: bool = True
+    skip_connections_feat: bool = False
+    skip_connections_agg: bool = True
+    residual_scale: float = 0.5
+    non_affine_group_norm: bool = False
+    no_conv_bias: bool = False
+    agg_zero_pad: bool = False
+    vq_type: str = "none"  # "none" | "gumbel" | "kmeans"
+    vq_vars: int = 320
+    vq_groups: int = 2
+    vq_dim: int = 0        # 0 = the extractor width
+    vq_depth: int = 1
+    combine_groups: bool = False
 
     # ---- derived -------------------------------------------------------------------------
     @property
@@ -152,7 +172,7 @@ class EncoderConfig:
         T = self.num_frames(n_max)
         if T <= 0:
             return 0
-        if self.family in ("wav2vec2", "distiller"):  # distiller: cal_pad_mask, distiller/model.py:271-285
+        if self.family in ("wav2vec2", "distiller", "wav2vec"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec: no mask
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -249,6 +269,8 @@ class EncoderConfig:
                     if s < 1 or s > 4 or (k - 1) % s:
                         raise ValueError("multires_hubert: every rate must divide conv_adapter_kernel - 1 (the transposed "
                                          "conv is run as `rate` interleaved stride-1 convs)")
+        if self.family == "wav2vec":
+            return self._validate_wav2vec()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -274,6 +296,30 @@ class EncoderConfig:
             raise ValueError("the HIP attention kernel is specialised for head_dim == 64")
         if self.encoder_embed_dim % self.conv_pos_groups:
             raise ValueError("embed_dim must be divisible by conv_pos_groups")
+
+    def _validate_wav2vec(self) -> None:
+        """What the HIP path builds of ``Wav2VecConfig``; everything else is refused by name (s3enc_create repeats it)."""
+        if self.aggregator != "cnn":
+            raise ValueError(f"wav2vec aggregator={self.aggregator!r} is not built: only the convolutional aggregator 'cnn'")
+        if self.activation != "relu":
+            raise ValueError(f"wav2vec activation={self.activation!r} is not built: only 'relu' (the released models)")
+        if self.skip_connections_feat:
+            raise ValueError("wav2vec skip_connections_feat is not built (off in the released models)")
+        if not self.agg_layers:
+            raise ValueError("wav2vec needs conv_aggregator_layers")
+        if len({d for d, _, _ in self.conv_layers} | {d for d, _, _ in self.agg_layers}) != 1:
+            raise ValueError("wav2vec layers of unequal widths are not built (the aggregator would need residual_proj)")
+        if any(s != 1 for _, _, s in self.agg_layers):
+            raise ValueError("wav2vec aggregator strides other than 1 are not built")
+        if self.encoder_layers != len(self.agg_layers) or self.encoder_embed_dim != self.conv_dim:
+            raise ValueError("wav2vec: encoder_layers / encoder_embed_dim must mirror the aggregator (config_from_wav2vec sets them)")
+        if self.vq_type not in ("none", "gumbel", "kmeans"):
+            raise ValueError(f"unknown vq_type {self.vq_type!r}")
+        if self.vq_type != "none":
+            if self.vq_dim not in (0, self.conv_dim):
+                raise ValueError("wav2vec vq_dim must be 0 or the extractor width (the aggregator reads the codewords)")
+            if self.conv_dim % self.vq_groups or (self.conv_dim // self.vq_groups) % 4:
+                raise ValueError("wav2vec vq_groups must divide the width into multiples of 4")
 
     def to_dict(self) -> Dict:
         return asdict(self)
@@ -318,6 +364,40 @@ def config_from_dicts(family: str, model_cfg: Dict, task_cfg: Dict | None = None
             cfg.normalize = bool(task_cfg["normalize"])
     cfg.validate()
     return cfg
+
+
+_W2V_KEYS = ("aggregator", "activation", "log_compression", "skip_connections_feat", "skip_connections_agg", "residual_scale",
+             "non_affine_group_norm", "no_conv_bias", "agg_zero_pad", "vq_type", "vq_vars", "vq_groups", "vq_dim", "vq_depth",
+             "combine_groups")
+# Wav2VecConfig defaults (wav2vec_model.py:307-318)
+W2V_DEFAULT_FEATURE_LAYERS = "[(512, 10, 5), (512, 8, 4), (512, 4, 2), (512, 4, 2), (512, 4, 2), (512, 1, 1), (512, 1, 1), (512, 1, 1)]"
+W2V_DEFAULT_AGG_LAYERS = "[" + ", ".join(f"(512, {k}, 1)" for k in range(2, 14)) + "]"
+
+
+def wav2vec_config(conv_layers, agg_layers, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "wav2vec": the Transformer fields mirror the aggregator."""
+    conv_layers, agg_layers = parse_conv_layers(conv_layers), parse_conv_layers(agg_layers)
+    cfg = EncoderConfig(family="wav2vec", conv_layers=conv_layers, agg_layers=agg_layers, encoder_layers=len(agg_layers),
+                        encoder_embed_dim=conv_layers[-1][0], **flags)
+    cfg.validate()
+    return cfg
+
+
+def config_from_wav2vec(model_cfg: Dict, task_cfg: Dict | None = None) -> EncoderConfig:
+    """``Wav2VecConfig`` (upstream/wav2vec/wav2vec_model.py:289-410) from a converted checkpoint's ``model_cfg``; keys the forward
+    does not read are dropped, missing ones take the reference defaults (``merge_with_parent``)."""
+    flags = {}
+    proto = EncoderConfig()
+    for k in _W2V_KEYS:
+        if k in model_cfg and model_cfg[k] is not None:
+            v = model_cfg[k]
+            v = getattr(v, "name", v)  # fairseq ChoiceEnum members
+            d = getattr(proto, k)
+            flags[k] = str(v) if isinstance(d, str) else type(d)(v)
+    if flags.get("vq_type") in ("None",):
+        flags["vq_type"] = "none"
+    return wav2vec_config(model_cfg.get("conv_feature_layers", W2V_DEFAULT_FEATURE_LAYERS),
+                          model_cfg.get("conv_aggregator_layers", W2V_DEFAULT_AGG_LAYERS), **flags)
 
 
 def config_from_multires(model_cfg: Dict, task_cfg: Dict | None = None) -> EncoderConfig:

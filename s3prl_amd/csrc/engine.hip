@@ -21,8 +21,9 @@ int valid_frames(const s3enc_config& c, long length, long n_max) {
     const long T = conv_len(c, n_max, c.n_conv);
     if (T <= 0) return 0;
     long v;
-    if (c.family == S3ENC_WAV2VEC2 || c.family == S3ENC_DISTILLER) {
-        v = conv_len(c, length, c.n_conv);  // wav2vec2_model.py:2652-2669; distiller/model.py:271-285
+    if (c.family == S3ENC_WAV2VEC2 || c.family == S3ENC_DISTILLER || c.family == S3ENC_WAV2VEC) {
+        // wav2vec2_model.py:2652-2669; distiller/model.py:271-285; wav2vec has no mask: the frames an utterance's own samples reach
+        v = conv_len(c, length, c.n_conv);
     } else {
         const long chunk = n_max / T;  // hubert_model.py:454-464
         v = (length + chunk - 1) / chunk;
@@ -91,7 +92,8 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 4) return fail("config: unknown family");
+    if (c.family < 0 || c.family > 5) return fail("config: unknown family");
+    if (c.family == S3ENC_WAV2VEC) return 0;  // s3enc_create_ex: wav2vec_check_config on both configuration blocks
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
         const int k = c.mr_kernel;
@@ -145,15 +147,47 @@ int check_config(const s3enc_config& c) {
 }
 }  // namespace
 
+// the handle's own device state behind the weights: staging-ring events and the status word of s3enc_forward_status
+static int finish_create(s3enc_encoder* e, s3enc_handle* out) {
+    for (int i = 0; i < s3enc_encoder::RING; ++i) {
+        if (hipEventCreateWithFlags(&e->slot_ev[i], hipEventDisableTiming) != hipSuccess) {
+            delete e;
+            return fail("hipEventCreate failed");
+        }
+    }
+    // the status word of s3enc_forward_status: device int + pinned host copy + the event behind the copy
+    bool st_ok = e->status_dev.ensure(64) == hipSuccess && hipMemset(e->status_dev.p, 0, 64) == hipSuccess &&
+                 hipHostMalloc((void**)&e->status_host, s3enc_encoder::STATUS_RING * sizeof(int), hipHostMallocDefault) == hipSuccess;
+    for (int i = 0; st_ok && i < s3enc_encoder::STATUS_RING; ++i)
+        st_ok = hipEventCreateWithFlags(&e->status_ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!st_ok) {
+        delete e;
+        return fail("s3enc_create: status word allocation failed");
+    }
+    *out = e;
+    return 0;
+}
+
 extern "C" {
 
 int s3enc_version(void) { return S3ENC_VERSION; }
 const char* s3enc_last_error(void) { return g_err.c_str(); }
 
 int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
+    return s3enc_create_ex(cfg, nullptr, tensors, n_tensors, device, out);
+}
+
+int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
+                    int32_t device, s3enc_handle* out) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
+    if (cfg->family == S3ENC_WAV2VEC) {
+        if (!w2v) return fail("s3enc_create: the wav2vec family needs its aggregator / quantizer block: use s3enc_create_ex");
+        if (wav2vec_check_config(W2vCfg(*cfg, *w2v))) return 1;
+    } else if (w2v) {
+        return fail("s3enc_create_ex: the wav2vec block belongs to family S3ENC_WAV2VEC only");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail("s3enc_create: no HIP device visible — libs3enc has no CPU fallback");
@@ -176,6 +210,14 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
     e->x2 = cfg->compute_dtype == 4;  // S3ENC_F16X2: the fp16 data flow, GEMM weights split into two fp16 terms
     e->dtype = e->x3 ? (int)F32 : (e->x2 ? (int)F16 : cfg->compute_dtype);
     e->es = e->dtype == F32 ? 4 : 2;
+    if (cfg->family == S3ENC_WAV2VEC) {
+        e->w2v_cfg = *w2v;
+        if (wav2vec_create(e, tensors, n_tensors)) {
+            delete e;
+            return 1;
+        }
+        return finish_create(e, out);
+    }
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads;
     const bool multires = c.family == S3ENC_MULTIRES;
@@ -602,23 +644,7 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
 #undef GET
 #undef UPW
 #undef UP
-    for (int i = 0; i < s3enc_encoder::RING; ++i) {
-        if (hipEventCreateWithFlags(&e->slot_ev[i], hipEventDisableTiming) != hipSuccess) {
-            delete e;
-            return fail("hipEventCreate failed");
-        }
-    }
-    // the status word of s3enc_forward_status: device int + pinned host copy + the event behind the copy
-    bool st_ok = e->status_dev.ensure(64) == hipSuccess && hipMemset(e->status_dev.p, 0, 64) == hipSuccess &&
-                 hipHostMalloc((void**)&e->status_host, s3enc_encoder::STATUS_RING * sizeof(int), hipHostMallocDefault) == hipSuccess;
-    for (int i = 0; st_ok && i < s3enc_encoder::STATUS_RING; ++i)
-        st_ok = hipEventCreateWithFlags(&e->status_ev[i], hipEventDisableTiming) == hipSuccess;
-    if (!st_ok) {
-        delete e;
-        return fail("s3enc_create: status word allocation failed");
-    }
-    *out = e;
-    return 0;
+    return finish_create(e, out);
 }
 
 int s3enc_destroy(s3enc_handle h) {
@@ -958,6 +984,7 @@ int forward_impl(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
 
 int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                  const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
+    if (e->cfg.family == S3ENC_WAV2VEC) return wav2vec_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
     const int dt = e->dtype, es = e->es;
@@ -1698,6 +1725,19 @@ int s3enc_forward_ex(s3enc_handle h, const float* const* wavs, const int64_t* le
     FwdOpts fo;
     if (parse_opts(h, opts, fo)) return 1;
     return forward_impl(h, wavs, lengths, B, n_max, fo, out, layer_stride, (hipStream_t)stream);
+}
+
+int s3enc_forward_aux(s3enc_handle h, const float* const* wavs, const int64_t* lengths, int32_t B, int64_t n_max,
+                      const s3enc_forward_opts* opts, void* out, int64_t layer_stride, float* codewords, int64_t* codeids, void* stream) {
+    if (!h || !wavs || !lengths) return fail("s3enc_forward_aux: null argument");
+    if ((codewords || codeids) && h->cfg.family != S3ENC_WAV2VEC)
+        return fail("s3enc_forward_aux: codewords / codeids are outputs of a wav2vec handle with a vector quantizer");
+    h->aux_codewords = codewords;
+    h->aux_codeids = (long long*)codeids;
+    const int rc = s3enc_forward_ex(h, wavs, lengths, B, n_max, opts, out, layer_stride, stream);
+    h->aux_codewords = nullptr;
+    h->aux_codeids = nullptr;
+    return rc;
 }
 
 int s3enc_forward_status(s3enc_handle h, int32_t wait, int32_t* status) {

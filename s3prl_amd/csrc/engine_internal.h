@@ -357,6 +357,17 @@ struct AdapterW {
     int up_rate = 1, down_rate = 1;
 };
 
+// wav2vec / vq-wav2vec (wav2vec.hip): conv0 [C][10]; every other convolution tap-major (C, k * C); GroupNorm(1, C) affine per
+// block (empty with non_affine_group_norm); the quantizer's projection(s) and its codebook as the gather table (Gt, V, Dv)
+struct W2vW {
+    std::vector<DevBuf> ext_w, ext_g, ext_b;
+    std::vector<DevBuf> agg_w, agg_bias, agg_g, agg_b;
+    std::vector<DevBuf> vq_w, vq_b;  // gumbel: weight_proj's Linear layers
+    std::vector<DevBuf> km_w;        // k-means: the grouped 1x1 projection, one (Cg, Cg) matrix per group
+    DevBuf km_g, km_b, emb_t;        // its GroupNorm(G, C) affine; the embedding as (G, Cg, V) for the distance kernel
+    DevBuf table;
+};
+
 struct ProfRec {
     int kind;
     hipEvent_t a, b;
@@ -411,6 +422,10 @@ struct s3enc_encoder {
     std::vector<BlockW> mr_blocks;      // S3ENC_MULTIRES: encoders..., middle_encoder, decoders... (execution order)
     std::vector<AdapterW> mr_adapters;  // downsample_modules[0..R-2], then upsample_modules[0..R-2]
     DevBuf ws_mr;                       // activation workspace of the U-net behind post_extract_proj
+    std::unique_ptr<W2vW> w2v;          // S3ENC_WAV2VEC
+    s3enc_wav2vec_config w2v_cfg = {};  // ... and its second configuration block (s3enc_create_ex)
+    float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
+    long long* aux_codeids = nullptr;
 
     // S3ENC_F16X2: MX-fp4 images of the weights' lo terms, keyed by the device pointer of the [hi | lo] rows they belong to
     std::map<const void*, std::unique_ptr<MxImage>> mx_images;
@@ -612,5 +627,15 @@ int num_states(const s3enc_config& c, int selection);
 // multires.hip: the U-net behind post_extract_proj (xproj: (B, T0, D) fp32, padded frames zero)
 int multires_tail(s3enc_handle e, hipStream_t st, int B, const MrPlan& plan, const std::vector<const int*>& d_valid, float* xproj,
                   void* out, long layer_stride, const FwdOpts& fo);
+
+// wav2vec.hip: the S3ENC_WAV2VEC family (its own configuration check, weights and forward schedule)
+// the family's configuration as one object: the extractor fields of s3enc_config beside the aggregator / quantizer block
+struct W2vCfg : s3enc_config, s3enc_wav2vec_config {
+    W2vCfg(const s3enc_config& a, const s3enc_wav2vec_config& b) : s3enc_config(a), s3enc_wav2vec_config(b) {}
+};
+int wav2vec_check_config(const W2vCfg& c);
+int wav2vec_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
+int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
 }  // namespace s3e

@@ -237,7 +237,8 @@ constexpr int C0_FT = 64;  // frames per block
 // FAST: packed fp32 arithmetic for the taps (v_pk_fma_f32 on channel pairs) and the packed one-transcendental GELU (common.h) — the
 // 16-bit operand modes and the split-precision modes (this kernel is VALU-bound there: 40 FMAs + ~50 GELU slots per 4
 // outputs), and the fp32 mode by default (tuning key gelu32 = 0: scalar FMAs in the same tap order and libm erff).
-template <typename T, int NG, int K0, int CS = 1, bool FAST = false>
+// RELU: the wav2vec extractor's first block (GroupNorm(1, C) folded into the per-(b, c) table, then ReLU instead of GELU).
+template <typename T, int NG, int K0, int CS = 1, bool FAST = false, bool RELU = false>
 __global__ __launch_bounds__(256) void conv0_kernel(Conv0Params p) {
     typedef typename Cvt<T>::store_t store_t;
     // 16-bit output with two channel groups per lane: the lane owns 8 CONSECUTIVE channels (groups g = 0, 1 are channels
@@ -315,7 +316,12 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Params p) {
             for (int g = 0; g < NG; ++g) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) v[g][u] = fmaf(v[g][u], a0[g][u], a1[g][u]);
-                gelu4<FAST>(v[g][0], v[g][1], v[g][2], v[g][3]);
+                if constexpr (RELU) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) v[g][u] = fmaxf(v[g][u], 0.f);
+                } else {
+                    gelu4<FAST>(v[g][0], v[g][1], v[g][2], v[g][3]);
+                }
             }
         } else {
             // Fp32LayerNorm over the C channels of this frame (wav2vec2_model.py:2887-2897), two-pass
@@ -398,6 +404,65 @@ hipError_t conv0_dispatch(const Conv0Params& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// wav2vec (wav2vec_model.py:235-286): fp32 rows, GroupNorm(1, C) table, ReLU
+hipError_t conv0_dispatch_relu(const Conv0Params& p, hipStream_t s) {
+    dim3 grid((unsigned)((p.L0 + C0_FT - 1) / C0_FT), p.wav.B);
+    const int ng = (p.C + 255) / 256;
+    if (ng <= 1)
+        hipLaunchKernelGGL((conv0_kernel<float, 1, 10, 1, false, true>), grid, dim3(256), 0, s, p);
+    else if (ng == 2)
+        hipLaunchKernelGGL((conv0_kernel<float, 1, 10, 2, false, true>), grid, dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL((conv0_kernel<float, 4, 10, 1, false, true>), grid, dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// GroupNorm(1, C) of conv0's output (Fp32GroupNorm(1, C), wav2vec_model.py:25-56): ONE mean / variance per utterance over all
+// C x L0 values, from the same lag sums gn_final_kernel reads, the channels' sums added in double in a fixed order.  Writes the
+// per-(b, c) table conv0_kernel applies: {rstd * gamma_c, beta_c - mean * rstd * gamma_c} (gamma / beta null: 1 / 0).
+__global__ __launch_bounds__(256) void gn1_final_kernel(const double* partial, int chunks, int k0, long L0, const float* w0,
+                                                        const float* gamma, const float* beta, int C, float2* gn) {
+    __shared__ double sums[STAT_K0_MAX * ROWLEN];
+    __shared__ double red[8];
+    const int b = blockIdx.x;
+    for (int e = threadIdx.x; e < k0 * ROWLEN; e += 256) {
+        double s = 0;
+        for (int c = 0; c < chunks; ++c) s += partial[((long)b * chunks + c) * k0 * ROWLEN + e];
+        sums[e] = s;
+    }
+    __syncthreads();
+    double S = 0, Q = 0;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        double m = 0, e2 = 0;
+        for (int j = 0; j < k0; ++j) {
+            const double wj = (double)w0[c * k0 + j];
+            m += wj * sums[j * ROWLEN];
+            double r = 0;
+            for (int jj = 0; jj < k0; ++jj) r += (double)w0[c * k0 + jj] * sums[j * ROWLEN + 1 + jj];
+            e2 += wj * r;
+        }
+        S += m;
+        Q += e2;
+    }
+    S = wave_sum_d(S);
+    Q = wave_sum_d(Q);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[2 * w] = S;
+        red[2 * w + 1] = Q;
+    }
+    __syncthreads();
+    const double n = (double)L0 * (double)C;
+    const double mean = ((red[0] + red[2]) + (red[4] + red[6])) / n;
+    double var = ((red[1] + red[3]) + (red[5] + red[7])) / n - mean * mean;
+    var = var > 0 ? var : 0;
+    const double rstd = 1.0 / sqrt(var + (double)LN_EPS);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const double scale = rstd * (gamma ? (double)gamma[c] : 1.0);
+        gn[(long)b * C + c] = make_float2((float)scale, (float)((beta ? (double)beta[c] : 0.0) - mean * scale));
+    }
+}
+
 }  // namespace
 
 size_t stats_partial_elems(int B, long n_max) {
@@ -425,9 +490,19 @@ hipError_t launch_gn_stats(const WavTable& w, const float2* norm, const float* w
     return hipGetLastError();
 }
 
+hipError_t launch_gn1_stats(const WavTable& w, const float2* norm, const float* w0, const float* gamma, const float* beta,
+                            int C, int k0, int s0, long L0, double* partial, float2* gn, hipStream_t s) {
+    if (k0 != 10 || s0 < 1 || s0 > 8) return hipErrorInvalidValue;
+    const int chunks = (int)((L0 + GN_FRAMES - 1) / GN_FRAMES);
+    hipLaunchKernelGGL(gn_lag_all_kernel<10>, dim3(chunks, w.B), dim3(256), 0, s, w, norm, s0, L0, partial, chunks);
+    hipLaunchKernelGGL(gn1_final_kernel, dim3(w.B), dim3(256), 0, s, partial, chunks, k0, L0, w0, gamma, beta, C, gn);
+    return hipGetLastError();
+}
+
 hipError_t launch_conv0(int dtype, const Conv0Params& p, hipStream_t s) {
     // the kernel is specialised for the first layer every released checkpoint has: k = 10, stride <= 8, C <= 1024
     if (p.k0 != 10 || p.s0 > 8 || p.s0 < 1 || p.C > 1024 || (p.C & 3)) return hipErrorInvalidValue;
+    if (p.relu) return (dtype == F32 && p.gn) ? conv0_dispatch_relu(p, s) : hipErrorInvalidValue;
     switch (dtype) {
         case F32: return ((p.fast ? tuning().conv0_fast : tuning().gelu32) == 1) ? conv0_dispatch<float, true>(p, s) : conv0_dispatch<float, false>(p, s);
         // (conv0_fast = 0: the FAST = false instantiation, a diagnostic of the concurrent-forward finding — kernels.h)

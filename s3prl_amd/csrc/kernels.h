@@ -211,7 +211,12 @@ struct Conv0Params {
     void* out;            // (B, L0, C) compute dtype
     int fast = 0;         // fp32 output with the packed one-transcendental GELU (the split-precision modes)
     int nt = 0;           // fp32 output: non-temporal stores
+    int relu = 0;         // wav2vec: ReLU instead of GELU behind the GroupNorm table (fp32 output, gn != null)
 };
+// wav2vec: GroupNorm(1, C) statistics of conv0's output (one mean / variance per utterance over all C x L0 values) from the
+// waveform's lag sums, as the per-(b, c) table {rstd * gamma_c, beta_c - mean * rstd * gamma_c}; gamma / beta may be null (1 / 0)
+hipError_t launch_gn1_stats(const WavTable& w, const float2* norm, const float* w0 /*[C][10]*/, const float* gamma,
+                            const float* beta, int C, int k0, int s0, long L0, double* partial, float2* gn, hipStream_t s);
 hipError_t launch_conv0(int dtype, const Conv0Params& p, hipStream_t s);
 
 // ---- norm.hip -------------------------------------------------------------------------------------------
@@ -344,6 +349,53 @@ hipError_t launch_emit_upsampled(int dtype, const float* x, long x_bs, int facto
 // the same state as its Featurizer term only: fa.acc[b][t] (+)= fa.w * (fa.norm ? layer_norm(x[b][t / factor]) : x[b][t / factor])
 hipError_t launch_emit_upsampled_acc(const float* x, long x_bs, int factor, int B, int rows_out, int D, const LnAcc& fa,
                                      hipStream_t s);
+
+// ---- wav2vec.hip (wav2vec / vq-wav2vec: upstream/wav2vec/wav2vec_model.py:59-286, wav2vec2_model.py:1591-1782) ------------
+// The row pass behind every convolution but the first: GroupNorm(1, C) + ReLU from the double partials of launch_group1_stats,
+//   y = relu((x - mean_b) * rstd_b * gamma_c + beta_c);  res: y = (y + res) * scale;  log: y = log(|y| + 1)
+// written to up to three places in one pass: `dst` (the next convolution's operand: per utterance `pad` rows in front of the
+// `rows` data rows, filled with frame 0 — ReplicationPad1d — or zeros), `state` (a (B, rows, C) hidden-state slot) and the
+// Featurizer term `acc`.  dst == x with pad == 0 works in place.
+struct Gn1ApplyParams {
+    const float* x;         // (B, rows, C) raw conv output, utterance b at x + b * x_bs
+    long x_bs;
+    const double* partial;  // [B][GS_BLOCKS][2] of launch_group1_stats over that output
+    double count;           // rows * C
+    const float* gamma;     // [C] or null (non_affine_group_norm)
+    const float* beta;
+    const float* res;       // skip term: row t of utterance b at res + b * res_bs + t * C, or null
+    long res_bs;
+    float scale;            // sqrt(residual_scale), used with res
+    int log;                // log(|y| + 1) (log_compression)
+    int B, rows, C;
+    int pad, pad_zero;      // rows in front of every utterance in dst; 1 = zeros (agg_zero_pad), 0 = copies of frame 0
+    float* dst;             // (B, pad + rows, C), utterance b at dst + b * dst_bs; or null
+    long dst_bs;
+    float* state;           // (B, rows, C) contiguous, or null
+    LnAcc acc;              // mode != 0: acc.acc (B, rows, C) (+)= w * (norm ? layer_norm(y) : y)
+};
+hipError_t launch_gn1_apply(const Gn1ApplyParams& p, hipStream_t s);
+// Per (row, group): the index of the largest of V scores (ties: the lowest index, like torch.max / argmin of the negated
+// distances), as int64, and the gathered codeword.  scores: (rows, G, V); table: (Gt, V, Dv) with Gt = G, or 1 when the
+// groups share their variables (combine_groups); ids: (rows, G) or null; out: (rows, G * Dv) or null.
+struct ArgmaxGatherParams {
+    const float* scores;
+    const float* table;
+    int shared;  // 1: table has one group
+    long rows;
+    int G, V, Dv;
+    long long* ids;
+    float* out;
+};
+hipError_t launch_argmax_gather(const ArgmaxGatherParams& p, hipStream_t s);
+hipError_t launch_relu(float* x, long n, hipStream_t s);  // in place, n % 4 == 0
+// (B, rows, C) contiguous -> the padded operand geometry of Gn1ApplyParams::dst
+hipError_t launch_w2v_pad_rows(const float* x, int B, int rows, int C, int pad, int pad_zero, float* dst, hipStream_t s);
+// k-means quantizer (wav2vec_model.py:117-232) behind the grouped 1x1 projection: GroupNorm(G, C) statistics per (b, group) over
+// the (rows x Cg) block of proj, then scores[row][g][v] = -|| norm(proj)[row][g] - emb[v][g] ||^2.  emb_t: (G, Cg, V).
+hipError_t launch_kmeans_stats(const float* proj, int B, int rows, int C, int G, float2* stats, hipStream_t s);
+hipError_t launch_kmeans_scores(const float* proj, const float2* stats, const float* gamma, const float* beta, const float* emb_t,
+                                int B, int rows, int C, int G, int V, float* scores, hipStream_t s);
 
 // ---- featurizer.hip (weighted sum over layers, the consumer of hidden_states) ---------------------
 #define S3_WS_MAX_LAYERS 32

@@ -237,6 +237,68 @@ int s3enc_op_conformer_conv(const float* x, const float* taps, const float* shif
     return 0;
 }
 
+int s3enc_op_gn1_apply(const float* x, const float* gamma, const float* beta, const float* res, float scale, int32_t log_compress,
+                       int32_t B, int32_t rows, int32_t C, int32_t pad, int32_t pad_zero, float* dst, float* state, float* acc,
+                       float acc_w, int32_t acc_norm, int32_t acc_init, void* stream) {
+    if (!x || (!dst && !state && !acc)) return fail("s3enc_op_gn1_apply: null argument");
+    if (B <= 0 || rows <= 0 || C <= 0 || (C & 3) || C > 1024) return fail("s3enc_op_gn1_apply: bad shape (C % 4 == 0, C <= 1024)");
+    if (pad < 0 || pad > 64 || (pad && !dst)) return fail("s3enc_op_gn1_apply: pad rows need dst (0..64)");
+    hipStream_t st = (hipStream_t)stream;
+    double* partial = nullptr;
+    HIP_TRY(hipMalloc((void**)&partial, (size_t)B * GS_BLOCKS * 2 * sizeof(double)));
+    Gn1ApplyParams p{};
+    p.x = x;
+    p.x_bs = (long)rows * C;
+    p.partial = partial;
+    p.count = (double)rows * C;
+    p.gamma = gamma;
+    p.beta = beta;
+    p.res = res;
+    p.res_bs = (long)rows * C;
+    p.scale = scale;
+    p.log = log_compress;
+    p.B = B;
+    p.rows = rows;
+    p.C = C;
+    p.pad = pad;
+    p.pad_zero = pad_zero;
+    p.dst = dst;
+    p.dst_bs = (long)(pad + rows) * C;
+    p.state = state;
+    if (acc) {
+        p.acc.acc = acc;
+        p.acc.w = acc_w;
+        p.acc.mode = 2;
+        p.acc.norm = acc_norm;
+        p.acc.init = acc_init;
+    }
+    hipError_t er = launch_group1_stats(x, (long)rows * C, (long)rows * C, B, partial, st);
+    if (er == hipSuccess) er = launch_gn1_apply(p, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(partial);
+    HIP_TRY(er);
+    HIP_TRY(es);
+    return 0;
+}
+
+int s3enc_op_argmax_gather(const float* scores, const float* table, int32_t shared, int64_t rows, int32_t G, int32_t V, int32_t Dv,
+                           int64_t* ids, float* out, void* stream) {
+    if (!scores || (!ids && !out) || (out && !table)) return fail("s3enc_op_argmax_gather: null argument");
+    if (rows <= 0 || G <= 0 || V <= 0 || Dv <= 0) return fail("s3enc_op_argmax_gather: bad shape");
+    ArgmaxGatherParams p{};
+    p.scores = scores;
+    p.table = table;
+    p.shared = shared;
+    p.rows = rows;
+    p.G = G;
+    p.V = V;
+    p.Dv = Dv;
+    p.ids = (long long*)ids;
+    p.out = out;
+    HIP_TRY(launch_argmax_gather(p, (hipStream_t)stream));
+    return 0;
+}
+
 int s3enc_op_relpos_attention(const float* qkv, float* out, const int32_t* valid, int32_t B, int32_t T, int32_t H, const float* P,
                               const float* qadd, void* stream) {
     if (!qkv || !out || !valid || !P || !qadd) return fail("s3enc_op_relpos_attention: null argument");

@@ -28,6 +28,8 @@ class HipEncoder:
         if cfg.layer_type == "conformer" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             # s3enc_create refuses it with this message too; raised here as the configuration error it is
             raise ValueError(f"conformer layers ({cfg.pos_enc_type}) are built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "wav2vec" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"wav2vec / vq-wav2vec are built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -53,7 +55,12 @@ class HipEncoder:
                 tensors[i].shape[j] = int(s)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h)), "s3enc_create")
+            if cfg.family == "wav2vec":  # its aggregator / quantizer block travels beside the (unchanged) s3enc_config
+                w2v = _lib.make_wav2vec_config(cfg)
+                rc = self._lib.s3enc_create_ex(C.byref(ccfg), C.byref(w2v), tensors, len(weights), self.device, C.byref(h))
+            else:
+                rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
+            _lib.check(rc, "s3enc_create")
         self._h = h
         self.num_layers = cfg.encoder_layers
         self.embed_dim = cfg.encoder_embed_dim
@@ -164,11 +171,13 @@ class HipEncoder:
         return dev, held, lengths, nm, T
 
     def forward(self, wavs: Sequence["torch.Tensor"], n_max: Optional[int] = None, out: Optional["torch.Tensor"] = None,
-                selection: Optional[str] = None, out_dtype: Optional[str] = None):
+                selection: Optional[str] = None, out_dtype: Optional[str] = None, aux: Optional[dict] = None):
         """wavs: list of 1-D fp32 CUDA tensors.  Returns a (NS, B, T, D) CUDA tensor; ``[i]`` is state i of
         ``selection`` (default: ``hidden_states``).  ``n_max``: pad-to length of the GLOBAL batch (data-parallel
         shards).  ``out_dtype``: None / "fp32", or the encoder's own 16-bit compute dtype ("bf16" / "fp16") to get
-        the states as 16-bit tensors (half the bytes to write and to all-gather)."""
+        the states as 16-bit tensors (half the bytes to write and to all-gather).  ``aux``: a dict that a vq-wav2vec encoder
+        fills with the quantizer's outputs of this forward: ``codewords`` (B, T, vq_dim) fp32 and ``codeids`` (B, T, groups)
+        int64 (wav2vec/expert.py:49-53)."""
         import torch
 
         dev, held, lengths, nm, T = self._prepare(wavs, n_max)
@@ -188,10 +197,22 @@ class HipEncoder:
         ptrs = (C.c_void_p * B)(*[w.data_ptr() for w in held])
         lens = (C.c_int64 * B)(*lengths)
         opts = _lib.S3ForwardOpts(_lib.SELECTIONS[selection], code, 0, 0, None)
+        cw = ci = None
+        if aux is not None:
+            if self.cfg.family != "wav2vec" or self.cfg.vq_type == "none":
+                raise ValueError("aux outputs (codewords / codeids) need a vq-wav2vec encoder")
+            cw = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+            ci = torch.empty((B, T, self.cfg.vq_groups), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = self._lib.s3enc_forward_ex(self._h, ptrs, lens, B, nm, C.byref(opts), C.c_void_p(out.data_ptr()), B * T * D,
-                                            C.c_void_p(stream))
+            if aux is not None:
+                rc = self._lib.s3enc_forward_aux(self._h, ptrs, lens, B, nm, C.byref(opts), C.c_void_p(out.data_ptr()), B * T * D,
+                                                 C.c_void_p(cw.data_ptr()), C.c_void_p(ci.data_ptr()), C.c_void_p(stream))
+            else:
+                rc = self._lib.s3enc_forward_ex(self._h, ptrs, lens, B, nm, C.byref(opts), C.c_void_p(out.data_ptr()), B * T * D,
+                                                C.c_void_p(stream))
+        if aux is not None:
+            aux["codewords"], aux["codeids"] = cw, ci
         _lib.check(rc, "s3enc_forward")
         self._after_forward()
         return out

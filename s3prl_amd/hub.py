@@ -13,6 +13,8 @@ from .upstream.multires_hubert.hubconf import *  # noqa: F401,F403
 from .upstream.hf_hubert.hubconf import *  # noqa: F401,F403
 from .upstream.hf_wav2vec2.hubconf import *  # noqa: F401,F403
 from .upstream.baseline.hubconf import *  # noqa: F401,F403
+from .upstream.wav2vec.hubconf import *  # noqa: F401,F403
+from .upstream.vq_wav2vec.hubconf import *  # noqa: F401,F403
 
 
 def options(only_registered_ckpt: bool = False):

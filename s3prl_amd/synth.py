@@ -20,6 +20,8 @@ from .config import EncoderConfig
 
 def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     """Hot-path parameter names → shapes (reference naming)."""
+    if cfg.family == "wav2vec":
+        return _wav2vec_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -117,6 +119,50 @@ def _conformer_shapes(s: Dict[str, tuple], p: str, cfg: EncoderConfig) -> None:
     s[f"{p}.conv_module.pointwise_conv2.weight"] = (D, D, 1)
     s[f"{p}.final_layer_norm.weight"] = (D,)
     s[f"{p}.final_layer_norm.bias"] = (D,)
+
+
+def _wav2vec_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """Wav2VecModel (upstream/wav2vec/wav2vec_model.py:565-700) parameters the forward reads, reference state_dict names;
+    ``wav2vec_predictions.*`` / ``project_features.*`` are training-only."""
+    s: Dict[str, tuple] = {}
+    affine = not cfg.non_affine_group_norm
+    cin = 1
+    for i, (dim, k, _) in enumerate(cfg.conv_layers):
+        p = f"feature_extractor.conv_layers.{i}"
+        s[f"{p}.0.weight"] = (dim, cin, k)
+        if affine:
+            s[f"{p}.2.weight"] = (dim,)
+            s[f"{p}.2.bias"] = (dim,)
+        cin = dim
+    C = cfg.conv_dim
+    if cfg.vq_type != "none":
+        G, V = cfg.vq_groups, cfg.vq_vars
+        Gt, Dv = (1 if cfg.combine_groups else G), C // G
+        if cfg.vq_type == "gumbel":
+            s["vector_quantizer.vars"] = (1, Gt * V, Dv)
+            if cfg.vq_depth > 1:
+                for i in range(cfg.vq_depth - 1):
+                    s[f"vector_quantizer.weight_proj.{i}.0.weight"] = (2 * C, C if i == 0 else 2 * C)
+                    s[f"vector_quantizer.weight_proj.{i}.0.bias"] = (2 * C,)
+                s[f"vector_quantizer.weight_proj.{cfg.vq_depth - 1}.weight"] = (G * V, 2 * C)
+                s[f"vector_quantizer.weight_proj.{cfg.vq_depth - 1}.bias"] = (G * V,)
+            else:
+                s["vector_quantizer.weight_proj.weight"] = (G * V, C)
+                s["vector_quantizer.weight_proj.bias"] = (G * V,)
+        else:
+            s["vector_quantizer.embedding"] = (V, Gt, Dv)
+            s["vector_quantizer.projection.0.weight"] = (C, Dv, 1)
+            s["vector_quantizer.projection.1.weight"] = (C,)
+            s["vector_quantizer.projection.1.bias"] = (C,)
+    for j, (dim, k, _) in enumerate(cfg.agg_layers):
+        p = f"feature_aggregator.conv_layers.{j}"
+        s[f"{p}.1.weight"] = (dim, C, k)
+        if not cfg.no_conv_bias:
+            s[f"{p}.1.bias"] = (dim,)
+        if affine:
+            s[f"{p}.3.weight"] = (dim,)
+            s[f"{p}.3.bias"] = (dim,)
+    return s
 
 
 def _multires_shapes(cfg: EncoderConfig, s: Dict[str, tuple]) -> Dict[str, tuple]:
@@ -245,6 +291,14 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
         leaf = name.rsplit(".", 1)[-1]
         if name.endswith("relative_attention_bias.weight"):
             w = rng.standard_normal(shape) * 0.5
+        elif name in ("vector_quantizer.embedding", "vector_quantizer.vars"):
+            # codebooks at the scale of what they are compared with / replace (a trained k-means embedding lives where the
+            # normalised projection does: unit variance; the reference's 0.01 * randn init leaves argmin decisions at rounding level)
+            w = rng.standard_normal(shape) if name.endswith("embedding") else rng.uniform(0.0, 1.0, size=shape)
+        elif name.startswith("vector_quantizer.weight_proj") and leaf == "weight":
+            w = rng.standard_normal(shape) * np.sqrt(2.0 / shape[-1])
+        elif name == "vector_quantizer.projection.0.weight":
+            w = rng.standard_normal(shape) * np.sqrt(1.0 / shape[1])
         elif name.endswith("batch_norm.running_mean"):  # non-trivial eval statistics: the BatchNorm fold is exercised
             w = 0.2 * rng.standard_normal(shape)
         elif name.endswith("batch_norm.running_var"):
@@ -370,8 +424,24 @@ def named_config(name: str) -> EncoderConfig:
                                  **{**tiny, "extractor_mode": "layer_norm", "layer_norm_first": True,
                                     "normalize": True}),
     }
+    # wav2vec / vq-wav2vec: the seven extractor layers at their real kernels and strides (receptive field 465, hop 160)
+    w2v_feat = lambda C: [(C, 10, 5), (C, 8, 4), (C, 4, 2), (C, 4, 2), (C, 4, 2), (C, 1, 1), (C, 1, 1)]  # noqa: E731
+    w2v_tiny = dict(conv_layers=w2v_feat(64), agg_layers=[(64, k, 1) for k in range(2, 6)])
+    w2v = {
+        "tiny_wav2vec": dict(**w2v_tiny),
+        "tiny_wav2vec_zeropad_noaffine": dict(agg_zero_pad=True, non_affine_group_norm=True, no_conv_bias=True,
+                                              skip_connections_agg=False, log_compression=False, **w2v_tiny),
+        "tiny_vq_wav2vec_gumbel": dict(vq_type="gumbel", vq_vars=32, vq_groups=2, vq_depth=2, **w2v_tiny),
+        "tiny_vq_wav2vec_kmeans": dict(vq_type="kmeans", vq_vars=32, vq_groups=2, **w2v_tiny),
+        # the released wav2vec_large shape as published with the model (a checkpoint's own config decides at load time)
+        "wav2vec_large": dict(conv_layers=w2v_feat(512), agg_layers=[(512, k, 1) for k in range(2, 14)]),
+    }
+    if name in w2v:
+        from .config import wav2vec_config
+
+        return wav2vec_config(**w2v[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(table)}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
