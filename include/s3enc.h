@@ -90,8 +90,10 @@ typedef struct s3enc_config {
     int32_t ffn_dim;
     int32_t heads;
     int32_t layer_norm_first;              /* 0: post-LN (base); 1: pre-LN (large) */
-    int32_t conv_pos;                      /* positional conv kernel (128) */
-    int32_t conv_pos_groups;               /* (16) */
+    int32_t conv_pos;                      /* positional conv kernel (128): 1..256 */
+    int32_t conv_pos_groups;               /* (16): embed_dim / conv_pos_groups, the group width, must be 32, 48 or 64 — for every
+                                            * layer_type (a Conformer handle packs the positional conv of its checkpoint too);
+                                            * EncoderConfig.validate refuses the same */
     int32_t normalize;                     /* per-utterance waveform layer-norm (task_cfg.normalize) */
     int32_t rel_pos;                       /* WavLM: relative_position_embedding */
     int32_t num_buckets;

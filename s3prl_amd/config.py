@@ -296,6 +296,13 @@ class EncoderConfig:
             raise ValueError("the HIP attention kernel is specialised for head_dim == 64")
         if self.encoder_embed_dim % self.conv_pos_groups:
             raise ValueError("embed_dim must be divisible by conv_pos_groups")
+        if self.encoder_embed_dim // self.conv_pos_groups not in (32, 48, 64):
+            # the positional-conv kernels are built for these group widths (s3enc_create repeats it); a Conformer never runs
+            # its positional conv, but its checkpoint carries one and the handle packs it
+            raise ValueError("embed_dim / conv_pos_groups (the positional conv's group width) must be 32, 48 or 64, got "
+                             f"{self.encoder_embed_dim} / {self.conv_pos_groups}")
+        if not 1 <= self.conv_pos <= 256:
+            raise ValueError(f"conv_pos (the positional conv's kernel) must be 1..256, got {self.conv_pos}")
 
     def _validate_wav2vec(self) -> None:
         """What the HIP path builds of ``Wav2VecConfig``; everything else is refused by name (s3enc_create repeats it)."""

@@ -60,12 +60,24 @@ def test_fixture_fp32(name, golden_loader):
 @pytest.mark.parametrize("T", [1, 17, 31, 49, 499, 749])
 def test_conv_module_op(T):
     """GLU -> depthwise conv (zero outside each utterance's T rows) -> folded BatchNorm -> swish, against float64."""
+    B, D, K = (3, 128, 31) if T < 499 else (2, 256, 31)
+    _check_conv_module(B, T, D, K, np.random.default_rng(T))
+
+
+@pytest.mark.parametrize("T", [1, 7, 8, 9, 127, 128, 129, 136])
+@pytest.mark.parametrize("D", [64, 192])
+@pytest.mark.parametrize("K", [1, 3, 7, 15, 63])
+def test_conv_module_op_kernel_and_tile_edges(K, D, T):
+    """Every kernel width class (1: no window; 63: the largest, 63.25 KiB of LDS) at one and three channel blocks, with T around
+    the 8 frames of a thread and the 128 frames of a workgroup: the window's zero rows on both sides of every utterance."""
+    _check_conv_module(3, T, D, K, np.random.default_rng((K * 1000 + D) * 1000 + T))
+
+
+def _check_conv_module(B, T, D, K, rng):
     from s3prl_amd import _lib
 
     torch = _torch()
     lib = _lib.load()
-    B, D, K = (3, 128, 31) if T < 499 else (2, 256, 31)
-    rng = np.random.default_rng(T)
     x = rng.standard_normal((B, T, 2 * D)).astype(np.float32)
     dw = (rng.standard_normal((D, K)) / np.sqrt(K)).astype(np.float32)
     bn = dict(weight=1 + 0.1 * rng.standard_normal(D), bias=0.05 * rng.standard_normal(D), running_mean=0.2 * rng.standard_normal(D),
@@ -73,25 +85,37 @@ def test_conv_module_op(T):
     sc = bn["weight"] / np.sqrt(bn["running_var"] + 1e-5)
     taps = (dw * sc[:, None]).astype(np.float32)
     shift = (bn["bias"] - bn["running_mean"] * sc).astype(np.float32)
-    out = torch.empty((B * T, D), device="cuda")
+    out = torch.full((B * T, D), float("nan"), device="cuda")
     dx, dtaps, dshift = _dev(x), _dev(taps), _dev(shift)  # (held: a temporary's memory would be reused by the next argument)
     _lib.check(lib.s3enc_op_conformer_conv(_ptr(dx), _ptr(dtaps), _ptr(dshift), B, T, D, K, _ptr(out), None),
                "s3enc_op_conformer_conv")
     torch.cuda.synchronize()
     ref = R.glu_dw_bn_swish(x.astype(np.float64), dw.astype(np.float64), bn)
-    assert O.rel_err(out.cpu().numpy().reshape(B, T, D), ref) < OP_TOL
+    got = out.cpu().numpy().reshape(B, T, D)
+    assert O.rel_err(got, ref) < OP_TOL
+    assert max(O.rel_err(got[b], ref[b]) for b in range(B)) < OP_TOL  # per utterance
 
 
 @pytest.mark.parametrize("T", [1, 17, 31, 49, 499, 749])
 def test_relpos_attention_op(T):
     """score = q.k + (q + qadd).P[(j - i) + T - 1], masked softmax, ragged valid — against float64."""
+    B, H = (3, 2) if T < 499 else (2, 4)
+    _check_relpos_attention(B, T, H, np.random.default_rng(100 + T))
+
+
+@pytest.mark.parametrize("T", [63, 64, 65])
+@pytest.mark.parametrize("H", [1, 3])
+def test_relpos_attention_op_row_tile_edges(H, T):
+    """One head and an odd head count (D = 64, 192) with T one short of, at and one past two 32-key tiles."""
+    _check_relpos_attention(3, T, H, np.random.default_rng(7000 + 10 * T + H))
+
+
+def _check_relpos_attention(B, T, H, rng):
     from s3prl_amd import _lib
 
     torch = _torch()
     lib = _lib.load()
-    B, H = (3, 2) if T < 499 else (2, 4)
     D = 64 * H
-    rng = np.random.default_rng(100 + T)
     qkv = rng.standard_normal((B, T, 3 * D)).astype(np.float32)
     qkv[..., :D] *= 0.3
     P = (0.5 * rng.standard_normal((2 * T - 1, D))).astype(np.float32)

@@ -81,8 +81,13 @@ def test_frame_arithmetic_of_the_library():
     assert enc.downsample_rate() == 160 and enc.num_states() == 5
 
 
-@pytest.mark.parametrize("C_", [64, 512])
-@pytest.mark.parametrize("T", [1, 17, 31, 49, 998])
+# launch_gn1_apply picks gn1_apply_kernel<1..4> by ceil((C / 4) / 64): 64 -> 1, 512 -> 2 (the released width), 544 and 768 -> 3,
+# 1024 -> 4; 32, 96, 288 and 544 leave lanes of the last pass without a channel quad
+GN1_SHAPES = [(T, C_) for C_ in (64, 512) for T in (1, 17, 31, 49, 998)] + \
+             [(T, C_) for C_ in (32, 96, 288, 544, 768, 1024) for T in (1, 17, 49)]
+
+
+@pytest.mark.parametrize("T,C_", GN1_SHAPES)
 def test_gn1_apply_op(T, C_):
     """GroupNorm(1, C) + ReLU [+ skip] [+ log] into the padded operand, the state slot and the Featurizer term, against float64:
     pad rows 0 / 1 / 12 of both kinds, with and without residual, log compression and a (plain / normalised) Featurizer term."""
@@ -136,10 +141,6 @@ def test_gn1_apply_op(T, C_):
 @pytest.mark.parametrize("V", [32, 320])
 def test_argmax_gather_op(V, G, rows):
     """int64 index of the largest score per (row, group), ties to the lowest index (torch.max), and the gathered codeword."""
-    from s3prl_amd import _lib
-
-    torch = _torch()
-    lib = _lib.load()
     Dv = 24
     rng = np.random.default_rng(V * 7 + G * 3 + rows)
     sc = rng.standard_normal((rows, G, V)).astype(np.float32)
@@ -151,6 +152,15 @@ def test_argmax_gather_op(V, G, rows):
         sc[r, g, a] = sc[r, g, b] = 10.0
         if V > 64 and r % 2 == 0:
             sc[r, g, (a + 64) % V] = 10.0
+    _check_argmax_gather(sc, Dv, rng)
+
+
+def _check_argmax_gather(sc, Dv, rng):
+    from s3prl_amd import _lib
+
+    torch = _torch()
+    lib = _lib.load()
+    rows, G, V = sc.shape
     for shared in (0, 1):
         table = rng.standard_normal((1 if shared else G, V, Dv)).astype(np.float32)
         ids = torch.full((rows, G), -1, dtype=torch.int64, device="cuda")
@@ -163,6 +173,36 @@ def test_argmax_gather_op(V, G, rows):
         assert np.array_equal(ids.cpu().numpy(), want)
         cw = np.stack([table[0 if shared else g][want[:, g]] for g in range(G)], axis=1).reshape(rows, G * Dv)
         assert np.array_equal(out.cpu().numpy(), cw)  # a gather: exact
+
+
+@pytest.mark.parametrize("rows", [2, 7])
+@pytest.mark.parametrize("Dv", [4, 64, 200])
+@pytest.mark.parametrize("G", [4, 16])
+@pytest.mark.parametrize("V", [1, 5, 63, 64, 65])
+def test_argmax_gather_op_lane_edges(V, G, Dv, rows):
+    """V below, at and just past one wave (idle lanes carry the INT_MAX sentinel through the shuffle reduction; V = 1: all but
+    lane 0), more groups than a workgroup's four waves, codewords of less than, exactly and more than one pass of the gather loop.
+    Planted in every case: a tie between index 0 and the last index (0 wins), a row of all-equal scores (0 wins), a largest value
+    at the last index alone, and all scores -inf but one."""
+    rng = np.random.default_rng(((V * 17 + G) * 201 + Dv) * 8 + rows)
+    sc = rng.standard_normal((rows, G, V)).astype(np.float32)
+    want = {}
+    sc[0, 0, 0] = sc[0, 0, V - 1] = 10.0            # first and last index tie (V = 1: the only one)
+    want[(0, 0)] = 0
+    sc[1, G - 1, :] = -0.75                          # all equal
+    want[(1, G - 1)] = 0
+    sc[rows - 1, 1, V - 1] = 11.0                    # the last index alone: the last lane that holds a value
+    want[(rows - 1, 1)] = V - 1
+    sc[0, 2, :] = -np.inf                            # every score -inf but one: the initial best value is -inf too
+    sc[0, 2, V // 2] = -3.0
+    want[(0, 2)] = V // 2
+    sc[1, 0, :] = 5.0                                # all equal but a smaller first entry: the second index wins
+    sc[1, 0, 0] = 4.0
+    want[(1, 0)] = min(1, V - 1)
+    ref = sc.argmax(-1)
+    for (r, g), v in want.items():
+        assert ref[r, g] == v
+    _check_argmax_gather(sc, Dv, rng)
 
 
 @pytest.mark.parametrize("cfg_name", ["tiny_wav2vec", "tiny_vq_wav2vec_kmeans"])

@@ -44,7 +44,9 @@ def pad_left(x, n, zero):
 
 
 def top2_margin(scores):
-    """per decision: (best - second best) of `scores` (..., V), largest = chosen"""
+    """per decision: (best - second best) of `scores` (..., V), largest = chosen; a single variable is no decision: inf"""
+    if scores.shape[-1] < 2:
+        return np.full(scores.shape[:-1], np.inf)
     s = np.sort(scores, axis=-1)
     return s[..., -1] - s[..., -2]
 
