@@ -396,7 +396,8 @@ int s3enc_debug_clock_sample(uint64_t* out3_device, void* stream);
  *                   operands under the current item's last key tile, 0 (default) = the one-shot grid; bit-identical results; a measured
  *                   prototype that lost (profiles/r06_attention_persist.md), kept for re-measurement;
  *   "reserve_cus":  CUs the persistent one-workgroup-per-CU GEMM of the 16-bit modes leaves out of its grid (default 0; a measurement
- *                   knob — leaving CUs to a collective's channel kernels costs more than sharing them: profiles/r05_cu_contention.md);
+ *                   knob — leaving CUs to a collective's channel kernels costs more than sharing them: profiles/r05_cu_contention.md;
+ *                   tests/test_col_edges_gpu.py sets 128 to make the persistent grid walk several tiles per workgroup on small shapes);
  *   "conv_f22":     S3ENC_F32: 1 (default) = conv layers 1.. with kernel 3 and stride 2 (conv1-4 of every extractor) run in the
  *                   two-output form (convf22.hip: 5 block products per pair of outputs instead of 6, fp32 operands and accumulation,
  *                   a different association — results differ in the last bits), 0 = the implicit GEMM;
