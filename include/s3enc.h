@@ -45,7 +45,12 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * extractor, an optional vector quantizer and a causal convolutional aggregator — no Transformer, no frame mask.  The
         * states are z (the extractor output) and every aggregator layer's output: n_agg + 1 states of (B, T, conv_dim).
         * compute_dtype S3ENC_F32 only. */
-       S3ENC_WAV2VEC = 5 };
+       S3ENC_WAV2VEC = 5,
+       /* modified CPC (upstream/cpc/model.py:62-104,146-191, expert.py:25-49): five strided Conv1d layers with symmetric zero
+        * padding, each followed by a per-frame channel norm and ReLU, then a multi-layer LSTM or GRU over the whole padded
+        * time axis — no frame mask.  Two states of (B, T, width): the encoder output and the recurrent output.
+        * compute_dtype S3ENC_F32 only; built by s3enc_create_cpc. */
+       S3ENC_CPC = 6 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -163,6 +168,28 @@ typedef struct s3enc_wav2vec_config {
     int32_t combine_groups;                         /* the groups share one set of variables */
 } s3enc_wav2vec_config;
 
+/* S3ENC_CPC only (cpc_default_config.py, cpc/model.py:62-104,146-191): the second configuration block of s3enc_create_cpc.
+ * s3enc_config carries the extractor as for every family (n_conv, conv_dim, conv_kernel (10,8,4,4,4), conv_stride (5,4,2,2,2));
+ * encoder_layers = 1 and embed_dim = conv_dim; its Transformer fields are ignored.  Every convolution has a bias and `conv_pad`
+ * zero frames on both sides (L_out = floor((L_in + 2 pad - k) / stride) + 1) and is followed by ChannelNorm — per frame over the
+ * C channels, (x - mean) * rsqrt(var + 1e-5) * weight + bias with the UNBIASED variance (divide by C - 1) — and ReLU.  The
+ * recurrent network is torch's nn.LSTM (gates i, f, g, o) or nn.GRU (gates r, z, n; b_hn inside the product with r), batch_first,
+ * zero initial state, run over the padded time axis.  Checkpoint tensors, reference state_dict names: gEncoder.convN.{weight,bias},
+ * gEncoder.batchNormN.{weight,bias} (1, C, 1), gAR.baseNet.{weight_ih,weight_hh,bias_ih,bias_hh}_lN; every one of them is
+ * required (the reference's load_state_dict(strict=False) would keep a random initialisation instead).  s3enc_create_cpc refuses
+ * by name what is not built: every compute dtype but fp32, norm_mode other than layerNorm, arMode RNN / transformer / no_ar,
+ * cpc_mode "reverse", samplingType "sequential" (keep_hidden: state carried between forwards), hiddenGar != hiddenEncoder,
+ * widths that are not a multiple of 64 or above 512, more than 4 recurrent layers. */
+typedef struct s3enc_cpc_config {
+    int32_t conv_pad[S3ENC_MAX_CONV];               /* (3,2,1,1,1) */
+    int32_t norm_mode;                              /* 0 layerNorm (ChannelNorm); 1 instanceNorm, 2 ID, 3 batchNorm (refused) */
+    int32_t ar_mode;                                /* 0 LSTM, 1 GRU; 2 RNN, 3 transformer, 4 no_ar (refused) */
+    int32_t ar_layers;                              /* nLevelsGRU: 1..4 */
+    int32_t ar_hidden;                              /* hiddenGar: equal to conv_dim */
+    int32_t reverse;                                /* cpc_mode == "reverse" (refused) */
+    int32_t keep_hidden;                            /* samplingType == "sequential" (refused) */
+} s3enc_cpc_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -186,6 +213,13 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
  * Replaces UpstreamExpert.__init__ of upstream/wav2vec/expert.py:16-34 (load_converted_model, wav2vec/convert.py:24-37). */
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out);
+/* The S3ENC_CPC family: s3enc_config beside its own block (s3enc_create and s3enc_create_ex refuse that family by name: they have no
+ * place for the paddings and the recurrent network).  Replaces UpstreamExpert.__init__ of upstream/cpc/expert.py:26-42.  On the
+ * handle: s3enc_num_frames / _num_output_frames count with the paddings (159 samples give one frame, fewer give 0 and the forward
+ * refuses them), s3enc_valid_frames follows the wav2vec convention (the frames the utterance's own samples reach),
+ * s3enc_num_states is 2 for S3ENC_SEL_HIDDEN (the other selections are refused), out_dtype must be S3ENC_F32. */
+int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
+                     int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -491,6 +525,20 @@ int s3enc_op_gn1_apply(const float* x, const float* gamma, const float* beta, co
  * (rows, G) or NULL; out: device fp32 (rows, G * Dv) or NULL. */
 int s3enc_op_argmax_gather(const float* scores, const float* table, int32_t shared, int64_t rows, int32_t G, int32_t V, int32_t Dv,
                            int64_t* ids, float* out, void* stream);
+
+/* modified CPC: the row pass behind a convolution (cpc/model.py:33-59,99-104): per frame over the C channels
+ * y = relu((x - mean) * rsqrt(var + 1e-5) * gamma + beta), var unbiased (divided by C - 1).  x: device fp32 (B, rows, C);
+ * gamma / beta: device (C) or NULL (1 / 0); dst: device (B, pad + rows + pad, C) or NULL: the next convolution's operand, its
+ * `pad` rows in front of and behind every utterance written as zeros; state: device (B, rows, C) or NULL.  C % 4 == 0, C <= 1024. */
+int s3enc_op_channelnorm_relu(const float* x, const float* gamma, const float* beta, int32_t B, int32_t rows, int32_t C,
+                              int32_t pad, float* dst, float* state, void* stream);
+/* The recurrence of nn.LSTM (cell 0) / nn.GRU (cell 1), batch_first, zero initial state, all T steps in one launch, one
+ * workgroup per utterance.  gates = 4 (i, f, g, o) / 3 (r, z, n).  pre: device fp32, row (b, t) at pre + (b * T + t) * ld_pre,
+ * gates * H values x W_ih^T + b_ih plus the part of b_hh that may be folded (LSTM: all of it; GRU: the r and z parts only).
+ * w_hh_host: HOST fp32 (gates * H, H), nn's weight_hh_l*; packed and uploaded inside.  b_hn: device (H), GRU's b_hh[2H:3H], NULL
+ * for LSTM.  out: device fp32, row (b, t) at out + (b * T + t) * ldo, H values.  H % 64 == 0, H <= 512.  Synchronises. */
+int s3enc_op_rnn(int32_t cell, const float* pre, const float* w_hh_host, const float* b_hn, int32_t B, int32_t T, int32_t H,
+                 int64_t ld_pre, float* out, int64_t ldo, void* stream);
 
 /* Convolutional position embedding + residual: out = x + GELU(SamePad(Conv1d(D, D, K, padding=K/2, groups=G)(x)) + bias)
  * (make_conv_pos / SamePad, wav2vec2_model.py:2937-2953,1797-1808).  x, out: device fp32 (B, T, D); w_host: HOST fp32

@@ -19,7 +19,9 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6}
+CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
+CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 VQ_TYPE = {"none": 0, "gumbel": 1, "kmeans": 2}  # s3enc_config.vq_type
 SEL_HIDDEN, SEL_LAYER_OUT, SEL_FFN_OUT = 0, 1, 2
 SELECTIONS = {None: SEL_HIDDEN, "hidden_states": SEL_HIDDEN, "fairseq_layers": SEL_LAYER_OUT,
@@ -57,6 +59,14 @@ class S3Wav2vecConfig(C.Structure):
     ]
 
 
+class S3CpcConfig(C.Structure):
+    """s3enc_cpc_config: the padding / recurrent-network block of a modified-CPC handle (s3enc_create_cpc)."""
+    _fields_ = [
+        ("conv_pad", C.c_int32 * S3ENC_MAX_CONV), ("norm_mode", C.c_int32), ("ar_mode", C.c_int32), ("ar_layers", C.c_int32),
+        ("ar_hidden", C.c_int32), ("reverse", C.c_int32), ("keep_hidden", C.c_int32),
+    ]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -84,6 +94,7 @@ _PROTOS = {
     "s3enc_last_error": (C.c_char_p, []),
     "s3enc_create": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_ex": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Wav2vecConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    "s3enc_create_cpc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3CpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -126,6 +137,8 @@ _PROTOS = {
     "s3enc_op_conformer_conv": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP]),
     "s3enc_op_gn1_apply": (C.c_int, [_VP, _VP, _VP, _VP, C.c_float, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, C.c_float,
                                      _I32, _I32, _VP]),
+    "s3enc_op_channelnorm_relu": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),
+    "s3enc_op_rnn": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I64, _VP, _I64, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
@@ -248,4 +261,20 @@ def make_wav2vec_config(cfg) -> S3Wav2vecConfig:
     c.vq_vars, c.vq_groups, c.vq_depth = int(cfg.vq_vars), int(cfg.vq_groups), int(cfg.vq_depth)
     c.vq_dim = int(cfg.vq_dim) or cfg.conv_dim
     c.combine_groups = int(cfg.combine_groups)
+    return c
+
+
+def make_cpc_config(cfg) -> S3CpcConfig:
+    """The second configuration block of a ``family="cpc"`` EncoderConfig (``s3enc_create_cpc``)."""
+    if cfg.family != "cpc":
+        raise S3EncError("make_cpc_config needs a cpc configuration")
+    c = S3CpcConfig()
+    if len(cfg.conv_pads) > S3ENC_MAX_CONV:
+        raise S3EncError("too many conv layers")
+    for i, p in enumerate(cfg.conv_pads):
+        c.conv_pad[i] = int(p)
+    c.norm_mode = CPC_NORM.get(cfg.norm_mode, -1)
+    c.ar_mode = CPC_AR.get(cfg.ar_mode, -1)
+    c.ar_layers, c.ar_hidden = int(cfg.ar_layers), int(cfg.ar_hidden)
+    c.reverse, c.keep_hidden = int(cfg.cpc_reverse), int(cfg.cpc_keep_hidden)
     return c

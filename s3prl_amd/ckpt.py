@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, config_from_cpc, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -43,8 +43,39 @@ def _plain(d):
     return dict(vars(d))
 
 
+def load_cpc_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"config": dict, "weights": state_dict}`` (upstream/cpc/expert.py:29-36): the checkpoint's ``config`` overrides the defaults
+    of ``cpc_default_config.py``.  The reference loads the weights with ``strict=False`` — a missing tensor silently keeps its random
+    initialisation, which nobody can reproduce — so every tensor the forward reads is required here."""
+    import torch
+
+    state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    for key in ("config", "weights"):
+        if key not in state:
+            raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: {key} is missing")
+    config = state["config"]
+    cfg = config_from_cpc(config if isinstance(config, dict) else _plain(config))
+    return cfg, _hot_path_weights(ckpt, cfg, state["weights"])
+
+
+def _hot_path_weights(ckpt: str, cfg: EncoderConfig, sd) -> Dict[str, np.ndarray]:
+    weights = {}
+    for name, shape in param_shapes(cfg).items():
+        if name not in sd:
+            raise ValueError(f"{ckpt}: missing parameter {name}")
+        w = sd[name]
+        w = w.detach().cpu().float().numpy() if hasattr(w, "detach") else np.asarray(w, dtype=np.float32)
+        if tuple(w.shape) != tuple(shape):
+            raise ValueError(f"{ckpt}: parameter {name} has shape {tuple(w.shape)}, expected {tuple(shape)}")
+        weights[name] = np.ascontiguousarray(w)
+    return weights
+
+
 def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
     import torch
+
+    if family == "cpc":
+        return load_cpc_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -92,6 +123,12 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
     import torch
 
     sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.items()}
+    if cfg.family == "cpc":  # upstream/cpc/expert.py:29-36
+        config = dict(hiddenEncoder=cfg.conv_dim, hiddenGar=cfg.ar_hidden, arMode=cfg.ar_mode, nLevelsGRU=cfg.ar_layers,
+                      normMode=cfg.norm_mode, encoder_type="cpc", cpc_mode="reverse" if cfg.cpc_reverse else None,
+                      samplingType="sequential" if cfg.cpc_keep_hidden else "samespeaker")
+        torch.save({"config": config, "weights": sd}, path)
+        return
     if cfg.family == "wav2vec":
         w2v = dict(conv_feature_layers=str([tuple(t) for t in cfg.conv_layers]),
                    conv_aggregator_layers=str([tuple(t) for t in cfg.agg_layers]), aggregator=cfg.aggregator,

@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -121,6 +121,17 @@ class EncoderConfig:
     vq_dim: int = 0        # 0 = the extractor width
     vq_depth: int = 1
     combine_groups: bool = False
+    # modified CPC (family "cpc", upstream/cpc/model.py:62-104,146-191, cpc_default_config.py): ``conv_layers`` with ``conv_pads``
+    # zero frames on both sides of every convolution, each followed by a per-frame channel norm and ReLU, then ``ar_layers``
+    # LSTM / GRU layers of width ``ar_hidden``.  No Transformer: ``encoder_layers`` = 1 and ``encoder_embed_dim`` = the conv
+    # width, so the states are 2 x (B, T, C): the encoder output and the recurrent output
+    conv_pads: List[int] = field(default_factory=list)
+    norm_mode: str = "layerNorm"   # normMode: only the channel norm is built
+    ar_mode: str = "LSTM"          # arMode: "LSTM" | "GRU"
+    ar_layers: int = 1             # nLevelsGRU
+    ar_hidden: int = 256           # hiddenGar
+    cpc_reverse: bool = False      # cpc_mode == "reverse" (refused)
+    cpc_keep_hidden: bool = False  # samplingType == "sequential" (refused)
 
     # ---- derived -------------------------------------------------------------------------
     @property
@@ -151,10 +162,11 @@ class EncoderConfig:
         return r
 
     def conv_lengths(self, n: int) -> List[int]:
-        """floor((L-k)/s)+1 per layer (wav2vec2_model.py:2615-2616)."""
+        """floor((L-k)/s)+1 per layer (wav2vec2_model.py:2615-2616); modified CPC: floor((L + 2 pad - k)/s)+1."""
         out = []
-        for _, k, s in self.conv_layers:
-            n = (n - k) // s + 1 if n >= k else 0
+        pads = self.conv_pads if self.family == "cpc" else [0] * len(self.conv_layers)
+        for (_, k, s), p in zip(self.conv_layers, pads):
+            n = (n + 2 * p - k) // s + 1 if n > 0 and n + 2 * p >= k else 0
             out.append(n)
         return out
 
@@ -172,7 +184,7 @@ class EncoderConfig:
         T = self.num_frames(n_max)
         if T <= 0:
             return 0
-        if self.family in ("wav2vec2", "distiller", "wav2vec"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec: no mask
+        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -271,6 +283,8 @@ class EncoderConfig:
                                          "conv is run as `rate` interleaved stride-1 convs)")
         if self.family == "wav2vec":
             return self._validate_wav2vec()
+        if self.family == "cpc":
+            return self._validate_cpc()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -327,6 +341,27 @@ class EncoderConfig:
                 raise ValueError("wav2vec vq_dim must be 0 or the extractor width (the aggregator reads the codewords)")
             if self.conv_dim % self.vq_groups or (self.conv_dim // self.vq_groups) % 4:
                 raise ValueError("wav2vec vq_groups must divide the width into multiples of 4")
+
+    def _validate_cpc(self) -> None:
+        """What the HIP path builds of the CPC configuration; everything else is refused by name (s3enc_create_cpc repeats it)."""
+        if self.norm_mode != "layerNorm":
+            raise ValueError(f"cpc normMode={self.norm_mode!r} is not built: only 'layerNorm' (the channel norm)")
+        if self.ar_mode not in ("LSTM", "GRU"):
+            raise ValueError(f"cpc arMode={self.ar_mode!r} is not built: only 'LSTM' and 'GRU'")
+        if self.cpc_reverse:
+            raise ValueError("cpc_mode='reverse' is not built")
+        if self.cpc_keep_hidden:
+            raise ValueError("cpc samplingType='sequential' (the recurrent state carried between forwards) is not built")
+        if len({d for d, _, _ in self.conv_layers}) != 1 or len(self.conv_pads) != len(self.conv_layers):
+            raise ValueError("cpc needs conv layers of one width and one padding per layer")
+        if self.ar_hidden != self.conv_dim:
+            raise ValueError(f"cpc hiddenGar != hiddenEncoder ({self.ar_hidden} != {self.conv_dim}) is not built: the two states share one width")
+        if self.conv_dim % 64 or not 64 <= self.conv_dim <= 512:
+            raise ValueError(f"cpc widths must be a multiple of 64, at most 512 (the recurrent kernel's limit), got {self.conv_dim}")
+        if not 1 <= self.ar_layers <= 4:
+            raise ValueError(f"cpc nLevelsGRU must be 1..4 recurrent layers, got {self.ar_layers}")
+        if self.encoder_layers != 1 or self.encoder_embed_dim != self.conv_dim:
+            raise ValueError("cpc: encoder_layers / encoder_embed_dim must be 1 / the conv width (cpc_config sets them)")
 
     def to_dict(self) -> Dict:
         return asdict(self)
@@ -405,6 +440,31 @@ def config_from_wav2vec(model_cfg: Dict, task_cfg: Dict | None = None) -> Encode
         flags["vq_type"] = "none"
     return wav2vec_config(model_cfg.get("conv_feature_layers", W2V_DEFAULT_FEATURE_LAYERS),
                           model_cfg.get("conv_aggregator_layers", W2V_DEFAULT_AGG_LAYERS), **flags)
+
+
+# cpc_default_config.py: the arguments the forward reads, at their defaults
+CPC_DEFAULTS = dict(hiddenEncoder=256, hiddenGar=256, arMode="LSTM", nLevelsGRU=1, normMode="layerNorm", encoder_type="cpc",
+                    cpc_mode=None, samplingType="samespeaker")
+
+
+def cpc_config(hidden: int = 256, ar_mode: str = "LSTM", ar_layers: int = 1, ar_hidden: int | None = None, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "cpc" (CPCEncoder's five convolutions, cpc/model.py:84-93)."""
+    C = int(hidden)
+    cfg = EncoderConfig(family="cpc", conv_layers=[(C, 10, 5), (C, 8, 4), (C, 4, 2), (C, 4, 2), (C, 4, 2)], conv_pads=[3, 2, 1, 1, 1],
+                        conv_bias=True, encoder_layers=1, encoder_embed_dim=C, ar_mode=str(ar_mode), ar_layers=int(ar_layers),
+                        ar_hidden=int(C if ar_hidden is None else ar_hidden), **flags)
+    cfg.validate()
+    return cfg
+
+
+def config_from_cpc(config: Dict) -> EncoderConfig:
+    """The checkpoint's ``config`` dict over the defaults, exactly as ``loadArgs`` merges them (cpc/expert.py:29-31)."""
+    a = dict(CPC_DEFAULTS)
+    a.update({k: v for k, v in config.items() if k in CPC_DEFAULTS})
+    if a["encoder_type"] != "cpc":
+        raise ValueError(f"cpc encoder_type={a['encoder_type']!r} is not built: only 'cpc' (the convolutional encoder)")
+    return cpc_config(a["hiddenEncoder"], a["arMode"], a["nLevelsGRU"], a["hiddenGar"], norm_mode=str(a["normMode"]),
+                      cpc_reverse=a["cpc_mode"] == "reverse", cpc_keep_hidden=a["samplingType"] == "sequential")
 
 
 def config_from_multires(model_cfg: Dict, task_cfg: Dict | None = None) -> EncoderConfig:

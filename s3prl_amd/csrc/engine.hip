@@ -92,8 +92,9 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 5) return fail("config: unknown family");
+    if (c.family < 0 || c.family > 6) return fail("config: unknown family");
     if (c.family == S3ENC_WAV2VEC) return 0;  // s3enc_create_ex: wav2vec_check_config on both configuration blocks
+    if (c.family == S3ENC_CPC) return 0;      // s3enc_create_cpc: cpc_check_config on both configuration blocks
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
         const int k = c.mr_kernel;
@@ -177,11 +178,34 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
     return s3enc_create_ex(cfg, nullptr, tensors, n_tensors, device, out);
 }
 
+static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
+                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
+
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out) {
+    if (cfg && cfg->family == S3ENC_CPC) {
+        if (out) *out = nullptr;
+        return fail("s3enc_create: the modified-CPC family needs its padding / recurrent-network block: use s3enc_create_cpc");
+    }
+    return create_impl(cfg, w2v, nullptr, tensors, n_tensors, device, out);
+}
+
+int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
+                     int32_t device, s3enc_handle* out) {
+    if (!cfg || !cpc || !tensors || !out) return fail("s3enc_create_cpc: null argument");
+    *out = nullptr;
+    if (cfg->family != S3ENC_CPC) return fail("s3enc_create_cpc: the cpc block belongs to family S3ENC_CPC only");
+    return create_impl(cfg, nullptr, cpc, tensors, n_tensors, device, out);
+}
+
+static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
+                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
+    if (cfg->family == S3ENC_CPC) {
+        if (cpc_check_config(*cfg, *cpc)) return 1;
+    }
     if (cfg->family == S3ENC_WAV2VEC) {
         if (!w2v) return fail("s3enc_create: the wav2vec family needs its aggregator / quantizer block: use s3enc_create_ex");
         if (wav2vec_check_config(W2vCfg(*cfg, *w2v))) return 1;
@@ -213,6 +237,14 @@ int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, co
     if (cfg->family == S3ENC_WAV2VEC) {
         e->w2v_cfg = *w2v;
         if (wav2vec_create(e, tensors, n_tensors)) {
+            delete e;
+            return 1;
+        }
+        return finish_create(e, out);
+    }
+    if (cfg->family == S3ENC_CPC) {
+        e->cpc_cfg = *cpc;
+        if (cpc_create(e, tensors, n_tensors)) {
             delete e;
             return 1;
         }
@@ -657,12 +689,14 @@ int s3enc_destroy(s3enc_handle h) {
 
 int s3enc_num_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
     if (!h || !T) return fail("s3enc_num_frames: null argument");
-    *T = (int32_t)conv_len(h->cfg, n_samples, h->cfg.n_conv);
+    *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
+                                              : conv_len(h->cfg, n_samples, h->cfg.n_conv));
     return 0;
 }
 int s3enc_num_output_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
     if (!h || !T) return fail("s3enc_num_output_frames: null argument");
-    *T = (int32_t)output_frames(h->cfg, n_samples);
+    *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
+                                              : output_frames(h->cfg, n_samples));
     return 0;
 }
 int s3enc_downsample_rate(s3enc_handle h, int32_t* rate) {
@@ -674,6 +708,12 @@ int s3enc_downsample_rate(s3enc_handle h, int32_t* rate) {
 }
 int s3enc_valid_frames(s3enc_handle h, int64_t length, int64_t n_max, int32_t* valid) {
     if (!h || !valid) return fail("s3enc_valid_frames: null argument");
+    if (h->cfg.family == S3ENC_CPC) {  // no mask: the frames the utterance's own samples reach (the wav2vec convention)
+        const long T = cpc_conv_len(h->cfg, h->cpc_cfg, n_max, h->cfg.n_conv);
+        const long v = cpc_conv_len(h->cfg, h->cpc_cfg, length, h->cfg.n_conv);
+        *valid = (int32_t)(T <= 0 ? 0 : std::max(0L, std::min(v, T)));
+        return 0;
+    }
     *valid = valid_frames(h->cfg, length, n_max);
     return 0;
 }
@@ -985,6 +1025,7 @@ int forward_impl(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
 int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                  const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     if (e->cfg.family == S3ENC_WAV2VEC) return wav2vec_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+    if (e->cfg.family == S3ENC_CPC) return cpc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
     const int dt = e->dtype, es = e->es;
@@ -1756,6 +1797,8 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
         return fail("s3enc_num_states: DistilHuBERT / multires-HuBERT have one selection (their hidden_states list)");
     if (h->cfg.layer_type == 1 && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: feature_selection is not defined for a Conformer encoder");
+    if (h->cfg.family == S3ENC_CPC && selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_num_states: feature_selection is not defined for modified CPC (one hidden_states list of 2 states)");
     *n = num_states(h->cfg, selection);
     return 0;
 }

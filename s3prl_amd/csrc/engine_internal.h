@@ -2,6 +2,7 @@
 // the handle (struct s3enc_encoder), per-kernel profiling, the workspace allocator and the multires-HuBERT plan.
 //   engine.hip    s3enc_create (weight packing), the single-resolution forward schedule, the handle's C ABI
 //   multires.hip  the multires-HuBERT U-net behind post_extract_proj
+//   wav2vec.hip / cpc.hip  the convolutional families (wav2vec, modified CPC); rnn.hip: the LSTM / GRU recurrence
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
 #pragma once
 #include <hip/hip_runtime.h>
@@ -368,6 +369,14 @@ struct W2vW {
     DevBuf table;
 };
 
+// modified CPC (cpc.hip): conv0 [C][10]; conv1.. tap-major (C, k * C); every convolution's bias and ChannelNorm affine; per recurrent
+// layer weight_ih (G H, H) as the input projection's GEMM operand, its bias b_ih + the foldable part of b_hh, weight_hh in
+// rnn.hip's k-quad-major layout and, for a GRU, b_hn
+struct CpcW {
+    std::vector<DevBuf> conv_w, conv_b, cn_g, cn_b;
+    std::vector<DevBuf> w_ih, b_pre, w_hh, b_hn;
+};
+
 struct ProfRec {
     int kind;
     hipEvent_t a, b;
@@ -424,6 +433,8 @@ struct s3enc_encoder {
     DevBuf ws_mr;                       // activation workspace of the U-net behind post_extract_proj
     std::unique_ptr<W2vW> w2v;          // S3ENC_WAV2VEC
     s3enc_wav2vec_config w2v_cfg = {};  // ... and its second configuration block (s3enc_create_ex)
+    std::unique_ptr<CpcW> cpc;          // S3ENC_CPC
+    s3enc_cpc_config cpc_cfg = {};      // ... and its second configuration block (s3enc_create_cpc)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -637,5 +648,12 @@ int wav2vec_check_config(const W2vCfg& c);
 int wav2vec_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
 int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                     const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+
+// cpc.hip: the S3ENC_CPC family (its own configuration check, weights and forward schedule); frames through the padded conv stack
+long cpc_conv_len(const s3enc_config& c, const s3enc_cpc_config& x, long n, int upto /*exclusive*/);
+int cpc_check_config(const s3enc_config& c, const s3enc_cpc_config& x);
+int cpc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
+int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
 }  // namespace s3e

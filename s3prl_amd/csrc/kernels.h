@@ -397,6 +397,50 @@ hipError_t launch_kmeans_stats(const float* proj, int B, int rows, int C, int G,
 hipError_t launch_kmeans_scores(const float* proj, const float2* stats, const float* gamma, const float* beta, const float* emb_t,
                                 int B, int rows, int C, int G, int V, float* scores, hipStream_t s);
 
+// ---- cpc.hip (modified CPC encoder: upstream/cpc/model.py:33-104) ------------------------------------------------------
+// conv0 from the waveform table: Conv1d(1, C, k0 = 10, stride s0, padding pad0) + bias -> ChannelNorm (per frame over the C
+// channels, unbiased variance, eps 1e-5) -> ReLU, written channel-last into the next convolution's operand: per utterance
+// `pad` zero rows, the L0 frames, `pad` zero rows.  Samples outside [0, lens[b]) read as zero.
+struct CpcConv0Params {
+    WavTable wav;
+    const float* w0;     // [C][10]
+    const float* bias;   // [C]
+    const float* gamma;  // [C] or null
+    const float* beta;
+    int C, s0, pad0;
+    long L0;
+    int pad;             // border rows of dst
+    float* dst;          // (B, pad + L0 + pad, C)
+};
+hipError_t launch_cpc_conv0(const CpcConv0Params& p, hipStream_t s);
+// The row pass behind conv1..: ChannelNorm + ReLU of the raw convolution output (bias already added), a wave per frame.
+struct ChannelNormParams {
+    const float* x;      // (B, rows, C) contiguous
+    const float* gamma;  // [C] or null
+    const float* beta;
+    int B, rows, C;
+    int pad;             // zero rows in front of and behind every utterance in dst
+    float* dst;          // (B, pad + rows + pad, C) or null
+    float* state;        // (B, rows, C) or null
+};
+hipError_t launch_channelnorm_relu(const ChannelNormParams& p, hipStream_t s);
+
+// ---- rnn.hip (nn.LSTM / nn.GRU recurrence, one workgroup per utterance, all T steps in one launch) ---------------------
+constexpr int RNN_H_MAX = 512;  // hidden width limit (a multiple of 64): gate rows are walked by up to 1024 threads, two rows each
+struct RnnParams {
+    int cell;            // 0 LSTM (i, f, g, o), 1 GRU (r, z, n)
+    const float* pre;    // row (b, t) at pre + (b * T + t) * ld_pre: gates * H values, x W_ih^T + the foldable biases
+    const float* w;      // pack_rnn_whh image of weight_hh
+    const float* b_hn;   // GRU: [H]; LSTM: null
+    int B, T, H;
+    long ld_pre;
+    float* out;          // row (b, t) at out + (b * T + t) * ldo
+    long ldo;
+};
+// host: weight_hh (gates * H, H) -> [H / 4][gates * H][4]: thread r of a step reads 16 consecutive bytes next to thread r + 1's
+void pack_rnn_whh(const float* w, int gates, int H, std::vector<float>& out);
+hipError_t launch_rnn(const RnnParams& p, hipStream_t s);
+
 // ---- featurizer.hip (weighted sum over layers, the consumer of hidden_states) ---------------------
 #define S3_WS_MAX_LAYERS 32
 // out[row] = sum_l w[l] * (normalize ? layer_norm(hs[l][row]) : hs[l][row]);  w: HOST array (softmax already applied,

@@ -281,6 +281,54 @@ int s3enc_op_gn1_apply(const float* x, const float* gamma, const float* beta, co
     return 0;
 }
 
+int s3enc_op_channelnorm_relu(const float* x, const float* gamma, const float* beta, int32_t B, int32_t rows, int32_t C, int32_t pad,
+                              float* dst, float* state, void* stream) {
+    if (!x || (!dst && !state)) return fail("s3enc_op_channelnorm_relu: null argument");
+    if (B <= 0 || rows <= 0 || C < 8 || (C & 3) || C > 1024) return fail("s3enc_op_channelnorm_relu: bad shape (C % 4 == 0, 8 <= C <= 1024)");
+    if (pad < 0 || pad > 64 || (pad && !dst)) return fail("s3enc_op_channelnorm_relu: border rows need dst (0..64)");
+    ChannelNormParams p{};
+    p.x = x;
+    p.gamma = gamma;
+    p.beta = beta;
+    p.B = B;
+    p.rows = rows;
+    p.C = C;
+    p.pad = pad;
+    p.dst = dst;
+    p.state = state;
+    HIP_TRY(launch_channelnorm_relu(p, (hipStream_t)stream));
+    return 0;
+}
+
+int s3enc_op_rnn(int32_t cell, const float* pre, const float* w_hh_host, const float* b_hn, int32_t B, int32_t T, int32_t H,
+                 int64_t ld_pre, float* out, int64_t ldo, void* stream) {
+    if (!pre || !w_hh_host || !out) return fail("s3enc_op_rnn: null argument");
+    if (cell < 0 || cell > 1) return fail("s3enc_op_rnn: cell must be 0 (LSTM) or 1 (GRU)");
+    if ((cell == 1) != (b_hn != nullptr)) return fail("s3enc_op_rnn: b_hn belongs to the GRU cell (NULL for LSTM)");
+    if (B <= 0 || T <= 0) return fail("s3enc_op_rnn: bad shape");
+    if (H < 64 || H % 64 || H > RNN_H_MAX) return fail("s3enc_op_rnn: H must be a multiple of 64, at most 512");
+    const int G = cell == 0 ? 4 : 3;
+    if (ld_pre < (int64_t)G * H || ldo < H) return fail("s3enc_op_rnn: ld_pre / ldo smaller than the row");
+    std::vector<float> packed;
+    pack_rnn_whh(w_hh_host, G, H, packed);
+    DevBuf dw;
+    HIP_TRY(upload_f32(dw, packed));
+    RnnParams p{};
+    p.cell = cell;
+    p.pre = pre;
+    p.w = (const float*)dw.p;
+    p.b_hn = b_hn;
+    p.B = B;
+    p.T = T;
+    p.H = H;
+    p.ld_pre = ld_pre;
+    p.out = out;
+    p.ldo = ldo;
+    HIP_TRY(launch_rnn(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
+    return 0;
+}
+
 int s3enc_op_argmax_gather(const float* scores, const float* table, int32_t shared, int64_t rows, int32_t G, int32_t V, int32_t Dv,
                            int64_t* ids, float* out, void* stream) {
     if (!scores || (!ids && !out) || (out && !table)) return fail("s3enc_op_argmax_gather: null argument");

@@ -30,6 +30,8 @@ class HipEncoder:
             raise ValueError(f"conformer layers ({cfg.pos_enc_type}) are built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "wav2vec" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             raise ValueError(f"wav2vec / vq-wav2vec are built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "cpc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"modified CPC is built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -58,6 +60,9 @@ class HipEncoder:
             if cfg.family == "wav2vec":  # its aggregator / quantizer block travels beside the (unchanged) s3enc_config
                 w2v = _lib.make_wav2vec_config(cfg)
                 rc = self._lib.s3enc_create_ex(C.byref(ccfg), C.byref(w2v), tensors, len(weights), self.device, C.byref(h))
+            elif cfg.family == "cpc":  # its paddings and recurrent network travel beside the (unchanged) s3enc_config
+                cpc = _lib.make_cpc_config(cfg)
+                rc = self._lib.s3enc_create_cpc(C.byref(ccfg), C.byref(cpc), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")

@@ -15,6 +15,7 @@ from .upstream.hf_wav2vec2.hubconf import *  # noqa: F401,F403
 from .upstream.baseline.hubconf import *  # noqa: F401,F403
 from .upstream.wav2vec.hubconf import *  # noqa: F401,F403
 from .upstream.vq_wav2vec.hubconf import *  # noqa: F401,F403
+from .upstream.cpc.hubconf import *  # noqa: F401,F403
 
 
 def options(only_registered_ckpt: bool = False):

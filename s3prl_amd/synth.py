@@ -22,6 +22,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     """Hot-path parameter names → shapes (reference naming)."""
     if cfg.family == "wav2vec":
         return _wav2vec_shapes(cfg)
+    if cfg.family == "cpc":
+        return _cpc_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -165,6 +167,25 @@ def _wav2vec_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     return s
 
 
+def _cpc_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """CPCModel (upstream/cpc/model.py:62-104,146-191) parameters, reference state_dict names."""
+    s: Dict[str, tuple] = {}
+    cin = 1
+    for i, (dim, k, _) in enumerate(cfg.conv_layers):
+        s[f"gEncoder.conv{i}.weight"] = (dim, cin, k)
+        s[f"gEncoder.conv{i}.bias"] = (dim,)
+        s[f"gEncoder.batchNorm{i}.weight"] = (1, dim, 1)
+        s[f"gEncoder.batchNorm{i}.bias"] = (1, dim, 1)
+        cin = dim
+    G, H = (4 if cfg.ar_mode == "LSTM" else 3), cfg.ar_hidden
+    for l in range(cfg.ar_layers):
+        s[f"gAR.baseNet.weight_ih_l{l}"] = (G * H, cfg.conv_dim if l == 0 else H)
+        s[f"gAR.baseNet.weight_hh_l{l}"] = (G * H, H)
+        s[f"gAR.baseNet.bias_ih_l{l}"] = (G * H,)
+        s[f"gAR.baseNet.bias_hh_l{l}"] = (G * H,)
+    return s
+
+
 def _multires_shapes(cfg: EncoderConfig, s: Dict[str, tuple]) -> Dict[str, tuple]:
     """multires-HuBERT (hubert_model.py:337-530): encoders.{i} / middle_encoder / decoders.{i} TransformerEncoders (only
     encoders.0 keeps its positional conv, :399-403,434-449) and the conv adapters between them."""
@@ -291,6 +312,20 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
         leaf = name.rsplit(".", 1)[-1]
         if name.endswith("relative_attention_bias.weight"):
             w = rng.standard_normal(shape) * 0.5
+        elif name.startswith("gEncoder.batchNorm"):  # ChannelNorm (1, C, 1): gains 1 + 0.1 N(0, 1), shifts 0.05 N(0, 1)
+            w = (1.0 if leaf == "weight" else 0.0) + (0.1 if leaf == "weight" else 0.05) * rng.standard_normal(shape)
+        elif name.startswith("gEncoder.conv") and leaf == "weight":  # (out, in, k): unit variance in front of the channel norm
+            w = rng.standard_normal(shape) * np.sqrt(1.0 / (shape[1] * shape[2]))
+        elif name.startswith("gAR.baseNet.weight"):
+            # input weights 2.5 / sqrt(fan_in) (6 / sqrt(fan_in) in layers 1.., whose inputs are hidden states of RMS 0.2-0.5),
+            # recurrent weights 1.5 / sqrt(H): the gate pre-activations have a standard deviation above 1, so sigmoid and tanh are
+            # exercised outside their linear range — torch's default U(-1/sqrt(H), 1/sqrt(H)) leaves the recurrent output below
+            # 0.2 in magnitude — while an fp32 evaluation stays within 1e-6 of a float64 one (stronger recurrent weights
+            # amplify every rounding error from step to step: at 3 / sqrt(H) the reference itself is 1.8e-6 away)
+            gain = 1.5 if "weight_hh" in name else (2.5 if name.endswith("_l0") else 6.0)
+            w = rng.standard_normal(shape) * (gain / np.sqrt(shape[1]))
+        elif name.startswith("gAR.baseNet.bias"):
+            w = 0.1 * rng.standard_normal(shape)
         elif name in ("vector_quantizer.embedding", "vector_quantizer.vars"):
             # codebooks at the scale of what they are compared with / replace (a trained k-means embedding lives where the
             # normalised projection does: unit variance; the reference's 0.01 * randn init leaves argmin decisions at rounding level)
@@ -440,8 +475,20 @@ def named_config(name: str) -> EncoderConfig:
         from .config import wav2vec_config
 
         return wav2vec_config(**w2v[name])
+    # modified CPC: the five convolutions at their real kernels, strides and paddings (receptive field 159 + 160 n, hop 160)
+    cpc = {
+        "tiny_cpc": dict(hidden=64, ar_mode="LSTM", ar_layers=2),
+        "tiny_cpc_gru": dict(hidden=64, ar_mode="GRU", ar_layers=1),
+        "tiny_cpc_lstm1": dict(hidden=64, ar_mode="LSTM", ar_layers=1),
+        # the shape the released 60k_epoch4 checkpoint is believed to carry (a checkpoint's own config decides at load time)
+        "cpc_base": dict(hidden=256, ar_mode="LSTM", ar_layers=2),
+    }
+    if name in cpc:
+        from .config import cpc_config
+
+        return cpc_config(**cpc[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
