@@ -469,7 +469,9 @@ def test_attention_with_every_score_far_below_zero(dtype):
 @pytest.mark.parametrize("shape", [(2, 499, 768, 16, 128), (1, 300, 1024, 16, 128), (3, 70, 128, 4, 16), (2, 257, 768, 16, 128)])
 def test_posconv(dtype, shape):
     """Positional conv + GELU + residual (posconv.hip: fp32 Toeplitz kernel and the 16-bit implicit-GEMM kernel) against
-    the oracle's pos_conv on the same (operand-rounded) inputs; Dg = 48 / 64 / 32, tiles with ragged frame counts."""
+    the oracle's pos_conv on the same (operand-rounded) inputs; Dg = 48 / 64 / 32, tiles with ragged frame counts.  The reference sees
+    the operands the kernel sees, so bf16 and fp16 are held to the fp32 band: products of 16-bit operands are exact in fp32 and only
+    the fp32 accumulation is left (tests/test_posconv_edges_gpu.py scores the same per frame at every tile edge)."""
     torch = _torch()
     from s3prl_amd import _lib
     from types import SimpleNamespace
@@ -495,7 +497,8 @@ def test_posconv(dtype, shape):
     got = out.cpu().numpy()
     assert np.isfinite(got).all()
     err = O.rel_err(got - x, ref - x)  # error of the conv branch itself, not hidden behind the residual
-    assert err < TOL[dtype], f"posconv {dtype}/{shape}: rel-err {err:.3e}"
+    tol = TOL["fp32x3"] if dtype == "fp32x3" else TOL["fp32"]
+    assert err < tol, f"posconv {dtype}/{shape}: rel-err {err:.3e}"
 
 
 @pytest.mark.parametrize("tile", [0, 1, 2, 4])
