@@ -50,7 +50,12 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * padding, each followed by a per-frame channel norm and ReLU, then a multi-layer LSTM or GRU over the whole padded
         * time axis — no frame mask.  Two states of (B, T, width): the encoder output and the recurrent output.
         * compute_dtype S3ENC_F32 only; built by s3enc_create_cpc. */
-       S3ENC_CPC = 6 };
+       S3ENC_CPC = 6,
+       /* APC / VQ-APC (upstream/apc/apc.py:101-169, audio.py:53-115, expert.py:18-59): a kaldi log-mel front end (hamming window, no
+        * deltas, CMVN over time) and 3 or 4 unidirectional GRU layers run on PACKED sequences: an utterance's recurrence stops at
+        * its own frame count and the rows behind it are zeros.  Three states of (B, T, hidden): the inputs of rnn_layers[1] and
+        * rnn_layers[2] and the last layer's output.  compute_dtype S3ENC_F32 only; built by s3enc_create_apc. */
+       S3ENC_APC = 7 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -190,6 +195,27 @@ typedef struct s3enc_cpc_config {
     int32_t keep_hidden;                            /* samplingType == "sequential" (refused) */
 } s3enc_cpc_config;
 
+/* S3ENC_APC only (apc/apc.py:26-71, apc/audio.py:53-115): the second configuration block of s3enc_create_apc.  s3enc_config
+ * carries the frame geometry as a one-layer "conv stack": n_conv = 1, conv_kernel[0] / conv_stride[0] = the analysis window / the
+ * frame shift in samples (400 / 160; both multiples of 4), conv_dim = embed_dim = hidden, encoder_layers = 2 (three states).
+ * Front end: torchaudio.compliance.kaldi.fbank(num_mel_bins, frame_length, frame_shift, window_type) at 16 kHz -> CMVN over time
+ * (unbiased std, eps 1e-10 added to the std) when `cmvn`.  Model: num_layers nn.GRU(batch_first) layers on packed sequences,
+ * layer i > 0 adding its own input to its output when `residual`.  Checkpoint tensors, reference state_dict names:
+ * rnn_layers.N.{weight_ih,weight_hh,bias_ih,bias_hh}_l0, every one of them required; vq_layers.* and postnet.* (VQ-APC's
+ * quantizer and the regression head) feed only the prediction the upstream discards: accepted and not uploaded.
+ * s3enc_create_apc refuses by name: every compute dtype but fp32, num_layers below 3 (the reference's hooks index rnn_layers[2])
+ * or above 4, hidden not a multiple of 64 or above 512, window / shift that are not multiples of 4 samples. */
+typedef struct s3enc_apc_config {
+    int32_t num_mel_bins;                           /* feat_dim: 80 */
+    float frame_length_ms;                          /* 25 */
+    float frame_shift_ms;                           /* 10 */
+    int32_t window;                                 /* 0 povey, 1 hamming (the reference's WINDOW_TYPE) */
+    int32_t cmvn;                                   /* apply_cmvn */
+    int32_t hidden;                                 /* hidden_size */
+    int32_t num_layers;                             /* 3 or 4 */
+    int32_t residual;                               /* rnn_residual */
+} s3enc_apc_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -219,6 +245,13 @@ int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, co
  * refuses them), s3enc_valid_frames follows the wav2vec convention (the frames the utterance's own samples reach),
  * s3enc_num_states is 2 for S3ENC_SEL_HIDDEN (the other selections are refused), out_dtype must be S3ENC_F32. */
 int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
+                     int32_t device, s3enc_handle* out);
+/* The S3ENC_APC family: s3enc_config beside its own block (s3enc_create, s3enc_create_ex and s3enc_create_cpc refuse that family
+ * by name).  Replaces UpstreamExpert.__init__ of upstream/apc/expert.py:19-42.  On the handle: s3enc_num_frames counts whole
+ * analysis windows (snip_edges: 400 samples give one frame, fewer give 0 and the forward refuses such an utterance),
+ * s3enc_valid_frames is the utterance's own frame count, s3enc_num_states is 3 for S3ENC_SEL_HIDDEN (the other selections are
+ * refused), out_dtype must be S3ENC_F32.  Every state row behind an utterance's frame count is exactly 0. */
+int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
@@ -432,6 +465,11 @@ int s3enc_debug_clock_sample(uint64_t* out3_device, void* stream);
  *   "reserve_cus":  CUs the persistent one-workgroup-per-CU GEMM of the 16-bit modes leaves out of its grid (default 0; a measurement
  *                   knob — leaving CUs to a collective's channel kernels costs more than sharing them: profiles/r05_cu_contention.md;
  *                   tests/test_col_edges_gpu.py sets 128 to make the persistent grid walk several tiles per workgroup on small shapes);
+ *   "rnn_split":    the length-aware recurrence (s3enc_op_rnn_len, S3ENC_APC handles): 0 = one launch per layer runs all steps, one
+ *                   workgroup per utterance; 1 / 2 / 4 / 8 = the step-split form: one launch per time step on a (S, B) grid, workgroup
+ *                   (s, b) owning hidden / S units of utterance b (hidden / S a multiple of 64, S * B <= 256; refused otherwise) —
+ *                   the same bits for every S; -1 (default) = S = 8 for a GRU at hidden = 512 with 8 B <= 256, where it was measured
+ *                   to win (27.0 against 88.8 ms per 32 x 10 s apc_360hr forward, profiles/apc_360hr_fp32.md), one launch elsewhere;
  *   "conv_f22":     S3ENC_F32: 1 (default) = conv layers 1.. with kernel 3 and stride 2 (conv1-4 of every extractor) run in the
  *                   two-output form (convf22.hip: 5 block products per pair of outputs instead of 6, fp32 operands and accumulation,
  *                   a different association — results differ in the last bits), 0 = the implicit GEMM;
@@ -540,6 +578,15 @@ int s3enc_op_channelnorm_relu(const float* x, const float* gamma, const float* b
 int s3enc_op_rnn(int32_t cell, const float* pre, const float* w_hh_host, const float* b_hn, int32_t B, int32_t T, int32_t H,
                  int64_t ld_pre, float* out, int64_t ldo, void* stream);
 
+/* s3enc_op_rnn with packed-sequence semantics (pack_padded_sequence / pad_packed_sequence): utterance b runs len_host[b] steps
+ * (HOST int32 (B), each in 1..T) and its rows [len, T) are written as zeros.  res: device fp32 or NULL, row (b, t) at
+ * res + (b * T + t) * ld_res, H values added to the row written (the carried state stays the un-summed h_t).  out must be
+ * 16-byte aligned and ldo a multiple of 4.  With every length equal to T and no res the result is bit-identical to
+ * s3enc_op_rnn.  Synchronises. */
+int s3enc_op_rnn_len(int32_t cell, const float* pre, const float* w_hh_host, const float* b_hn, const int32_t* len_host,
+                     const float* res, int64_t ld_res, int32_t B, int32_t T, int32_t H, int64_t ld_pre, float* out, int64_t ldo,
+                     void* stream);
+
 /* Convolutional position embedding + residual: out = x + GELU(SamePad(Conv1d(D, D, K, padding=K/2, groups=G)(x)) + bias)
  * (make_conv_pos / SamePad, wav2vec2_model.py:2937-2953,1797-1808).  x, out: device fp32 (B, T, D); w_host: HOST fp32
  * (D, D/G, K), the nn.Conv1d weight with weight_norm already folded; packed and uploaded inside.  Synchronises. */
@@ -580,6 +627,10 @@ int s3enc_fbank_num_frames(const s3enc_fbank_config* cfg, int64_t n_samples, int
  * zero beyond each utterance's frames (pad_sequence); T_max >= the longest utterance's frame count. */
 int s3enc_fbank_forward(const s3enc_fbank_config* cfg, const float* const* wavs, const int64_t* lengths, int32_t B,
                         float* out, int64_t T_max, int32_t device, void* stream);
+/* The same with kaldi's window_type: 0 povey (s3enc_fbank_forward, bit for bit), 1 hamming
+ * 0.54 - 0.46 cos(2 pi i / (N - 1)) (APC's front end, apc/audio.py:22,82-88).  s3enc_fbank_config is unchanged. */
+int s3enc_fbank_forward_ex(const s3enc_fbank_config* cfg, int32_t window, const float* const* wavs, const int64_t* lengths,
+                           int32_t B, float* out, int64_t T_max, int32_t device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,9 +19,10 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
+APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
 VQ_TYPE = {"none": 0, "gumbel": 1, "kmeans": 2}  # s3enc_config.vq_type
 SEL_HIDDEN, SEL_LAYER_OUT, SEL_FFN_OUT = 0, 1, 2
 SELECTIONS = {None: SEL_HIDDEN, "hidden_states": SEL_HIDDEN, "fairseq_layers": SEL_LAYER_OUT,
@@ -67,6 +68,14 @@ class S3CpcConfig(C.Structure):
     ]
 
 
+class S3ApcConfig(C.Structure):
+    """s3enc_apc_config: the front-end / GRU block of an APC handle (s3enc_create_apc)."""
+    _fields_ = [
+        ("num_mel_bins", C.c_int32), ("frame_length_ms", C.c_float), ("frame_shift_ms", C.c_float), ("window", C.c_int32),
+        ("cmvn", C.c_int32), ("hidden", C.c_int32), ("num_layers", C.c_int32), ("residual", C.c_int32),
+    ]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -95,6 +104,7 @@ _PROTOS = {
     "s3enc_create": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_ex": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Wav2vecConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_cpc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3CpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    "s3enc_create_apc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3ApcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -139,6 +149,7 @@ _PROTOS = {
                                      _I32, _I32, _VP]),
     "s3enc_op_channelnorm_relu": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_rnn": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I64, _VP, _I64, _VP]),
+    "s3enc_op_rnn_len": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I64, _VP, _I64, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
@@ -147,6 +158,7 @@ _PROTOS = {
     "s3enc_weighted_sum_backward": (C.c_int, [_VP, _I64, _I32, _I32, _I64, _I32, _VP, _VP, _VP, _VP]),
     "s3enc_fbank_num_frames": (C.c_int, [C.POINTER(S3FbankConfig), _I64, C.POINTER(_I32)]),
     "s3enc_fbank_forward": (C.c_int, [C.POINTER(S3FbankConfig), _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
+    "s3enc_fbank_forward_ex": (C.c_int, [C.POINTER(S3FbankConfig), _I32, _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
 }
 
 _lib = None
@@ -277,4 +289,17 @@ def make_cpc_config(cfg) -> S3CpcConfig:
     c.ar_mode = CPC_AR.get(cfg.ar_mode, -1)
     c.ar_layers, c.ar_hidden = int(cfg.ar_layers), int(cfg.ar_hidden)
     c.reverse, c.keep_hidden = int(cfg.cpc_reverse), int(cfg.cpc_keep_hidden)
+    return c
+
+
+def make_apc_config(cfg) -> S3ApcConfig:
+    """The second configuration block of a ``family="apc"`` EncoderConfig (``s3enc_create_apc``)."""
+    if cfg.family != "apc":
+        raise S3EncError("make_apc_config needs an apc configuration")
+    c = S3ApcConfig()
+    c.num_mel_bins = int(cfg.apc_feat_dim)
+    c.frame_length_ms, c.frame_shift_ms = float(cfg.apc_frame_length), float(cfg.apc_frame_shift)
+    c.window = APC_WINDOW.get(cfg.apc_window, -1)
+    c.cmvn = int(cfg.apc_cmvn)
+    c.hidden, c.num_layers, c.residual = int(cfg.conv_dim), int(cfg.apc_layers), int(cfg.apc_residual)
     return c

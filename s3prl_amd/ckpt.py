@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, config_from_cpc, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, config_from_apc, config_from_cpc, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -58,6 +58,20 @@ def load_cpc_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]
     return cfg, _hot_path_weights(ckpt, cfg, state["weights"])
 
 
+def load_apc_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"config": {"data": {"audio": ...}, "model": {"paras": ...}}, "model": state_dict}`` (upstream/apc/expert.py:22-27).
+    Every GRU tensor is required; ``postnet.*`` and VQ-APC's ``vq_layers.*`` feed only the prediction the upstream discards and are
+    left in the file."""
+    import torch
+
+    state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    for key in ("config", "model"):
+        if key not in state:
+            raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: {key} is missing")
+    cfg = config_from_apc(state["config"])
+    return cfg, _hot_path_weights(ckpt, cfg, state["model"])
+
+
 def _hot_path_weights(ckpt: str, cfg: EncoderConfig, sd) -> Dict[str, np.ndarray]:
     weights = {}
     for name, shape in param_shapes(cfg).items():
@@ -76,6 +90,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
 
     if family == "cpc":
         return load_cpc_checkpoint(ckpt)
+    if family == "apc":
+        return load_apc_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -123,6 +139,14 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
     import torch
 
     sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.items()}
+    if cfg.family == "apc":  # upstream/apc/expert.py:22-27
+        audio = dict(feat_type=cfg.apc_feat_type, feat_dim=cfg.apc_feat_dim, frame_length=cfg.apc_frame_length,
+                     frame_shift=cfg.apc_frame_shift, decode_wav=False, cmvn=cfg.apc_cmvn)
+        paras = dict(hidden_size=cfg.conv_dim, num_layers=cfg.apc_layers, dropout=0.0, residual=cfg.apc_residual)
+        if cfg.apc_vq is not None:
+            paras["vq"] = dict(cfg.apc_vq)
+        torch.save({"config": {"data": {"audio": audio}, "model": {"paras": paras}}, "model": sd}, path)
+        return
     if cfg.family == "cpc":  # upstream/cpc/expert.py:29-36
         config = dict(hiddenEncoder=cfg.conv_dim, hiddenGar=cfg.ar_hidden, arMode=cfg.ar_mode, nLevelsGRU=cfg.ar_layers,
                       normMode=cfg.norm_mode, encoder_type="cpc", cpc_mode="reverse" if cfg.cpc_reverse else None,

@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -132,6 +132,19 @@ class EncoderConfig:
     ar_hidden: int = 256           # hiddenGar
     cpc_reverse: bool = False      # cpc_mode == "reverse" (refused)
     cpc_keep_hidden: bool = False  # samplingType == "sequential" (refused)
+    # APC / VQ-APC (family "apc", upstream/apc/apc.py:26-169, audio.py:53-115): a kaldi log-mel front end and ``apc_layers`` GRU
+    # layers of width ``conv_dim`` on packed sequences.  ``conv_layers`` = [(hidden, window, shift)] in samples carries the frame
+    # geometry; ``encoder_layers`` = 2 and ``encoder_embed_dim`` = hidden, so the states are 3 x (B, T, hidden): the inputs of
+    # rnn_layers[1] and rnn_layers[2] and the last layer's output
+    apc_feat_type: str = "fbank"      # audio.feat_type: only the Mel spectrogram exists in the reference
+    apc_feat_dim: int = 80            # audio.feat_dim = num_mel_bins
+    apc_frame_length: float = 25.0    # ms
+    apc_frame_shift: float = 10.0     # ms
+    apc_window: str = "hamming"       # the reference's WINDOW_TYPE constant
+    apc_cmvn: bool = True             # audio.cmvn
+    apc_layers: int = 3               # paras.num_layers
+    apc_residual: bool = True         # paras.residual
+    apc_vq: Dict | None = None        # paras.vq (VQ-APC): feeds only the discarded prediction; kept for the checkpoint round trip
 
     # ---- derived -------------------------------------------------------------------------
     @property
@@ -184,7 +197,7 @@ class EncoderConfig:
         T = self.num_frames(n_max)
         if T <= 0:
             return 0
-        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask
+        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -285,6 +298,8 @@ class EncoderConfig:
             return self._validate_wav2vec()
         if self.family == "cpc":
             return self._validate_cpc()
+        if self.family == "apc":
+            return self._validate_apc()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -362,6 +377,30 @@ class EncoderConfig:
             raise ValueError(f"cpc nLevelsGRU must be 1..4 recurrent layers, got {self.ar_layers}")
         if self.encoder_layers != 1 or self.encoder_embed_dim != self.conv_dim:
             raise ValueError("cpc: encoder_layers / encoder_embed_dim must be 1 / the conv width (cpc_config sets them)")
+
+    def _validate_apc(self) -> None:
+        """What the HIP path builds of the APC configuration; everything else is refused by name (s3enc_create_apc repeats it)."""
+        if self.apc_feat_type != "fbank":
+            raise ValueError(f"apc feat_type={self.apc_feat_type!r} is not built: only 'fbank' (the reference implements nothing else)")
+        if self.apc_window not in ("hamming", "povey"):
+            raise ValueError(f"apc window_type={self.apc_window!r} is not built: only 'hamming' and 'povey'")
+        if not 3 <= self.apc_layers <= 4:
+            raise ValueError(f"apc num_layers must be 3 or 4, got {self.apc_layers} (the reference's hooks read rnn_layers[1] and "
+                             "rnn_layers[2]: fewer layers raise IndexError there; more than 4 are not built)")
+        if len(self.conv_layers) != 1:
+            raise ValueError("apc: conv_layers carries the frame geometry as one (hidden, window, shift) entry (apc_config sets it)")
+        H, size, shift = self.conv_layers[0]
+        if H % 64 or not 64 <= H <= 512:
+            raise ValueError(f"apc hidden_size must be a multiple of 64, at most 512 (the recurrent kernel's limit), got {H}")
+        if (size, shift) != (int(16000 * self.apc_frame_length * 0.001), int(16000 * self.apc_frame_shift * 0.001)):
+            raise ValueError("apc: conv_layers does not match frame_length / frame_shift (apc_config sets it)")
+        if size < 4 or shift < 4 or size % 4 or shift % 4:
+            raise ValueError(f"apc frame_length / frame_shift of {size} / {shift} samples are not built: both must be a multiple of 4 "
+                             "samples (the front end's GEMM reads 16-byte vectors)")
+        if self.apc_feat_dim % 4 or not 4 <= self.apc_feat_dim <= 256:
+            raise ValueError(f"apc feat_dim must be a multiple of 4, at most 256, got {self.apc_feat_dim}")
+        if self.encoder_layers != 2 or self.encoder_embed_dim != H:
+            raise ValueError("apc: encoder_layers / encoder_embed_dim must be 2 / hidden_size (apc_config sets them)")
 
     def to_dict(self) -> Dict:
         return asdict(self)
@@ -465,6 +504,37 @@ def config_from_cpc(config: Dict) -> EncoderConfig:
         raise ValueError(f"cpc encoder_type={a['encoder_type']!r} is not built: only 'cpc' (the convolutional encoder)")
     return cpc_config(a["hiddenEncoder"], a["arMode"], a["nLevelsGRU"], a["hiddenGar"], norm_mode=str(a["normMode"]),
                       cpc_reverse=a["cpc_mode"] == "reverse", cpc_keep_hidden=a["samplingType"] == "sequential")
+
+
+def apc_config(hidden: int = 512, num_layers: int = 3, residual: bool = True, feat_dim: int = 80, frame_length: float = 25.0,
+               frame_shift: float = 10.0, cmvn: bool = True, vq: Dict | None = None, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "apc" (apc/apc.py:27-71, apc/audio.py:107-115)."""
+    H = int(hidden)
+    size, shift = int(16000 * float(frame_length) * 0.001), int(16000 * float(frame_shift) * 0.001)
+    cfg = EncoderConfig(family="apc", conv_layers=[(H, size, shift)], encoder_layers=2, encoder_embed_dim=H,
+                        apc_feat_dim=int(feat_dim), apc_frame_length=float(frame_length), apc_frame_shift=float(frame_shift),
+                        apc_cmvn=bool(cmvn), apc_layers=int(num_layers), apc_residual=bool(residual),
+                        apc_vq=None if vq is None else dict(vq), **flags)
+    cfg.validate()
+    return cfg
+
+
+def config_from_apc(config: Dict) -> EncoderConfig:
+    """The checkpoint's ``config``: ``data.audio`` as ``create_transform`` reads it (apc/audio.py:107-115: feat_type, feat_dim,
+    decode_wav and cmvn are popped, the rest goes to ``kaldi.fbank``) and ``model.paras`` as ``APC(feat_dim, **paras)`` does."""
+    audio = dict(config["data"]["audio"])
+    feat_type, feat_dim = audio.pop("feat_type"), audio.pop("feat_dim")
+    audio.pop("decode_wav", None)  # how a FILE is read; the upstream is handed waveforms
+    cmvn = audio.pop("cmvn", True)
+    frame_length, frame_shift = audio.pop("frame_length", 25.0), audio.pop("frame_shift", 10.0)
+    if audio:
+        raise ValueError(f"apc audio options {sorted(audio)} are not built: only frame_length / frame_shift reach kaldi.fbank here")
+    paras = dict(config["model"]["paras"])
+    for key in ("hidden_size", "num_layers", "residual"):
+        if key not in paras:
+            raise ValueError(f"apc checkpoint: model.paras.{key} is missing")
+    return apc_config(paras["hidden_size"], paras["num_layers"], paras["residual"], feat_dim, frame_length, frame_shift, cmvn,
+                      paras.get("vq"), apc_feat_type=str(feat_type))
 
 
 def config_from_multires(model_cfg: Dict, task_cfg: Dict | None = None) -> EncoderConfig:

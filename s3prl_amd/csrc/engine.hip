@@ -21,8 +21,9 @@ int valid_frames(const s3enc_config& c, long length, long n_max) {
     const long T = conv_len(c, n_max, c.n_conv);
     if (T <= 0) return 0;
     long v;
-    if (c.family == S3ENC_WAV2VEC2 || c.family == S3ENC_DISTILLER || c.family == S3ENC_WAV2VEC) {
-        // wav2vec2_model.py:2652-2669; distiller/model.py:271-285; wav2vec has no mask: the frames an utterance's own samples reach
+    if (c.family == S3ENC_WAV2VEC2 || c.family == S3ENC_DISTILLER || c.family == S3ENC_WAV2VEC || c.family == S3ENC_APC) {
+        // wav2vec2_model.py:2652-2669; distiller/model.py:271-285; wav2vec has no mask: the frames an utterance's own samples reach;
+        // APC: the utterance's own whole analysis windows (its packed length)
         v = conv_len(c, length, c.n_conv);
     } else {
         const long chunk = n_max / T;  // hubert_model.py:454-464
@@ -92,9 +93,10 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 6) return fail("config: unknown family");
+    if (c.family < 0 || c.family > 7) return fail("config: unknown family");
     if (c.family == S3ENC_WAV2VEC) return 0;  // s3enc_create_ex: wav2vec_check_config on both configuration blocks
     if (c.family == S3ENC_CPC) return 0;      // s3enc_create_cpc: cpc_check_config on both configuration blocks
+    if (c.family == S3ENC_APC) return 0;      // s3enc_create_apc: apc_check_config on both configuration blocks
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
         const int k = c.mr_kernel;
@@ -179,7 +181,7 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
+                       const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
 
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out) {
@@ -187,24 +189,40 @@ int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, co
         if (out) *out = nullptr;
         return fail("s3enc_create: the modified-CPC family needs its padding / recurrent-network block: use s3enc_create_cpc");
     }
-    return create_impl(cfg, w2v, nullptr, tensors, n_tensors, device, out);
+    if (cfg && cfg->family == S3ENC_APC) {
+        if (out) *out = nullptr;
+        return fail("s3enc_create: the APC family needs its front-end / GRU block: use s3enc_create_apc");
+    }
+    return create_impl(cfg, w2v, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out) {
     if (!cfg || !cpc || !tensors || !out) return fail("s3enc_create_cpc: null argument");
     *out = nullptr;
+    if (cfg->family == S3ENC_APC) return fail("s3enc_create_cpc: the APC family needs its front-end / GRU block: use s3enc_create_apc");
     if (cfg->family != S3ENC_CPC) return fail("s3enc_create_cpc: the cpc block belongs to family S3ENC_CPC only");
-    return create_impl(cfg, nullptr, cpc, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, cpc, nullptr, tensors, n_tensors, device, out);
+}
+
+int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors,
+                     int32_t device, s3enc_handle* out) {
+    if (!cfg || !apc || !tensors || !out) return fail("s3enc_create_apc: null argument");
+    *out = nullptr;
+    if (cfg->family != S3ENC_APC) return fail("s3enc_create_apc: the apc block belongs to family S3ENC_APC only");
+    return create_impl(cfg, nullptr, nullptr, apc, tensors, n_tensors, device, out);
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
+                       const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
     if (cfg->family == S3ENC_CPC) {
         if (cpc_check_config(*cfg, *cpc)) return 1;
+    }
+    if (cfg->family == S3ENC_APC) {
+        if (apc_check_config(*cfg, *apc)) return 1;
     }
     if (cfg->family == S3ENC_WAV2VEC) {
         if (!w2v) return fail("s3enc_create: the wav2vec family needs its aggregator / quantizer block: use s3enc_create_ex");
@@ -245,6 +263,14 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
     if (cfg->family == S3ENC_CPC) {
         e->cpc_cfg = *cpc;
         if (cpc_create(e, tensors, n_tensors)) {
+            delete e;
+            return 1;
+        }
+        return finish_create(e, out);
+    }
+    if (cfg->family == S3ENC_APC) {
+        e->apc_cfg = *apc;
+        if (apc_create(e, tensors, n_tensors)) {
             delete e;
             return 1;
         }
@@ -1026,6 +1052,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
                  const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     if (e->cfg.family == S3ENC_WAV2VEC) return wav2vec_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     if (e->cfg.family == S3ENC_CPC) return cpc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+    if (e->cfg.family == S3ENC_APC) return apc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
     const int dt = e->dtype, es = e->es;
@@ -1799,6 +1826,8 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
         return fail("s3enc_num_states: feature_selection is not defined for a Conformer encoder");
     if (h->cfg.family == S3ENC_CPC && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: feature_selection is not defined for modified CPC (one hidden_states list of 2 states)");
+    if (h->cfg.family == S3ENC_APC && selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_num_states: feature_selection is not defined for APC (one hidden_states list of 3 states)");
     *n = num_states(h->cfg, selection);
     return 0;
 }

@@ -377,6 +377,12 @@ struct CpcW {
     std::vector<DevBuf> w_ih, b_pre, w_hh, b_hn;
 };
 
+// APC / VQ-APC (apc.hip): per GRU layer weight_ih (3 H, I) as the input projection's GEMM operand (I = the mel bins for layer 0),
+// its bias b_ih + the r and z parts of b_hh, weight_hh in rnn.hip's k-quad-major layout, and b_hn
+struct ApcW {
+    std::vector<DevBuf> w_ih, b_pre, w_hh, b_hn;
+};
+
 struct ProfRec {
     int kind;
     hipEvent_t a, b;
@@ -435,6 +441,8 @@ struct s3enc_encoder {
     s3enc_wav2vec_config w2v_cfg = {};  // ... and its second configuration block (s3enc_create_ex)
     std::unique_ptr<CpcW> cpc;          // S3ENC_CPC
     s3enc_cpc_config cpc_cfg = {};      // ... and its second configuration block (s3enc_create_cpc)
+    std::unique_ptr<ApcW> apc;          // S3ENC_APC
+    s3enc_apc_config apc_cfg = {};      // ... and its second configuration block (s3enc_create_apc)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -654,6 +662,12 @@ long cpc_conv_len(const s3enc_config& c, const s3enc_cpc_config& x, long n, int 
 int cpc_check_config(const s3enc_config& c, const s3enc_cpc_config& x);
 int cpc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
 int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+
+// apc.hip: the S3ENC_APC family (kaldi log-mel front end + GRU layers on packed sequences)
+int apc_check_config(const s3enc_config& c, const s3enc_apc_config& x);
+int apc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
+int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
 }  // namespace s3e

@@ -2,7 +2,7 @@
 //   torchaudio.compliance.kaldi.fbank(80 mel bins, 25 ms / 10 ms, log) -> 2 x ComputeDeltas(win 5) -> CMVN over time
 //   (upstream/baseline/extracter.py:32-90, baseline/fbank.yaml).
 //
-// Framing, DC removal, pre-emphasis, the povey window and the zero-padded 512-point real DFT are all linear in the
+// Framing, DC removal, pre-emphasis, the window (povey; hamming for APC's front end, FbankParams::window) and the zero-padded 512-point real DFT are all linear in the
 // 400 samples of a frame, so they are folded (in fp64, once per configuration) into ONE (2*257) x 400 matrix; the
 // spectrum of every frame is then a GEMM whose A rows OVERLAP in the raw waveform (row t starts at sample 160 t:
 // lda = 160 < K = 400) — the same implicit-GEMM addressing as the strided convs, served by gemm.hip's exact-fp32 MFMA
@@ -100,7 +100,7 @@ std::mutex g_mu;
 std::map<std::vector<long>, FbankPlan> g_plans;
 std::map<std::pair<int, uintptr_t>, FbankScratch> g_scratch;
 
-hipError_t build_plan(FbankPlan& pl, int nmel, int size, int shift, double preemph, int sample_rate) {
+hipError_t build_plan(FbankPlan& pl, int nmel, int size, int shift, double preemph, int sample_rate, int window) {
     pl.size = size;
     pl.shift = shift;
     pl.padded = 1;
@@ -113,7 +113,8 @@ hipError_t build_plan(FbankPlan& pl, int nmel, int size, int shift, double preem
     for (int i = 0; i < N; ++i)
         for (int j = 0; j < N; ++j) tmp[(size_t)i * N + j] = (i == j ? 1.0 : 0.0) - 1.0 / N;  // C
     for (int i = 0; i < N; ++i) {
-        const double w = std::pow(0.5 - 0.5 * std::cos(2.0 * M_PI * i / (N - 1)), 0.85);  // povey
+        const double w = window == 1 ? 0.54 - 0.46 * std::cos(2.0 * M_PI * i / (N - 1))             // hamming
+                                     : std::pow(0.5 - 0.5 * std::cos(2.0 * M_PI * i / (N - 1)), 0.85);  // povey
         const int ip = i == 0 ? 0 : i - 1;
         for (int j = 0; j < N; ++j) D[(size_t)i * N + j] = w * (tmp[(size_t)i * N + j] - preemph * tmp[(size_t)ip * N + j]);
     }
@@ -170,16 +171,17 @@ hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* o
     const int size = (int)(c.sample_rate * c.frame_length_ms * 0.001), shift = (int)(c.sample_rate * c.frame_shift_ms * 0.001);
     const long T = fbank_num_frames(n, c);
     if (T <= 0) return hipSuccess;
-    if (size <= 0 || shift <= 0 || (size & 3) || (shift & 3) || c.num_mel_bins <= 0 || c.delta_order < 0 || c.delta_order > 2)
+    if (size <= 0 || shift <= 0 || (size & 3) || (shift & 3) || c.num_mel_bins <= 0 || c.delta_order < 0 || c.delta_order > 2 ||
+        c.window < 0 || c.window > 1)
         return hipErrorInvalidValue;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lock(g_mu);
-    const std::vector<long> key{dev, c.num_mel_bins, size, shift, (long)std::lround(c.preemph * 1e6), c.sample_rate};
+    const std::vector<long> key{dev, c.num_mel_bins, size, shift, (long)std::lround(c.preemph * 1e6), c.sample_rate, c.window};
     FbankPlan& pl = g_plans[key];
     if (!pl.dft) {
-        e = build_plan(pl, c.num_mel_bins, size, shift, c.preemph, c.sample_rate);
+        e = build_plan(pl, c.num_mel_bins, size, shift, c.preemph, c.sample_rate, c.window);
         if (e != hipSuccess) return e;
     }
     const int N2 = 2 * pl.nbin;

@@ -84,6 +84,10 @@ struct Tuning {
                            // (tools/two_stream_probe.py, profiles/r06c_concurrent_forwards.md; no kernel or pair of kernels reproduces it in
                            // isolation, two streams never do).  Price: sub-batches that under-fill the chip no longer overlap (four
                            // 8-utterance forwards: 8.5 -> 12.1 ms; the same 32 utterances as ONE batch: 6.8 ms).  0 = forwards may overlap
+    int rnn_split = -1;    // rnn.hip, the length-aware recurrence: 0 = one launch runs all steps (one workgroup per utterance), 1 / 2 / 4 / 8 =
+                           // the step-split form with that many workgroups per utterance, one launch per step (bit-identical);
+                           // -1 (default) = the step form with S = 8 where it was measured to win (a GRU at H = 512 with
+                           // 8 B <= 256: 27.0 against 88.8 ms per apc_360hr forward, profiles/apc_360hr_fp32.md), else one launch
     int comm_self_p2p = 0; // comm.hip, S3ENC_EXCHANGE_DIRECT: 1 = a rank's OWN block also travels as an ncclSend-to-self / ncclRecv-from-self
                            // pair inside the state's group instead of a device copy — on a one-GPU box this is the only way the
                            // all-pairs code (symbols, counts, datatype, group bracketing, stream order behind the layer events)
@@ -440,6 +444,30 @@ struct RnnParams {
 // host: weight_hh (gates * H, H) -> [H / 4][gates * H][4]: thread r of a step reads 16 consecutive bytes next to thread r + 1's
 void pack_rnn_whh(const float* w, int gates, int H, std::vector<float>& out);
 hipError_t launch_rnn(const RnnParams& p, hipStream_t s);
+// The same recurrence with packed-sequence semantics (pack_padded_sequence / pad_packed_sequence; APC: upstream/apc/apc.py:118-139):
+// utterance b stops at len[b] steps and its rows [len[b], T) are written as zeros.  For t < len[b] the row written is h_t (+ res[b, t]
+// when `res` is given: the layer's residual operand); the carried state is the un-summed h_t.  A struct of its own, so that the
+// kernels behind launch_rnn keep their argument block.
+struct RnnLenParams : RnnParams {
+    const int* len;      // device [B], each in 1..T
+    const float* res;    // row (b, t) at res + (b * T + t) * ld_res, H values; or null
+    long ld_res;
+};
+// out must be 16-byte aligned and ldo a multiple of 4 (the zero tail is written with 16-byte stores)
+hipError_t launch_rnn_len(const RnnLenParams& p, hipStream_t s);
+// The step-split form of launch_rnn_len: one launch per time step on a (S, B) grid, workgroup (s, b) owning H / S hidden units of
+// utterance b with all their gate rows; bit-identical to launch_rnn_len for every S.  S a power of two, H / S a multiple of 64,
+// S * B <= 256 (rnn_split_ok).
+struct RnnStepParams : RnnLenParams {
+    int S;               // workgroups per utterance
+    int max_len;         // the largest len[b] (host): the number of launches
+    int t;               // (set per launch)
+    float* hbuf;         // device (2, B, H) ping-pong of h; need not be initialised
+    float* cbuf;         // LSTM: device (B, H); GRU: null
+};
+bool rnn_split_ok(int H, int B, int S);
+int rnn_split_pick(int cell, int H, int B);  // tuning().rnn_split, or its default rule: 0 = launch_rnn_len, S = launch_rnn_step
+hipError_t launch_rnn_step(const RnnStepParams& p, hipStream_t s);
 
 // ---- featurizer.hip (weighted sum over layers, the consumer of hidden_states) ---------------------
 #define S3_WS_MAX_LAYERS 32
@@ -461,6 +489,7 @@ struct FbankParams {
     int delta_order = 2, delta_win = 5;
     int use_cmvn = 1;
     float cmvn_eps = 1e-10f;
+    int window = 0;  // 0 povey (hann ** 0.85), 1 hamming (0.54 - 0.46 cos(2 pi i / (N - 1))): kaldi's window_type
 };
 long fbank_num_frames(long n_samples, const FbankParams& c);
 // one utterance: wav (device) -> out (device, frames x ldo), columns [0, num_mel_bins * (delta_order + 1))

@@ -26,6 +26,7 @@ int tuning_set(Tuning& t, const char* key, int value, const char** err) {
         {"ln_rows", &Tuning::ln_rows, 1, 2},                 {"ln1_fold", &Tuning::ln1_fold, 0, 1},
         {"ln_preload", &Tuning::ln_preload, 0, 1},           {"forward_chain", &Tuning::forward_chain, 0, 1},
         {"conv0_fast", &Tuning::conv0_fast, 0, 1},           {"conv_f22", &Tuning::conv_f22, 0, 1},
+        {"rnn_split", &Tuning::rnn_split, -1, 8},
     };
     static thread_local char msg[160];
     if (!key) {
@@ -329,6 +330,61 @@ int s3enc_op_rnn(int32_t cell, const float* pre, const float* w_hh_host, const f
     return 0;
 }
 
+int s3enc_op_rnn_len(int32_t cell, const float* pre, const float* w_hh_host, const float* b_hn, const int32_t* len_host,
+                     const float* res, int64_t ld_res, int32_t B, int32_t T, int32_t H, int64_t ld_pre, float* out, int64_t ldo,
+                     void* stream) {
+    if (!pre || !w_hh_host || !out || !len_host) return fail("s3enc_op_rnn_len: null argument");
+    if (cell < 0 || cell > 1) return fail("s3enc_op_rnn_len: cell must be 0 (LSTM) or 1 (GRU)");
+    if ((cell == 1) != (b_hn != nullptr)) return fail("s3enc_op_rnn_len: b_hn belongs to the GRU cell (NULL for LSTM)");
+    if (B <= 0 || T <= 0) return fail("s3enc_op_rnn_len: bad shape");
+    if (H < 64 || H % 64 || H > RNN_H_MAX) return fail("s3enc_op_rnn_len: H must be a multiple of 64, at most 512");
+    const int G = cell == 0 ? 4 : 3;
+    if (ld_pre < (int64_t)G * H || ldo < H) return fail("s3enc_op_rnn_len: ld_pre / ldo smaller than the row");
+    if (res && ld_res < H) return fail("s3enc_op_rnn_len: ld_res smaller than the row");
+    if ((((uintptr_t)out) & 15) || (ldo & 3)) return fail("s3enc_op_rnn_len: out must be 16-byte aligned and ldo a multiple of 4");
+    for (int b = 0; b < B; ++b)
+        if (len_host[b] < 1 || len_host[b] > T) return fail("s3enc_op_rnn_len: every length must be in 1..T");
+    std::vector<float> packed;
+    pack_rnn_whh(w_hh_host, G, H, packed);
+    DevBuf dw, dl;
+    HIP_TRY(upload_f32(dw, packed));
+    HIP_TRY(dl.ensure((size_t)B * sizeof(int)));
+    HIP_TRY(hipMemcpy(dl.p, len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    RnnLenParams p{};
+    p.cell = cell;
+    p.pre = pre;
+    p.w = (const float*)dw.p;
+    p.b_hn = b_hn;
+    p.B = B;
+    p.T = T;
+    p.H = H;
+    p.ld_pre = ld_pre;
+    p.out = out;
+    p.ldo = ldo;
+    p.len = (const int*)dl.p;
+    p.res = res;
+    p.ld_res = ld_res;
+    const int S = rnn_split_pick(cell, H, B);
+    if (S) {  // the step-split form (tuning key rnn_split, or its default rule)
+        if (!rnn_split_ok(H, B, S)) return fail("s3enc_op_rnn_len: rnn_split must be a power of two with H / S a multiple of 64 and S * B <= 256");
+        DevBuf dh, dc;
+        HIP_TRY(dh.ensure((size_t)2 * B * H * sizeof(float)));
+        if (cell == 0) HIP_TRY(dc.ensure((size_t)B * H * sizeof(float)));
+        RnnStepParams q{};
+        static_cast<RnnLenParams&>(q) = p;
+        q.S = S;
+        q.max_len = *std::max_element(len_host, len_host + B);
+        q.hbuf = (float*)dh.p;
+        q.cbuf = (float*)dc.p;
+        HIP_TRY(launch_rnn_step(q, (hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        return 0;
+    }
+    HIP_TRY(launch_rnn_len(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights and the lengths are freed on return
+    return 0;
+}
+
 int s3enc_op_argmax_gather(const float* scores, const float* table, int32_t shared, int64_t rows, int32_t G, int32_t V, int32_t Dv,
                            int64_t* ids, float* out, void* stream) {
     if (!scores || (!ids && !out) || (out && !table)) return fail("s3enc_op_argmax_gather: null argument");
@@ -499,9 +555,16 @@ int s3enc_fbank_num_frames(const s3enc_fbank_config* cfg, int64_t n_samples, int
 
 int s3enc_fbank_forward(const s3enc_fbank_config* cfg, const float* const* wavs, const int64_t* lengths, int32_t B, float* out,
                         int64_t T_max, int32_t device, void* stream) {
+    return s3enc_fbank_forward_ex(cfg, 0, wavs, lengths, B, out, T_max, device, stream);
+}
+
+int s3enc_fbank_forward_ex(const s3enc_fbank_config* cfg, int32_t window, const float* const* wavs, const int64_t* lengths,
+                           int32_t B, float* out, int64_t T_max, int32_t device, void* stream) {
     if (!cfg || !wavs || !lengths || !out) return fail("s3enc_fbank_forward: null argument");
     if (B <= 0) return fail("s3enc_fbank_forward: empty batch");
-    const FbankParams f = fbank_params(cfg);
+    if (window < 0 || window > 1) return fail("s3enc_fbank_forward_ex: window must be 0 (povey) or 1 (hamming)");
+    FbankParams f = fbank_params(cfg);
+    f.window = window;
     if (f.delta_order < 0 || f.delta_order > 2 || f.delta_win < 3 || !(f.delta_win & 1)) return fail("s3enc_fbank_forward: unsupported delta configuration");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("s3enc_fbank_forward: no HIP device (there is no CPU fallback)");

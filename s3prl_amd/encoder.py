@@ -32,6 +32,8 @@ class HipEncoder:
             raise ValueError(f"wav2vec / vq-wav2vec are built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "cpc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             raise ValueError(f"modified CPC is built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "apc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"APC / VQ-APC are built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -63,6 +65,9 @@ class HipEncoder:
             elif cfg.family == "cpc":  # its paddings and recurrent network travel beside the (unchanged) s3enc_config
                 cpc = _lib.make_cpc_config(cfg)
                 rc = self._lib.s3enc_create_cpc(C.byref(ccfg), C.byref(cpc), tensors, len(weights), self.device, C.byref(h))
+            elif cfg.family == "apc":  # its front end and GRU stack travel beside the (unchanged) s3enc_config
+                apc = _lib.make_apc_config(cfg)
+                rc = self._lib.s3enc_create_apc(C.byref(ccfg), C.byref(apc), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")
@@ -168,6 +173,9 @@ class HipEncoder:
             held.append(w)
         lengths = [int(w.numel()) for w in held]
         nm = max(lengths) if n_max is None else int(n_max)
+        if self.cfg.family == "apc" and min(self.num_frames(n) for n in lengths) < 1:
+            raise ValueError(f"an utterance of {min(lengths)} samples is shorter than one analysis window of the APC front end "
+                             f"({self.cfg.conv_layers[0][1]} samples)")
         if self.num_frames(nm) < 1:
             raise ValueError(f"input of {nm} samples is shorter than the receptive field of the conv stack")
         T = self.num_output_frames(nm)

@@ -16,6 +16,8 @@ from .upstream.baseline.hubconf import *  # noqa: F401,F403
 from .upstream.wav2vec.hubconf import *  # noqa: F401,F403
 from .upstream.vq_wav2vec.hubconf import *  # noqa: F401,F403
 from .upstream.cpc.hubconf import *  # noqa: F401,F403
+from .upstream.apc.hubconf import *  # noqa: F401,F403
+from .upstream.vq_apc.hubconf import *  # noqa: F401,F403
 
 
 def options(only_registered_ckpt: bool = False):

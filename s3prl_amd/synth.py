@@ -24,6 +24,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _wav2vec_shapes(cfg)
     if cfg.family == "cpc":
         return _cpc_shapes(cfg)
+    if cfg.family == "apc":
+        return _apc_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -186,6 +188,19 @@ def _cpc_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     return s
 
 
+def _apc_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """APC (upstream/apc/apc.py:41-48): the GRU layers, reference state_dict names.  ``postnet.*`` and VQ-APC's ``vq_layers.*``
+    feed only the discarded prediction and are not hot-path parameters."""
+    s: Dict[str, tuple] = {}
+    H = cfg.conv_dim
+    for l in range(cfg.apc_layers):
+        s[f"rnn_layers.{l}.weight_ih_l0"] = (3 * H, cfg.apc_feat_dim if l == 0 else H)
+        s[f"rnn_layers.{l}.weight_hh_l0"] = (3 * H, H)
+        s[f"rnn_layers.{l}.bias_ih_l0"] = (3 * H,)
+        s[f"rnn_layers.{l}.bias_hh_l0"] = (3 * H,)
+    return s
+
+
 def _multires_shapes(cfg: EncoderConfig, s: Dict[str, tuple]) -> Dict[str, tuple]:
     """multires-HuBERT (hubert_model.py:337-530): encoders.{i} / middle_encoder / decoders.{i} TransformerEncoders (only
     encoders.0 keeps its positional conv, :399-403,434-449) and the conv adapters between them."""
@@ -325,6 +340,13 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
             gain = 1.5 if "weight_hh" in name else (2.5 if name.endswith("_l0") else 6.0)
             w = rng.standard_normal(shape) * (gain / np.sqrt(shape[1]))
         elif name.startswith("gAR.baseNet.bias"):
+            w = 0.1 * rng.standard_normal(shape)
+        elif name.startswith("rnn_layers.") and ".weight_" in name:
+            # APC's GRU layers, by the rule above: the CMVN'd log-mel input has unit variance (2.5 / sqrt(fan_in)); the layers
+            # behind read hidden states (plus, with the residual, the states below them)
+            gain = 1.5 if "weight_hh" in name else (2.5 if name.startswith("rnn_layers.0.") else 4.0)
+            w = rng.standard_normal(shape) * (gain / np.sqrt(shape[1]))
+        elif name.startswith("rnn_layers.") and ".bias_" in name:
             w = 0.1 * rng.standard_normal(shape)
         elif name in ("vector_quantizer.embedding", "vector_quantizer.vars"):
             # codebooks at the scale of what they are compared with / replace (a trained k-means embedding lives where the
@@ -487,8 +509,23 @@ def named_config(name: str) -> EncoderConfig:
         from .config import cpc_config
 
         return cpc_config(**cpc[name])
+    # APC / VQ-APC: 25 ms / 10 ms hamming log-mel (80 bins, CMVN) into GRU layers on packed sequences
+    apc = {
+        "tiny_apc": dict(hidden=64, num_layers=3, residual=True),
+        "tiny_apc_nores": dict(hidden=64, num_layers=3, residual=False),
+        "tiny_apc_nocmvn": dict(hidden=64, num_layers=3, residual=True, cmvn=False),  # a one-frame utterance has no std
+        "tiny_apc_l4": dict(hidden=64, num_layers=4, residual=True),
+        "tiny_vq_apc": dict(hidden=128, num_layers=3, residual=True,
+                            vq=dict(codebook_size=[32], code_dim=[128], gumbel_temperature=0.5)),
+        # the released apc_360hr / vq_apc_360hr shape (a checkpoint's own config decides at load time)
+        "apc_360hr": dict(hidden=512, num_layers=3, residual=True),
+    }
+    if name in apc:
+        from .config import apc_config
+
+        return apc_config(**apc[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
