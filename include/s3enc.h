@@ -55,7 +55,13 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * deltas, CMVN over time) and 3 or 4 unidirectional GRU layers run on PACKED sequences: an utterance's recurrence stops at
         * its own frame count and the rows behind it are zeros.  Three states of (B, T, hidden): the inputs of rnn_layers[1] and
         * rnn_layers[2] and the last layer's output.  compute_dtype S3ENC_F32 only; built by s3enc_create_apc. */
-       S3ENC_APC = 7 };
+       S3ENC_APC = 7,
+       /* Mockingjay / TERA / AudioALBERT (upstream/mockingjay/{expert,builder,model}.py): a spectrogram front end (the
+        * OnlinePreprocessor log-mel or the kaldi fbank of upstream/baseline), Linear + sinusoid position table + LayerNorm, then
+        * post-LN BERT layers (optionally one layer's weights run encoder_layers times), inputs over `sequence_length` frames
+        * forwarded in chunks.  encoder_layers + 1 states of (B, T, embed_dim).  compute_dtype S3ENC_F32 only; built by
+        * s3enc_create_mockingjay. */
+       S3ENC_MOCKINGJAY = 8 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -216,6 +222,37 @@ typedef struct s3enc_apc_config {
     int32_t residual;                               /* rnn_residual */
 } s3enc_apc_config;
 
+/* S3ENC_MOCKINGJAY only: the second configuration block of s3enc_create_mockingjay.  s3enc_config carries embed_dim (hidden_size),
+ * ffn_dim (intermediate_size), heads, encoder_layers (num_hidden_layers) and the frame geometry as a one-layer "conv stack":
+ * n_conv = 1, conv_stride[0] = 160, conv_kernel[0] = 0 for the mel front end (centred frames: T = 1 + n / 160) or the analysis
+ * window (400) for the kaldi one; conv_dim = embed_dim.  Checkpoint tensors, reference state_dict names of `Transformer`:
+ * input_representations.{spec_transform,LayerNorm}.{weight,bias}, encoder.layer.N.attention.self.{query,key,value}.{weight,bias},
+ * encoder.layer.N.attention.output.{dense,LayerNorm}.{weight,bias}, encoder.layer.N.intermediate.dense.{weight,bias},
+ * encoder.layer.N.output.{dense,LayerNorm}.{weight,bias}; with share_layer only N = 0 is read (and uploaded once).
+ * Refused by name: every compute dtype but fp32, pre_layer_norm, hidden_act other than gelu, embed_dim / heads != 64,
+ * input_dim not a multiple of 4. */
+typedef struct s3enc_mockingjay_config {
+    int32_t input_dim;        /* width of a feature row: n_mels, or num_mel_bins * (delta_order + 1) */
+    float layer_norm_eps;     /* 1e-12: EVERY LayerNorm of the family */
+    int32_t share_layer;      /* AudioALBERT: layer 0's weights run encoder_layers times */
+    int32_t sequence_length;  /* task.sequence_length: 0 = never chunk; T > it: torch.chunk(x, ceil(T / it), dim = 1) */
+    int32_t frontend;         /* 0 = kaldi (`fbank`), 1 = mel (OnlinePreprocessor, feat_type mel, log, delta 0) */
+    int32_t n_mels;           /* mel */
+    float target_level;       /* mel: -25 dB */
+    int32_t cmvn;             /* mel */
+    int32_t pre_layer_norm;   /* refused */
+    int32_t hidden_act;       /* 0 gelu; anything else is refused */
+    /* kaldi: what the `fbank` baseline's configuration block carries, at a sample rate of 16000 */
+    int32_t fbank_num_mel_bins;
+    float fbank_frame_length_ms;
+    float fbank_frame_shift_ms;
+    float fbank_preemphasis;
+    int32_t fbank_delta_order;
+    int32_t fbank_delta_win_length;
+    int32_t fbank_use_cmvn;
+    float fbank_cmvn_eps;
+} s3enc_mockingjay_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -253,6 +290,16 @@ int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const
  * refused), out_dtype must be S3ENC_F32.  Every state row behind an utterance's frame count is exactly 0. */
 int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out);
+/* The S3ENC_MOCKINGJAY family: s3enc_config beside its own block (the other create entries refuse the family by name).  Replaces
+ * PretrainedTransformer.__init__ / forward of upstream/mockingjay/builder.py.  On the handle: s3enc_num_frames is the STAND-ALONE
+ * frame count (mel: 1 + n / 160); s3enc_valid_frames(length, n_max) is the utterance's frame count INSIDE a batch padded to n_max
+ * — for the mel front end with CMVN round(length / (n_max / T)), which can be one less than the stand-alone count (8000 samples
+ * beside 16000: 50, alone 51); without CMVN every row is live (T).  States: the input representation, then every layer's output.
+ * Rows at or behind an utterance's frame count are padding: what the kernels compute there (the zero feature rows run through
+ * the model, attention over the chunk's live keys, or over key 0 alone in a chunk without a live key) — finite, deterministic,
+ * inside the buffer, and not the reference's values. */
+int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
+                            int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -631,6 +678,26 @@ int s3enc_fbank_forward(const s3enc_fbank_config* cfg, const float* const* wavs,
  * 0.54 - 0.46 cos(2 pi i / (N - 1)) (APC's front end, apc/audio.py:22,82-88).  s3enc_fbank_config is unchanged. */
 int s3enc_fbank_forward_ex(const s3enc_fbank_config* cfg, int32_t window, const float* const* wavs, const int64_t* lengths,
                            int32_t B, float* out, int64_t T_max, int32_t device, void* stream);
+
+
+/* ---- the OnlinePreprocessor log-mel front end (Mockingjay / TERA / AudioALBERT, upstream/baseline/preprocessor.py) ----
+ * counts[b] = round(lengths[b] / (n_max / T)) with T = 1 + n_max / 160, in doubles, halves to even (Python's round): the frames
+ * the reference's CMVN runs over.  n_max = 0: the longest length.  Host only. */
+int s3enc_logmel_frame_counts(const int64_t* lengths, int32_t B, int64_t n_max, int32_t* counts);
+/* wavs: host array of B device pointers; out: device fp32 (B, T, n_mels) with T = 1 + n_max / 160 (n_max = 0: the longest
+ * length; it must exceed 200 samples, like every utterance).  Per utterance x * 10^(target_level / 20) / (rms + 1e-10), the
+ * batch zero-padded to n_max, centred periodic-hann STFT (400 / 160, reflect) of the PADDED rows, |X|^2, HTK mel, log(x + 1e-10);
+ * with cmvn: per mel bin over counts[b] frames (HOST int32, each >= 2), rows behind are zeros.  Synchronises. */
+int s3enc_logmel_forward(const float* const* wavs, const int64_t* lengths, int32_t B, int64_t n_max, int32_t n_mels,
+                         float target_level, int32_t cmvn, const int32_t* counts, float* out, int32_t device, void* stream);
+/* TF-style LayerNorm with a run-time eps: y = (x - mean) / sqrt(var + eps) * gamma + beta over rows of C fp32 (C % 4 == 0,
+ * C <= 2048; biased variance).  Asynchronous on `stream`. */
+int s3enc_op_layernorm_eps(const float* x, const float* gamma, const float* beta, float eps, int64_t rows, int32_t C, float* out,
+                           void* stream);
+/* The family's input representation: out[r] = LayerNorm_eps(feat[r] W^T + bias + pos[r % Tc]) for `rows` rows; feat: device
+ * (rows, F), W: device (D, F), pos_host: HOST (>= Tc, D) position rows (uploaded inside).  F % 4 == 0, D % 4 == 0.  Synchronises. */
+int s3enc_op_input_repr(const float* feat, const float* w, const float* bias, const float* pos_host, int32_t Tc, const float* gamma,
+                        const float* beta, float eps, int64_t rows, int32_t F, int32_t D, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -76,6 +76,18 @@ class S3ApcConfig(C.Structure):
     ]
 
 
+class S3MockingjayConfig(C.Structure):
+    """s3enc_mockingjay_config: the front-end / input-representation block of a Mockingjay handle (s3enc_create_mockingjay)."""
+    _fields_ = [
+        ("input_dim", C.c_int32), ("layer_norm_eps", C.c_float), ("share_layer", C.c_int32), ("sequence_length", C.c_int32),
+        ("frontend", C.c_int32), ("n_mels", C.c_int32), ("target_level", C.c_float), ("cmvn", C.c_int32),
+        ("pre_layer_norm", C.c_int32), ("hidden_act", C.c_int32),
+        ("fbank_num_mel_bins", C.c_int32), ("fbank_frame_length_ms", C.c_float), ("fbank_frame_shift_ms", C.c_float),
+        ("fbank_preemphasis", C.c_float), ("fbank_delta_order", C.c_int32), ("fbank_delta_win_length", C.c_int32),
+        ("fbank_use_cmvn", C.c_int32), ("fbank_cmvn_eps", C.c_float),
+    ]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -105,6 +117,8 @@ _PROTOS = {
     "s3enc_create_ex": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Wav2vecConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_cpc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3CpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_apc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3ApcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    "s3enc_create_mockingjay": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3MockingjayConfig), C.POINTER(S3Tensor), _I32, _I32,
+                                          C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -159,6 +173,10 @@ _PROTOS = {
     "s3enc_fbank_num_frames": (C.c_int, [C.POINTER(S3FbankConfig), _I64, C.POINTER(_I32)]),
     "s3enc_fbank_forward": (C.c_int, [C.POINTER(S3FbankConfig), _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
     "s3enc_fbank_forward_ex": (C.c_int, [C.POINTER(S3FbankConfig), _I32, _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
+    "s3enc_logmel_frame_counts": (C.c_int, [C.POINTER(_I64), _I32, _I64, C.POINTER(_I32)]),
+    "s3enc_logmel_forward": (C.c_int, [_VP, C.POINTER(_I64), _I32, _I64, _I32, C.c_float, _I32, C.POINTER(_I32), _VP, _I32, _VP]),
+    "s3enc_op_layernorm_eps": (C.c_int, [_VP, _VP, _VP, C.c_float, _I64, _I32, _VP, _VP]),
+    "s3enc_op_input_repr": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, C.c_float, _I64, _I32, _I32, _VP, _VP]),
 }
 
 _lib = None
@@ -302,4 +320,25 @@ def make_apc_config(cfg) -> S3ApcConfig:
     c.window = APC_WINDOW.get(cfg.apc_window, -1)
     c.cmvn = int(cfg.apc_cmvn)
     c.hidden, c.num_layers, c.residual = int(cfg.conv_dim), int(cfg.apc_layers), int(cfg.apc_residual)
+    return c
+
+
+MJ_FRONTEND = {"kaldi": 0, "mel": 1}                                               # s3enc_mockingjay_config.frontend
+
+
+def make_mockingjay_config(cfg) -> S3MockingjayConfig:
+    """The second configuration block of a ``family="mockingjay"`` EncoderConfig (``s3enc_create_mockingjay``)."""
+    if cfg.family != "mockingjay":
+        raise S3EncError("make_mockingjay_config needs a mockingjay configuration")
+    c = S3MockingjayConfig()
+    c.input_dim, c.layer_norm_eps = int(cfg.mj_input_dim), float(cfg.mj_layer_norm_eps)
+    c.share_layer, c.sequence_length = int(cfg.mj_share_layer), int(cfg.mj_sequence_length)
+    c.frontend = MJ_FRONTEND.get(cfg.mj_frontend, -1)
+    c.n_mels, c.target_level, c.cmvn = int(cfg.mj_input_dim), float(cfg.mj_target_level), int(cfg.mj_cmvn)
+    c.pre_layer_norm, c.hidden_act = int(cfg.mj_pre_layer_norm), int(cfg.mj_hidden_act != "gelu")
+    c.fbank_num_mel_bins = int(cfg.mj_kaldi_mel_bins)
+    c.fbank_frame_length_ms, c.fbank_frame_shift_ms = float(cfg.mj_kaldi_frame_length), float(cfg.mj_kaldi_frame_shift)
+    c.fbank_preemphasis = float(cfg.mj_kaldi_preemphasis)
+    c.fbank_delta_order, c.fbank_delta_win_length = int(cfg.mj_delta_order), int(cfg.mj_delta_win)
+    c.fbank_use_cmvn, c.fbank_cmvn_eps = int(cfg.mj_cmvn), 1e-10
     return c

@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, config_from_apc, config_from_cpc, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, config_from_apc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -72,6 +72,69 @@ def load_apc_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]
     return cfg, _hot_path_weights(ckpt, cfg, state["model"])
 
 
+def mockingjay_state_dict(sd) -> Dict:
+    """The legacy LayerNorm names of a ``Transformer`` state_dict, renamed as ``TransformerBuilder.load_model`` does
+    (mockingjay/builder.py:136-150): ``gamma`` -> ``weight``, ``beta`` -> ``bias``."""
+    out = {}
+    for key, value in sd.items():
+        if "gamma" in key:
+            key = key.replace("gamma", "weight")
+        if "beta" in key:
+            key = key.replace("beta", "bias")
+        out[key] = value
+    return out
+
+
+def load_mockingjay_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"Transformer": state_dict, "Upstream_Config" (legacy: "Config"): {transformer, task, audio}, ...}``
+    (mockingjay/builder.py:59-76).  ``SpecHead`` (the pre-training head) is left in the file; a config without an ``audio`` block
+    is refused, as the reference's expert refuses it."""
+    import sys
+    import types
+
+    import torch
+
+    # old checkpoints pickle a scheduler of the reference's `optimizers` module (builder.py:53-56): a placeholder module lets the
+    # unpickler resolve the name; the object is never used
+    had = sys.modules.get("optimizers")
+    if had is None:
+        stub = types.ModuleType("optimizers")
+        stub.__getattr__ = lambda name: type(name, (), {"__setstate__": lambda self, st: None})  # type: ignore[assignment]
+        sys.modules["optimizers"] = stub
+    try:
+        state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    finally:
+        if had is None:
+            sys.modules.pop("optimizers", None)
+    if "Transformer" not in state:
+        raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: Transformer is missing")
+    if "transformer" in state.get("Config", {}):
+        config = state["Config"]  # legacy: 'Config' is the upstream config
+    elif "transformer" in state.get("Upstream_Config", {}):
+        config = state["Upstream_Config"]
+    else:
+        raise NotImplementedError(f"{ckpt}: neither 'Config' nor 'Upstream_Config' holds a 'transformer' block")
+    cfg = config_from_mockingjay(config)
+    return cfg, _hot_path_weights(ckpt, cfg, mockingjay_state_dict(state["Transformer"]))
+
+
+def mockingjay_upstream_config(cfg: EncoderConfig) -> Dict:
+    """The ``Upstream_Config`` dict of a ``family="mockingjay"`` configuration, in the schema of pretrain/tera/config_model.yaml."""
+    t = dict(input_dim=-1, hidden_size=cfg.encoder_embed_dim, num_hidden_layers=cfg.encoder_layers,
+             num_attention_heads=cfg.encoder_attention_heads, intermediate_size=cfg.encoder_ffn_embed_dim,
+             hidden_act=cfg.mj_hidden_act, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, initializer_range=0.02,
+             layer_norm_eps=cfg.mj_layer_norm_eps, share_layer=cfg.mj_share_layer, pre_layer_norm=cfg.mj_pre_layer_norm)
+    if cfg.mj_frontend == "kaldi":
+        audio = dict(kaldi=dict(feat_type="fbank", fbank=dict(num_mel_bins=cfg.mj_kaldi_mel_bins, frame_length=cfg.mj_kaldi_frame_length,
+                                                              frame_shift=cfg.mj_kaldi_frame_shift, use_log_fbank=True)),
+                     delta=dict(order=cfg.mj_delta_order, win_length=cfg.mj_delta_win), cmvn=dict(use_cmvn=cfg.mj_cmvn))
+    else:
+        feat = dict(feat_type="mel", channel=0, log=True, delta=0, cmvn=cfg.mj_cmvn)
+        audio = dict(target_level=cfg.mj_target_level, win_ms=25, hop_ms=10, n_freq=201, n_mels=cfg.mj_input_dim, n_mfcc=13,
+                     input=dict(feat), target=dict(feat, channel=1))
+    return dict(transformer=t, task=dict(sequence_length=cfg.mj_sequence_length), audio=audio)
+
+
 def _hot_path_weights(ckpt: str, cfg: EncoderConfig, sd) -> Dict[str, np.ndarray]:
     weights = {}
     for name, shape in param_shapes(cfg).items():
@@ -92,6 +155,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_cpc_checkpoint(ckpt)
     if family == "apc":
         return load_apc_checkpoint(ckpt)
+    if family == "mockingjay":
+        return load_mockingjay_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -139,6 +204,10 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
     import torch
 
     sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.items()}
+    if cfg.family == "mockingjay":  # upstream/mockingjay/builder.py:59-76
+        # new-style files keep the runner's config under "Config" and the reference's builder reads that key first
+        torch.save({"Transformer": sd, "Upstream_Config": mockingjay_upstream_config(cfg), "Config": {"runner": {}}}, path)
+        return
     if cfg.family == "apc":  # upstream/apc/expert.py:22-27
         audio = dict(feat_type=cfg.apc_feat_type, feat_dim=cfg.apc_feat_dim, frame_length=cfg.apc_frame_length,
                      frame_shift=cfg.apc_frame_shift, decode_wav=False, cmvn=cfg.apc_cmvn)

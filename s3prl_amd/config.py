@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -145,6 +145,25 @@ class EncoderConfig:
     apc_layers: int = 3               # paras.num_layers
     apc_residual: bool = True         # paras.residual
     apc_vq: Dict | None = None        # paras.vq (VQ-APC): feeds only the discarded prediction; kept for the checkpoint round trip
+    # Mockingjay / TERA / AudioALBERT (family "mockingjay", upstream/mockingjay/{builder,model}.py): a spectrogram front end, the
+    # input representation (Linear + sinusoid position table + LayerNorm) and ``encoder_layers`` post-LN BERT layers of width
+    # ``encoder_embed_dim``.  ``conv_layers`` = [(hidden, window, 160)] carries the frame geometry: window 0 for the mel front end
+    # (centred frames: T = 1 + n // 160), the analysis window in samples for the kaldi one
+    mj_input_dim: int = 80            # width of a feature row (n_mels, or num_mel_bins * (delta order + 1))
+    mj_layer_norm_eps: float = 1e-12  # transformer.layer_norm_eps: EVERY LayerNorm of the family
+    mj_share_layer: bool = False      # transformer.share_layer (AudioALBERT): one layer's weights run encoder_layers times
+    mj_sequence_length: int = 1500    # task.sequence_length: longer inputs are forwarded in torch.chunk pieces; 0 = never
+    mj_frontend: str = "mel"          # "mel" (audio.input: OnlinePreprocessor) or "kaldi" (audio.kaldi: baseline/extracter.py)
+    mj_target_level: float = -25.0    # audio.target_level (mel)
+    mj_cmvn: bool = True              # audio.input.cmvn (mel) / audio.cmvn.use_cmvn (kaldi)
+    mj_pre_layer_norm: bool = False   # transformer.pre_layer_norm (refused)
+    mj_hidden_act: str = "gelu"       # transformer.hidden_act (anything else is refused)
+    mj_kaldi_mel_bins: int = 80       # audio.kaldi.fbank.num_mel_bins
+    mj_kaldi_frame_length: float = 25.0
+    mj_kaldi_frame_shift: float = 10.0
+    mj_kaldi_preemphasis: float = 0.97
+    mj_delta_order: int = 2           # audio.delta.order (kaldi)
+    mj_delta_win: int = 5             # audio.delta.win_length
 
     # ---- derived -------------------------------------------------------------------------
     @property
@@ -184,6 +203,8 @@ class EncoderConfig:
         return out
 
     def num_frames(self, n: int) -> int:
+        if self.family == "mockingjay" and self.mj_frontend == "mel":  # centred STFT frames; torch.stft refuses n <= 200
+            return 1 + n // 160 if n > 200 else 0
         return self.conv_lengths(n)[-1]
 
     def valid_frames(self, length: int, n_max: int) -> int:
@@ -197,6 +218,11 @@ class EncoderConfig:
         T = self.num_frames(n_max)
         if T <= 0:
             return 0
+        if self.family == "mockingjay" and self.mj_frontend == "mel":
+            # preprocessor.py:204-205: batch-dependent, Python floats and Python's round; without CMVN no feature row is zero
+            return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
+        if self.family == "mockingjay":
+            return min(T, max(self.num_frames(length), 0))
         if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
@@ -300,6 +326,8 @@ class EncoderConfig:
             return self._validate_cpc()
         if self.family == "apc":
             return self._validate_apc()
+        if self.family == "mockingjay":
+            return self._validate_mockingjay()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -401,6 +429,44 @@ class EncoderConfig:
             raise ValueError(f"apc feat_dim must be a multiple of 4, at most 256, got {self.apc_feat_dim}")
         if self.encoder_layers != 2 or self.encoder_embed_dim != H:
             raise ValueError("apc: encoder_layers / encoder_embed_dim must be 2 / hidden_size (apc_config sets them)")
+
+    def _validate_mockingjay(self) -> None:
+        """What the HIP path builds of the Mockingjay configuration; everything else is refused by name (s3enc_create_mockingjay
+        repeats it)."""
+        D, H = self.encoder_embed_dim, self.encoder_attention_heads
+        if self.mj_pre_layer_norm:
+            raise ValueError("mockingjay pre_layer_norm=True is not built (no released checkpoint uses it)")
+        if self.mj_hidden_act != "gelu":
+            raise ValueError(f"mockingjay hidden_act={self.mj_hidden_act!r} is not built: only 'gelu'")
+        if H < 1 or D != 64 * H:
+            raise ValueError(f"mockingjay hidden_size / num_attention_heads must be 64 (the attention kernel's head width), got {D} / {H}")
+        if self.encoder_layers < 1:
+            raise ValueError("mockingjay num_hidden_layers must be positive")
+        if self.encoder_ffn_embed_dim % 4 or self.encoder_ffn_embed_dim < 4:
+            raise ValueError("mockingjay intermediate_size must be a multiple of 4")
+        if self.mj_input_dim % 4 or self.mj_input_dim < 4:
+            raise ValueError(f"mockingjay input_dim must be a multiple of 4 (the GEMM reads 16-byte vectors), got {self.mj_input_dim}")
+        if self.mj_sequence_length < 0:
+            raise ValueError("mockingjay sequence_length must not be negative")
+        if not 0.0 <= self.mj_layer_norm_eps <= 1.0:
+            raise ValueError("mockingjay layer_norm_eps out of range")
+        if self.mj_frontend not in ("mel", "kaldi"):
+            raise ValueError(f"mockingjay front end {self.mj_frontend!r}: 'mel' or 'kaldi'")
+        if self.mj_frontend == "mel":
+            if self.mj_input_dim > 256:
+                raise ValueError("mockingjay n_mels above 256 is not built")
+            want = [(D, 0, 160)]
+        else:
+            size, shift = int(16000 * self.mj_kaldi_frame_length * 0.001), int(16000 * self.mj_kaldi_frame_shift * 0.001)
+            if shift != 160 or size % 4 or size < 4:
+                raise ValueError("mockingjay kaldi front end: a 10 ms frame shift and a window that is a multiple of 4 samples")
+            if not 0 <= self.mj_delta_order <= 2 or self.mj_delta_win < 3 or self.mj_delta_win % 2 == 0:
+                raise ValueError("mockingjay kaldi front end: delta order 0..2 and an odd win_length >= 3")
+            if self.mj_input_dim != self.mj_kaldi_mel_bins * (self.mj_delta_order + 1):
+                raise ValueError("mockingjay input_dim must be num_mel_bins * (delta order + 1)")
+            want = [(D, size, 160)]
+        if [tuple(x) for x in self.conv_layers] != want:
+            raise ValueError("mockingjay: conv_layers carries the frame geometry as one (hidden, window, 160) entry (mockingjay_config sets it)")
 
     def to_dict(self) -> Dict:
         return asdict(self)
@@ -535,6 +601,71 @@ def config_from_apc(config: Dict) -> EncoderConfig:
             raise ValueError(f"apc checkpoint: model.paras.{key} is missing")
     return apc_config(paras["hidden_size"], paras["num_layers"], paras["residual"], feat_dim, frame_length, frame_shift, cmvn,
                       paras.get("vq"), apc_feat_type=str(feat_type))
+
+
+def mockingjay_config(hidden: int = 768, layers: int = 3, heads: int = 12, intermediate: int = 3072, input_dim: int = 80,
+                      frontend: str = "mel", sequence_length: int = 1500, share_layer: bool = False, layer_norm_eps: float = 1e-12,
+                      cmvn: bool = True, target_level: float = -25.0, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "mockingjay" (mockingjay/model.py:25-41, builder.py:96-122)."""
+    cfg = EncoderConfig(family="mockingjay", encoder_layers=int(layers), encoder_embed_dim=int(hidden),
+                        encoder_ffn_embed_dim=int(intermediate), encoder_attention_heads=int(heads), mj_input_dim=int(input_dim),
+                        mj_frontend=frontend, mj_sequence_length=int(sequence_length), mj_share_layer=bool(share_layer),
+                        mj_layer_norm_eps=float(layer_norm_eps), mj_cmvn=bool(cmvn), mj_target_level=float(target_level), **flags)
+    if frontend == "kaldi":
+        window = int(16000 * cfg.mj_kaldi_frame_length * 0.001)
+    else:
+        window = 0
+    cfg.conv_layers = [(int(hidden), window, 160)]
+    cfg.validate()
+    return cfg
+
+
+def config_from_mockingjay(config: Dict) -> EncoderConfig:
+    """The checkpoint's ``Upstream_Config`` (legacy: ``Config``): ``transformer`` as ``TransformerConfig`` reads it
+    (mockingjay/model.py:25-41), ``task.sequence_length`` and the ``audio`` block as ``TransformerBuilder`` does
+    (builder.py:100-114): ``audio.kaldi`` -> baseline/extracter.py, otherwise ``audio.input`` -> OnlinePreprocessor."""
+    for key in ("transformer", "task"):
+        if key not in config:
+            raise ValueError(f"mockingjay checkpoint: the upstream config has no {key!r} block")
+    if "audio" not in config:
+        raise ValueError("mockingjay checkpoint: no `audio` block — the upstream expert only supports on-the-fly checkpoints with "
+                         "a built-in feature extracter (upstream/mockingjay/expert.py:52-54)")
+    t, audio = config["transformer"], config["audio"]
+    flags = dict(mj_pre_layer_norm=bool(t.get("pre_layer_norm", False)), mj_hidden_act=str(t.get("hidden_act", "gelu")))
+    if "kaldi" in audio:
+        kaldi = audio["kaldi"]
+        if kaldi.get("feat_type", "fbank") != "fbank":
+            raise NotImplementedError(f"mockingjay audio.kaldi.feat_type={kaldi.get('feat_type')!r} is not built: only 'fbank'")
+        fb = dict(kaldi.get("fbank", {}))
+        if not fb.pop("use_log_fbank", True):
+            raise NotImplementedError("mockingjay audio.kaldi.fbank.use_log_fbank=False is not built")
+        flags.update(mj_kaldi_mel_bins=int(fb.pop("num_mel_bins", 23)), mj_kaldi_frame_length=float(fb.pop("frame_length", 25.0)),
+                     mj_kaldi_frame_shift=float(fb.pop("frame_shift", 10.0)),
+                     mj_kaldi_preemphasis=float(fb.pop("preemphasis_coefficient", 0.97)))
+        if fb:
+            raise NotImplementedError(f"mockingjay audio.kaldi.fbank options {sorted(fb)} are not built")
+        delta, cm = audio.get("delta", {}), audio.get("cmvn", {})
+        flags.update(mj_delta_order=int(delta.get("order", 2)), mj_delta_win=int(delta.get("win_length", 5)))
+        frontend, cmvn, target = "kaldi", bool(cm.get("use_cmvn", False)), -25.0
+        input_dim = flags["mj_kaldi_mel_bins"] * (flags["mj_delta_order"] + 1)
+    else:
+        if "input" not in audio:
+            raise ValueError("mockingjay checkpoint: audio has neither a `kaldi` nor an `input` block")
+        inp = audio["input"]
+        if inp.get("feat_type") != "mel":
+            raise NotImplementedError(f"mockingjay audio.input.feat_type={inp.get('feat_type')!r} is not built: only 'mel'")
+        if int(inp.get("delta", 0)) > 0:
+            raise NotImplementedError("mockingjay audio.input.delta > 0 is not built")
+        if not bool(inp.get("log", False)):
+            raise NotImplementedError("mockingjay audio.input.log=False is not built")
+        for key, want in (("win_ms", 25), ("hop_ms", 10), ("n_freq", 201), ("sample_rate", 16000)):
+            if audio.get(key, want) != want:
+                raise NotImplementedError(f"mockingjay audio.{key}={audio[key]!r} is not built: only {want}")
+        frontend, cmvn, target = "mel", bool(inp.get("cmvn", False)), float(audio["target_level"])
+        input_dim = int(audio.get("n_mels", 40))
+    return mockingjay_config(t["hidden_size"], t["num_hidden_layers"], t["num_attention_heads"], t["intermediate_size"], input_dim,
+                             frontend, config["task"]["sequence_length"], bool(t.get("share_layer", False)),
+                             float(t.get("layer_norm_eps", 1e-12)), cmvn, target, **flags)
 
 
 def config_from_multires(model_cfg: Dict, task_cfg: Dict | None = None) -> EncoderConfig:

@@ -93,10 +93,11 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 7) return fail("config: unknown family");
+    if (c.family < 0 || c.family > 8) return fail("config: unknown family");
     if (c.family == S3ENC_WAV2VEC) return 0;  // s3enc_create_ex: wav2vec_check_config on both configuration blocks
     if (c.family == S3ENC_CPC) return 0;      // s3enc_create_cpc: cpc_check_config on both configuration blocks
     if (c.family == S3ENC_APC) return 0;      // s3enc_create_apc: apc_check_config on both configuration blocks
+    if (c.family == S3ENC_MOCKINGJAY) return 0;  // s3enc_create_mockingjay: mj_check_config on both configuration blocks
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
         const int k = c.mr_kernel;
@@ -181,7 +182,8 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
+                       const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out,
+                       const s3enc_mockingjay_config* mj = nullptr);
 
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out) {
@@ -193,6 +195,10 @@ int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, co
         if (out) *out = nullptr;
         return fail("s3enc_create: the APC family needs its front-end / GRU block: use s3enc_create_apc");
     }
+    if (cfg && cfg->family == S3ENC_MOCKINGJAY) {
+        if (out) *out = nullptr;
+        return fail("s3enc_create: the Mockingjay / TERA / AudioALBERT family needs its front-end block: use s3enc_create_mockingjay");
+    }
     return create_impl(cfg, w2v, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
@@ -201,6 +207,8 @@ int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const
     if (!cfg || !cpc || !tensors || !out) return fail("s3enc_create_cpc: null argument");
     *out = nullptr;
     if (cfg->family == S3ENC_APC) return fail("s3enc_create_cpc: the APC family needs its front-end / GRU block: use s3enc_create_apc");
+    if (cfg->family == S3ENC_MOCKINGJAY)
+        return fail("s3enc_create_cpc: the Mockingjay / TERA / AudioALBERT family needs its front-end block: use s3enc_create_mockingjay");
     if (cfg->family != S3ENC_CPC) return fail("s3enc_create_cpc: the cpc block belongs to family S3ENC_CPC only");
     return create_impl(cfg, nullptr, cpc, nullptr, tensors, n_tensors, device, out);
 }
@@ -209,12 +217,23 @@ int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const
                      int32_t device, s3enc_handle* out) {
     if (!cfg || !apc || !tensors || !out) return fail("s3enc_create_apc: null argument");
     *out = nullptr;
+    if (cfg->family == S3ENC_MOCKINGJAY)
+        return fail("s3enc_create_apc: the Mockingjay / TERA / AudioALBERT family needs its front-end block: use s3enc_create_mockingjay");
     if (cfg->family != S3ENC_APC) return fail("s3enc_create_apc: the apc block belongs to family S3ENC_APC only");
     return create_impl(cfg, nullptr, nullptr, apc, tensors, n_tensors, device, out);
 }
 
+int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
+                            int32_t device, s3enc_handle* out) {
+    if (!cfg || !mj || !tensors || !out) return fail("s3enc_create_mockingjay: null argument");
+    *out = nullptr;
+    if (cfg->family != S3ENC_MOCKINGJAY) return fail("s3enc_create_mockingjay: the mockingjay block belongs to family S3ENC_MOCKINGJAY only");
+    return create_impl(cfg, nullptr, nullptr, nullptr, tensors, n_tensors, device, out, mj);
+}
+
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
+                       const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out,
+                       const s3enc_mockingjay_config* mj) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
@@ -223,6 +242,10 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
     }
     if (cfg->family == S3ENC_APC) {
         if (apc_check_config(*cfg, *apc)) return 1;
+    }
+    if (cfg->family == S3ENC_MOCKINGJAY) {
+        if (!mj) return fail("s3enc_create: the Mockingjay / TERA / AudioALBERT family needs its front-end block: use s3enc_create_mockingjay");
+        if (mj_check_config(*cfg, *mj)) return 1;
     }
     if (cfg->family == S3ENC_WAV2VEC) {
         if (!w2v) return fail("s3enc_create: the wav2vec family needs its aggregator / quantizer block: use s3enc_create_ex");
@@ -271,6 +294,14 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
     if (cfg->family == S3ENC_APC) {
         e->apc_cfg = *apc;
         if (apc_create(e, tensors, n_tensors)) {
+            delete e;
+            return 1;
+        }
+        return finish_create(e, out);
+    }
+    if (cfg->family == S3ENC_MOCKINGJAY) {
+        e->mj_cfg = *mj;
+        if (mj_create(e, tensors, n_tensors)) {
             delete e;
             return 1;
         }
@@ -715,12 +746,20 @@ int s3enc_destroy(s3enc_handle h) {
 
 int s3enc_num_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
     if (!h || !T) return fail("s3enc_num_frames: null argument");
+    if (h->cfg.family == S3ENC_MOCKINGJAY) {  // the stand-alone count; inside a batch see s3enc_valid_frames
+        *T = (int32_t)mj_num_frames(h->cfg, h->mj_cfg, n_samples);
+        return 0;
+    }
     *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
                                               : conv_len(h->cfg, n_samples, h->cfg.n_conv));
     return 0;
 }
 int s3enc_num_output_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
     if (!h || !T) return fail("s3enc_num_output_frames: null argument");
+    if (h->cfg.family == S3ENC_MOCKINGJAY) {
+        *T = (int32_t)mj_num_frames(h->cfg, h->mj_cfg, n_samples);
+        return 0;
+    }
     *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
                                               : output_frames(h->cfg, n_samples));
     return 0;
@@ -738,6 +777,10 @@ int s3enc_valid_frames(s3enc_handle h, int64_t length, int64_t n_max, int32_t* v
         const long T = cpc_conv_len(h->cfg, h->cpc_cfg, n_max, h->cfg.n_conv);
         const long v = cpc_conv_len(h->cfg, h->cpc_cfg, length, h->cfg.n_conv);
         *valid = (int32_t)(T <= 0 ? 0 : std::max(0L, std::min(v, T)));
+        return 0;
+    }
+    if (h->cfg.family == S3ENC_MOCKINGJAY) {  // mel + CMVN: round(length / (n_max / T)), batch-dependent
+        *valid = mj_valid_frames(h->cfg, h->mj_cfg, length, n_max);
         return 0;
     }
     *valid = valid_frames(h->cfg, length, n_max);
@@ -1053,6 +1096,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     if (e->cfg.family == S3ENC_WAV2VEC) return wav2vec_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     if (e->cfg.family == S3ENC_CPC) return cpc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     if (e->cfg.family == S3ENC_APC) return apc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+    if (e->cfg.family == S3ENC_MOCKINGJAY) return mj_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
     const int dt = e->dtype, es = e->es;
@@ -1828,6 +1872,8 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
         return fail("s3enc_num_states: feature_selection is not defined for modified CPC (one hidden_states list of 2 states)");
     if (h->cfg.family == S3ENC_APC && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: feature_selection is not defined for APC (one hidden_states list of 3 states)");
+    if (h->cfg.family == S3ENC_MOCKINGJAY && selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_num_states: feature_selection is not defined for Mockingjay / TERA / AudioALBERT (one hidden_states list)");
     *n = num_states(h->cfg, selection);
     return 0;
 }

@@ -383,6 +383,17 @@ struct ApcW {
     std::vector<DevBuf> w_ih, b_pre, w_hh, b_hn;
 };
 
+// Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table, and per layer (ONE layer with
+// share_layer) q|k|v stacked as one (3 D, D) operand with q pre-scaled by head_dim^-0.5, the other projections and LayerNorm affines
+struct MjLayerW {
+    DevBuf wqkv, bqkv, wo, bo, g1, b1n, w1, b1, w2, b2, g2, b2n;
+};
+struct MjW {
+    DevBuf in_w, in_b, in_g, in_beta, pos;
+    int pos_rows = 0;
+    std::vector<MjLayerW> layers;
+};
+
 struct ProfRec {
     int kind;
     hipEvent_t a, b;
@@ -443,6 +454,8 @@ struct s3enc_encoder {
     s3enc_cpc_config cpc_cfg = {};      // ... and its second configuration block (s3enc_create_cpc)
     std::unique_ptr<ApcW> apc;          // S3ENC_APC
     s3enc_apc_config apc_cfg = {};      // ... and its second configuration block (s3enc_create_apc)
+    std::unique_ptr<MjW> mj;            // S3ENC_MOCKINGJAY
+    s3enc_mockingjay_config mj_cfg = {};  // ... and its second configuration block (s3enc_create_mockingjay)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -669,5 +682,13 @@ int apc_check_config(const s3enc_config& c, const s3enc_apc_config& x);
 int apc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
 int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+
+// mockingjay.hip: the S3ENC_MOCKINGJAY family (spectrogram front end + input representation + post-LN BERT layers, chunked)
+int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x);
+int mj_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
+long mj_num_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long n);
+int mj_valid_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long length, long n_max);
+int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+               const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
 }  // namespace s3e

@@ -495,4 +495,45 @@ long fbank_num_frames(long n_samples, const FbankParams& c);
 // one utterance: wav (device) -> out (device, frames x ldo), columns [0, num_mel_bins * (delta_order + 1))
 hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* out, int ldo, hipStream_t st);
 
+// ---- logmel.hip (OnlinePreprocessor: decibel scale, centred hann STFT on the padded batch, HTK mel, log, CMVN) --------
+long logmel_num_frames(long max_len);               // 1 + max_len / 160
+int logmel_frame_count(long length, long max_len);  // round(length / (max_len / T)) as Python rounds, clamped to [0, T]
+size_t logmel_sig_elems(int B, long max_len);       // floats of LogmelParams::sig
+size_t logmel_spec_elems(int B, long max_len);      // floats of LogmelParams::spec
+struct LogmelParams {
+    const float* const* wavs;  // device [B]
+    const long* lens;          // device [B] samples
+    const int* counts;         // device [B] frames the CMVN runs over (read only with cmvn)
+    int B;
+    long max_len;              // > 200: the length the batch is padded to
+    int n_mels;
+    float target_level;        // dB
+    int cmvn;
+    float* scale;              // scratch, B floats
+    float* sig;                // scratch, logmel_sig_elems floats, 16-byte aligned
+    float* spec;               // scratch, logmel_spec_elems floats
+    float* out;                // row (b, t) at out + b * o_bs + t * n_mels, t < logmel_num_frames(max_len)
+    long o_bs;
+};
+hipError_t launch_logmel(const LogmelParams& p, hipStream_t st);
+
+// ---- mockingjay.hip (TF-style LayerNorm with a run-time eps; the input representation's row pass) -----------------
+// y = (x (+ pos[row % Tc]) - mean) / sqrt(var + eps) * gamma + beta per row of C (biased variance), one wave per row.
+// out: (rows, C) or null; out2: row r = (b, t) of a (B, Tp) layout goes to out2 + (b * T + t) * C when t < T (the rows the
+// chunk padding adds are not emitted), or null.  In place (out == x) is allowed.
+struct LnEpsParams {
+    const float* x;
+    const float* pos = nullptr;  // (>= Tc, C) or null
+    int Tc = 1;
+    const float* gamma;
+    const float* beta;
+    float eps;
+    long rows;
+    int C;
+    float* out = nullptr;
+    float* out2 = nullptr;
+    int Tp = 1, T = 1;
+};
+hipError_t launch_layernorm_eps(const LnEpsParams& p, hipStream_t st);
+
 }  // namespace s3

@@ -581,4 +581,131 @@ int s3enc_fbank_forward_ex(const s3enc_fbank_config* cfg, int32_t window, const 
     return 0;
 }
 
+int s3enc_logmel_frame_counts(const int64_t* lengths, int32_t B, int64_t n_max, int32_t* counts) {
+    if (!lengths || !counts) return fail("s3enc_logmel_frame_counts: null argument");
+    if (B <= 0) return fail("s3enc_logmel_frame_counts: empty batch");
+    long mx = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] <= 0) return fail("s3enc_logmel_frame_counts: empty utterance");
+        mx = std::max(mx, (long)lengths[b]);
+    }
+    if (n_max > 0) {
+        if (n_max < mx) return fail("s3enc_logmel_frame_counts: n_max is smaller than the longest utterance");
+        mx = n_max;
+    }
+    for (int b = 0; b < B; ++b) counts[b] = logmel_frame_count(lengths[b], mx);
+    return 0;
+}
+
+int s3enc_logmel_forward(const float* const* wavs, const int64_t* lengths, int32_t B, int64_t n_max, int32_t n_mels,
+                         float target_level, int32_t cmvn, const int32_t* counts, float* out, int32_t device, void* stream) {
+    if (!wavs || !lengths || !out) return fail("s3enc_logmel_forward: null argument");
+    if (B <= 0 || B > 65535) return fail("s3enc_logmel_forward: bad batch size");
+    if (n_mels < 1 || n_mels > 256) return fail("s3enc_logmel_forward: n_mels must be in 1..256");
+    if (cmvn && !counts) return fail("s3enc_logmel_forward: cmvn needs the frame counts (s3enc_logmel_frame_counts)");
+    long mx = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!wavs[b]) return fail("s3enc_logmel_forward: null waveform pointer");
+        if (lengths[b] <= 200) return fail("s3enc_logmel_forward: an utterance of at most 200 samples has no reflect-padded centred frame");
+        mx = std::max(mx, (long)lengths[b]);
+    }
+    if (n_max > 0) {
+        if (n_max < mx) return fail("s3enc_logmel_forward: n_max is smaller than the longest utterance");
+        mx = n_max;
+    }
+    const long T = logmel_num_frames(mx);
+    if ((long)B * T > 0x7fffffffL / 402) return fail("s3enc_logmel_forward: batch too large");
+    for (int b = 0; cmvn && b < B; ++b)
+        if (counts[b] < 2 || counts[b] > T) return fail("s3enc_logmel_forward: every frame count must be in 2..T (the CMVN's standard deviation)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("s3enc_logmel_forward: no HIP device (there is no CPU fallback)");
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail("s3enc_logmel_forward: hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf tbl, scale, sig, spec;
+    const size_t o_len = (size_t)B * 8, o_cnt = 2 * (size_t)B * 8;
+    std::vector<char> host(o_cnt + (size_t)B * 4, 0);
+    for (int b = 0; b < B; ++b) {
+        ((const float**)host.data())[b] = wavs[b];
+        ((long*)(host.data() + o_len))[b] = (long)lengths[b];
+        ((int*)(host.data() + o_cnt))[b] = cmvn ? counts[b] : (int)T;
+    }
+    HIP_TRY(tbl.ensure(host.size()));
+    HIP_TRY(hipMemcpy(tbl.p, host.data(), host.size(), hipMemcpyHostToDevice));
+    HIP_TRY(scale.ensure((size_t)B * 4));
+    HIP_TRY(sig.ensure(logmel_sig_elems(B, mx) * 4));
+    HIP_TRY(spec.ensure(logmel_spec_elems(B, mx) * 4));
+    LogmelParams p{};
+    p.wavs = (const float* const*)tbl.p;
+    p.lens = (const long*)((char*)tbl.p + o_len);
+    p.counts = (const int*)((char*)tbl.p + o_cnt);
+    p.B = B;
+    p.max_len = mx;
+    p.n_mels = n_mels;
+    p.target_level = target_level;
+    p.cmvn = cmvn;
+    p.scale = (float*)scale.p;
+    p.sig = (float*)sig.p;
+    p.spec = (float*)spec.p;
+    p.out = out;
+    p.o_bs = T * n_mels;
+    HIP_TRY(launch_logmel(p, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the scratch is freed on return
+    return 0;
+}
+
+int s3enc_op_layernorm_eps(const float* x, const float* gamma, const float* beta, float eps, int64_t rows, int32_t C, float* out,
+                           void* stream) {
+    if (!x || !gamma || !beta || !out) return fail("s3enc_op_layernorm_eps: null argument");
+    if (rows <= 0 || C < 4 || (C & 3) || C > 2048) return fail("s3enc_op_layernorm_eps: bad shape (C a multiple of 4, at most 2048)");
+    if (!(eps >= 0.f)) return fail("s3enc_op_layernorm_eps: eps must not be negative");
+    LnEpsParams p;
+    p.x = x;
+    p.gamma = gamma;
+    p.beta = beta;
+    p.eps = eps;
+    p.rows = rows;
+    p.C = C;
+    p.out = out;
+    HIP_TRY(launch_layernorm_eps(p, (hipStream_t)stream));
+    return 0;
+}
+
+int s3enc_op_input_repr(const float* feat, const float* w, const float* bias, const float* pos_host, int32_t Tc, const float* gamma,
+                        const float* beta, float eps, int64_t rows, int32_t F, int32_t D, float* out, void* stream) {
+    if (!feat || !w || !bias || !pos_host || !gamma || !beta || !out) return fail("s3enc_op_input_repr: null argument");
+    if (rows <= 0 || rows > 0x7fffffffL / 4 || Tc < 1) return fail("s3enc_op_input_repr: bad shape");
+    if (F < 4 || (F & 3) || D < 4 || (D & 3) || D > 2048) return fail("s3enc_op_input_repr: F and D must be multiples of 4 (D at most 2048)");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf pos, tmp;
+    HIP_TRY(pos.ensure((size_t)Tc * D * 4));
+    HIP_TRY(hipMemcpy(pos.p, pos_host, (size_t)Tc * D * 4, hipMemcpyHostToDevice));
+    HIP_TRY(tmp.ensure((size_t)rows * D * 4));
+    GemmParams g{};
+    g.A = feat;
+    g.lda = F;
+    g.W = w;
+    g.bias = bias;
+    g.M = (int)rows;
+    g.N = D;
+    g.K = F;
+    g.batches = 1;
+    g.out32 = (float*)tmp.p;
+    g.ldo = D;
+    HIP_TRY(launch_gemm(F32, g, st));
+    LnEpsParams p;
+    p.x = (const float*)tmp.p;
+    p.pos = (const float*)pos.p;
+    p.Tc = Tc;
+    p.gamma = gamma;
+    p.beta = beta;
+    p.eps = eps;
+    p.rows = rows;
+    p.C = D;
+    p.out = out;
+    HIP_TRY(launch_layernorm_eps(p, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the position rows and the projection are freed on return
+    return 0;
+}
+
 }  // extern "C"

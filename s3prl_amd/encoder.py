@@ -34,6 +34,8 @@ class HipEncoder:
             raise ValueError(f"modified CPC is built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "apc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             raise ValueError(f"APC / VQ-APC are built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "mockingjay" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"Mockingjay / TERA / AudioALBERT are built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -68,6 +70,9 @@ class HipEncoder:
             elif cfg.family == "apc":  # its front end and GRU stack travel beside the (unchanged) s3enc_config
                 apc = _lib.make_apc_config(cfg)
                 rc = self._lib.s3enc_create_apc(C.byref(ccfg), C.byref(apc), tensors, len(weights), self.device, C.byref(h))
+            elif cfg.family == "mockingjay":  # its front end and input representation travel beside the (unchanged) s3enc_config
+                mj = _lib.make_mockingjay_config(cfg)
+                rc = self._lib.s3enc_create_mockingjay(C.byref(ccfg), C.byref(mj), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")
@@ -176,6 +181,11 @@ class HipEncoder:
         if self.cfg.family == "apc" and min(self.num_frames(n) for n in lengths) < 1:
             raise ValueError(f"an utterance of {min(lengths)} samples is shorter than one analysis window of the APC front end "
                              f"({self.cfg.conv_layers[0][1]} samples)")
+        if self.cfg.family == "mockingjay" and self.cfg.mj_frontend == "mel" and min(lengths) <= 200:
+            raise ValueError(f"an utterance of {min(lengths)} samples has no reflect-padded centred STFT frame (torch.stft refuses "
+                             "n <= 200 samples)")
+        if self.cfg.family == "mockingjay" and min(self.valid_frames(n, nm) for n in lengths) < 1:
+            raise ValueError(f"an utterance of {min(lengths)} samples is shorter than one analysis window of the front end")
         if self.num_frames(nm) < 1:
             raise ValueError(f"input of {nm} samples is shorter than the receptive field of the conv stack")
         T = self.num_output_frames(nm)

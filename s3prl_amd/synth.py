@@ -26,6 +26,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _cpc_shapes(cfg)
     if cfg.family == "apc":
         return _apc_shapes(cfg)
+    if cfg.family == "mockingjay":
+        return _mockingjay_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -198,6 +200,24 @@ def _apc_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         s[f"rnn_layers.{l}.weight_hh_l0"] = (3 * H, H)
         s[f"rnn_layers.{l}.bias_ih_l0"] = (3 * H,)
         s[f"rnn_layers.{l}.bias_hh_l0"] = (3 * H,)
+    return s
+
+
+def _mockingjay_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """TransformerModel (upstream/mockingjay/model.py:102-386), reference state_dict names of the checkpoint's ``Transformer``.
+    With ``share_layer`` the ModuleList holds one module under every index: only ``encoder.layer.0`` is a hot-path parameter."""
+    D, F = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim
+    s: Dict[str, tuple] = {"input_representations.spec_transform.weight": (D, cfg.mj_input_dim),
+                           "input_representations.spec_transform.bias": (D,),
+                           "input_representations.LayerNorm.weight": (D,), "input_representations.LayerNorm.bias": (D,)}
+    for l in range(1 if cfg.mj_share_layer else cfg.encoder_layers):
+        p = f"encoder.layer.{l}"
+        for n in ("attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense"):
+            s[f"{p}.{n}.weight"], s[f"{p}.{n}.bias"] = (D, D), (D,)
+        s[f"{p}.attention.output.LayerNorm.weight"], s[f"{p}.attention.output.LayerNorm.bias"] = (D,), (D,)
+        s[f"{p}.intermediate.dense.weight"], s[f"{p}.intermediate.dense.bias"] = (F, D), (F,)
+        s[f"{p}.output.dense.weight"], s[f"{p}.output.dense.bias"] = (D, F), (D,)
+        s[f"{p}.output.LayerNorm.weight"], s[f"{p}.output.LayerNorm.bias"] = (D,), (D,)
     return s
 
 
@@ -524,8 +544,29 @@ def named_config(name: str) -> EncoderConfig:
         from .config import apc_config
 
         return apc_config(**apc[name])
+    # Mockingjay / TERA / AudioALBERT: a log-mel (or kaldi fbank) front end into post-LN BERT layers, long inputs in chunks
+    tiny_mj = dict(hidden=128, layers=2, heads=2, intermediate=256, input_dim=16, sequence_length=0)
+    mj = {
+        "tiny_mockingjay": dict(**tiny_mj),
+        "tiny_mockingjay_chunk": dict(**{**tiny_mj, "sequence_length": 16}),
+        "tiny_mockingjay_chunk3": dict(**{**tiny_mj, "sequence_length": 3}),
+        "tiny_mockingjay_eps": dict(**tiny_mj, layer_norm_eps=1e-2),
+        "tiny_mockingjay_albert": dict(**{**tiny_mj, "layers": 3}, share_layer=True),
+        "tiny_mockingjay_kaldi": dict(**{**tiny_mj, "input_dim": 24}, frontend="kaldi", mj_kaldi_mel_bins=8, mj_delta_order=2),
+        # pretrain/{tera,mockingjay,audio_albert}/config_model*.yaml (a checkpoint's own config decides at load time)
+        "tera_base": dict(hidden=768, layers=3, heads=12, intermediate=3072, input_dim=80, sequence_length=1500),
+        "mockingjay_base": dict(hidden=768, layers=3, heads=12, intermediate=3072, input_dim=240, sequence_length=1500,
+                                frontend="kaldi"),
+        "mockingjay_large": dict(hidden=768, layers=12, heads=12, intermediate=3072, input_dim=80, sequence_length=500),
+        "audio_albert_base": dict(hidden=768, layers=3, heads=12, intermediate=3072, input_dim=80, sequence_length=1500,
+                                  share_layer=True),
+    }
+    if name in mj:
+        from .config import mockingjay_config
+
+        return mockingjay_config(**mj[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(mj))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
