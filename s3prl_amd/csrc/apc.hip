@@ -56,59 +56,11 @@ int apc_check_config(const s3enc_config& c, const s3enc_apc_config& x) {
     return 0;
 }
 
-namespace {
-struct ApcFetch {
-    std::map<std::string, const s3enc_tensor*> m;
-    int get(const std::string& name, long expect, std::vector<float>& out) const {
-        auto it = m.find(name);
-        if (it == m.end()) return fail("checkpoint is missing tensor '" + name + "'");
-        long n = 1;
-        for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
-        if (n != expect)
-            return fail("tensor '" + name + "' has " + std::to_string(n) + " elements, expected " + std::to_string(expect));
-        out.assign(it->second->data, it->second->data + expect);
-        return 0;
-    }
-};
-}  // namespace
-
-int apc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors) {
+int apc_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_apc_config& x = e->apc_cfg;
-    const int H = x.hidden, F = x.num_mel_bins, NL = x.num_layers;
-    ApcFetch ck;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name && tensors[i].data) ck.m[tensors[i].name] = &tensors[i];
     e->apc.reset(new ApcW());
-    ApcW& w = *e->apc;
-    std::vector<float> t, t2, t3;
-#define APC_GET(name, n, vec) \
-    if (ck.get(name, n, vec)) return 1
-#define APC_UP(buf, vec)                                                                       \
-    do {                                                                                       \
-        hipError_t _e = upload_f32(buf, vec);                                                  \
-        if (_e != hipSuccess) return fail(std::string("weight upload failed: ") + hipGetErrorString(_e)); \
-    } while (0)
-    w.w_ih.resize(NL);
-    w.b_pre.resize(NL);
-    w.w_hh.resize(NL);
-    w.b_hn.resize(NL);
-    for (int l = 0; l < NL; ++l) {
-        const std::string n = "rnn_layers." + std::to_string(l) + ".";
-        const int I = l == 0 ? F : H;
-        APC_GET(n + "weight_ih_l0", 3L * H * I, t);
-        APC_UP(w.w_ih[l], t);
-        APC_GET(n + "weight_hh_l0", 3L * H * H, t);
-        pack_rnn_whh(t.data(), 3, H, t2);
-        APC_UP(w.w_hh[l], t2);
-        APC_GET(n + "bias_ih_l0", 3L * H, t);
-        APC_GET(n + "bias_hh_l0", 3L * H, t2);
-        for (int i = 0; i < 2 * H; ++i) t[i] += t2[i];  // b_hn stays inside r * (W_hn h + b_hn)
-        APC_UP(w.b_pre[l], t);
-        t3.assign(t2.begin() + 2 * H, t2.end());
-        APC_UP(w.b_hn[l], t3);
-    }
-#undef APC_GET
-#undef APC_UP
+    for (int l = 0; l < x.num_layers; ++l)
+        if (load_rnn_layer(ck, "rnn_layers." + std::to_string(l) + ".", "_l0", 3, x.hidden, l == 0 ? x.num_mel_bins : x.hidden, *e->apc)) return 1;
     return 0;
 }
 
@@ -118,36 +70,24 @@ int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     const ApcW& w = *e->apc;
     const int H = x.hidden, F = x.num_mel_bins, NL = x.num_layers;
     const s3::FbankParams fp = apc_fbank_params(x);
-    if (B <= 0) return fail("s3enc_forward: B must be positive");
     if (fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: feature_selection is not defined for APC (the reference expert has one hidden_states list)");
     if (fo.featurize && !fo.w) return fail("s3enc_forward: featurize needs feat_w");
     if (!fo.featurize && fo.out_dtype != F32) return fail("s3enc_forward: out_dtype must be S3ENC_F32 for an APC handle");
     if (e->aux_codewords || e->aux_codeids) return fail("s3enc_forward_aux: codewords / codeids are outputs of a wav2vec handle with a vector quantizer");
     if (B > 65535) return fail("s3enc_forward: batch too large");
-    long n_max = 0;
+    long n_max;
+    if (batch_n_max(wav_ptrs_host, lengths, B, n_max_in, n_max)) return 1;
     std::vector<int> frames(B);
     for (int b = 0; b < B; ++b) {
-        if (lengths[b] <= 0) return fail("s3enc_forward: empty utterance");
-        if (lengths[b] > n_max) n_max = lengths[b];
-        if (!wav_ptrs_host[b]) return fail("s3enc_forward: null waveform pointer");
         const long tb = s3::fbank_num_frames(lengths[b], fp);
         if (tb < 1) return fail("s3enc_forward: an utterance is shorter than one analysis window (APC's front end keeps whole windows only)");
         frames[b] = (int)tb;
     }
-    if (n_max_in > 0) {
-        if (n_max_in < n_max) return fail("s3enc_forward: n_max is smaller than the longest utterance");
-        n_max = n_max_in;
-    }
     const long T = s3::fbank_num_frames(n_max, fp);
     const long M = (long)B * T;
     if (M > 0x7fffffffL) return fail("s3enc_forward: batch too large");
-    if (!out) return fail("s3enc_forward: null output");
-    if (!fo.featurize) {
-        if (layer_stride < M * H) return fail("s3enc_forward: layer_stride < B*T*D");
-        if (layer_stride & 3) return fail("s3enc_forward: layer_stride must be a multiple of 4 elements (vector stores)");
-    }
-    if ((uintptr_t)out & 15) return fail("s3enc_forward: out must be 16-byte aligned");
+    if (check_out(out, fo, layer_stride, M * H)) return 1;
     DeviceGuard dg(e->device);
     if (!dg.ok) return fail("s3enc_forward: hipSetDevice failed");
 
@@ -155,22 +95,10 @@ int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     const size_t tbl_bytes = (size_t)B * sizeof(int);
     HIP_TRY(e->small.ensure_on_stream(tbl_bytes + 1024, st));
     int* d_len = (int*)e->small.p;
-    if (tbl_bytes > e->slot_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (e->pinned) HIP_TRY(hipHostFree(e->pinned));
-        e->pinned = nullptr;
-        e->slot_bytes = tbl_bytes * 4 + 4096;
-        HIP_TRY(hipHostMalloc(&e->pinned, e->slot_bytes * s3enc_encoder::RING, hipHostMallocDefault));
-    }
-    {
-        const int slot = e->slot_next;
-        e->slot_next = (slot + 1) % s3enc_encoder::RING;
-        HIP_TRY(hipEventSynchronize(e->slot_ev[slot]));
-        char* hp = (char*)e->pinned + (size_t)slot * e->slot_bytes;
-        memcpy(hp, frames.data(), tbl_bytes);
-        HIP_TRY(hipMemcpyAsync(d_len, hp, tbl_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(e->slot_ev[slot], st));
-    }
+    char* hp;
+    if (stage_begin(e, tbl_bytes, st, hp)) return 1;
+    memcpy(hp, frames.data(), tbl_bytes);
+    if (stage_commit(e, hp, d_len, tbl_bytes, st)) return 1;
 
     // ---- workspace ----
     const bool feat_sum = fo.featurize;
@@ -189,24 +117,8 @@ int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     e->taps.clear();
 
     // ---- where the states go ----
-    bool first = true;
-    if (feat_sum && fo.w[0] == 0.f && fo.w[1] == 0.f && fo.w[2] == 0.f) HIP_TRY(hipMemsetAsync(out, 0, (size_t)M * H * 4, st));
-    auto emit = [&](int si, const float* state) -> hipError_t {  // featurize: the state's term of the weighted sum
-        if (!feat_sum || fo.w[si] == 0.f) return hipSuccess;
-        LnAcc a;
-        a.acc = (float*)out;
-        a.w = fo.w[si];
-        a.mode = 1;
-        a.norm = fo.feat_norm;
-        a.init = first;
-        first = false;
-        Prof pr(e, st, "emit_state", 0, 4.0 * M * H * 2);
-        return launch_emit_state(F32, state, M, H, nullptr, a, st);
-    };
-    auto done = [&](int si) -> hipError_t {
-        if (feat_sum || e->layer_events.empty() || si >= (int)e->layer_events.size()) return hipSuccess;
-        return hipEventRecord(e->layer_events[si], st);
-    };
+    Sink sink{e, st, feat_sum ? 2 : 0, out, (long)layer_stride, F32, M, H, fo.w, fo.feat_norm};
+    HIP_TRY(sink.zero_without_terms(3, M));
 
     // ---- front end: (B, T, F), zeros behind every utterance's frames (pad_sequence) ----
     {
@@ -235,7 +147,7 @@ int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
             Prof pr(e, st, "gemm:apc_in", 2.0 * M * 3 * H * I, 4.0 * ((double)M * I + 3.0 * H * I + (double)M * 3 * H));
             HIP_TRY(launch_gemm(F32, g, st));
         }
-        float* hout = (si >= 0 && !feat_sum) ? (float*)out + (long)si * layer_stride : hb[l];
+        float* hout = sink.slot32(si) ? sink.slot32(si) : hb[l];
         RnnLenParams r{};
         r.cell = 1;
         r.pre = pre;
@@ -263,10 +175,11 @@ int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
                 HIP_TRY(launch_rnn_len(r, st));
             }
         }
-        if (si >= 0) {
-            HIP_TRY(emit(si, hout));
-            HIP_TRY(done(si));
+        if (sink.term(si)) {  // featurize: the state's term of the weighted sum
+            Prof pr(e, st, "emit_state", 0, 4.0 * M * H * 2);
+            HIP_TRY(sink.emit(si, hout));
         }
+        HIP_TRY(sink.done(si));
         xin = hout;
         I = H;
     }

@@ -223,39 +223,13 @@ int cpc_check_config(const s3enc_config& c, const s3enc_cpc_config& x) {
     return 0;
 }
 
-namespace {
-struct CpcFetch {
-    std::map<std::string, const s3enc_tensor*> m;
-    int get(const std::string& name, long expect, std::vector<float>& out) const {
-        auto it = m.find(name);
-        if (it == m.end()) return fail("checkpoint is missing tensor '" + name + "'");
-        long n = 1;
-        for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
-        if (n != expect)
-            return fail("tensor '" + name + "' has " + std::to_string(n) + " elements, expected " + std::to_string(expect));
-        out.assign(it->second->data, it->second->data + expect);
-        return 0;
-    }
-};
-}  // namespace
-
-int cpc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors) {
+int cpc_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_config& c = e->cfg;
     const s3enc_cpc_config& x = e->cpc_cfg;
     const int C = c.conv_dim, H = x.ar_hidden, G = x.ar_mode == 0 ? 4 : 3;
-    CpcFetch ck;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name && tensors[i].data) ck.m[tensors[i].name] = &tensors[i];
     e->cpc.reset(new CpcW());
     CpcW& w = *e->cpc;
-    std::vector<float> t, t2, t3;
-#define CPC_GET(name, n, vec) \
-    if (ck.get(name, n, vec)) return 1
-#define CPC_UP(buf, vec)                                                                       \
-    do {                                                                                       \
-        hipError_t _e = upload_f32(buf, vec);                                                  \
-        if (_e != hipSuccess) return fail(std::string("weight upload failed: ") + hipGetErrorString(_e)); \
-    } while (0)
+    std::vector<float> t, t2;
     w.conv_w.resize(c.n_conv);
     w.conv_b.resize(c.n_conv);
     w.cn_g.resize(c.n_conv);
@@ -263,48 +237,22 @@ int cpc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors) {
     for (int i = 0; i < c.n_conv; ++i) {
         const std::string n = std::to_string(i);
         const int cin = i == 0 ? 1 : C, k = c.conv_kernel[i];
-        CPC_GET("gEncoder.conv" + n + ".weight", (long)C * cin * k, t);
+        GET("gEncoder.conv" + n + ".weight", (long)C * cin * k, t);
         if (i == 0) {
-            CPC_UP(w.conv_w[i], t);  // [C][10]
-        } else {  // (Cout, Cin, k) -> [co][j * Cin + ci]: the K order of the channel-last implicit GEMM
-            t2.resize(t.size());
-            for (int co = 0; co < C; ++co)
-                for (int ci = 0; ci < C; ++ci)
-                    for (int j = 0; j < k; ++j) t2[((long)co * k + j) * C + ci] = t[((long)co * C + ci) * k + j];
-            CPC_UP(w.conv_w[i], t2);
+            UP(upload_f32(w.conv_w[i], t));  // [C][10]
+        } else {
+            tap_major(t, C, C, k, t2);
+            UP(upload_f32(w.conv_w[i], t2));
         }
-        CPC_GET("gEncoder.conv" + n + ".bias", C, t);
-        CPC_UP(w.conv_b[i], t);
-        CPC_GET("gEncoder.batchNorm" + n + ".weight", C, t);  // (1, C, 1)
-        CPC_UP(w.cn_g[i], t);
-        CPC_GET("gEncoder.batchNorm" + n + ".bias", C, t);
-        CPC_UP(w.cn_b[i], t);
+        GET("gEncoder.conv" + n + ".bias", C, t);
+        UP(upload_f32(w.conv_b[i], t));
+        GET("gEncoder.batchNorm" + n + ".weight", C, t);  // (1, C, 1)
+        UP(upload_f32(w.cn_g[i], t));
+        GET("gEncoder.batchNorm" + n + ".bias", C, t);
+        UP(upload_f32(w.cn_b[i], t));
     }
-    w.w_ih.resize(x.ar_layers);
-    w.b_pre.resize(x.ar_layers);
-    w.w_hh.resize(x.ar_layers);
-    w.b_hn.resize(x.ar_layers);
-    for (int l = 0; l < x.ar_layers; ++l) {
-        const std::string n = "_l" + std::to_string(l);
-        CPC_GET("gAR.baseNet.weight_ih" + n, (long)G * H * H, t);  // layer 0 reads the encoder output: C == H
-        CPC_UP(w.w_ih[l], t);
-        CPC_GET("gAR.baseNet.weight_hh" + n, (long)G * H * H, t);
-        pack_rnn_whh(t.data(), G, H, t2);
-        CPC_UP(w.w_hh[l], t2);
-        CPC_GET("gAR.baseNet.bias_ih" + n, (long)G * H, t);
-        CPC_GET("gAR.baseNet.bias_hh" + n, (long)G * H, t2);
-        // the input projection's bias: b_ih plus the part of b_hh outside a product — all of it for an LSTM, the r and z parts for
-        // a GRU (b_hn stays inside r * (W_hn h + b_hn))
-        const int fold = x.ar_mode == 0 ? G * H : 2 * H;
-        for (int i = 0; i < fold; ++i) t[i] += t2[i];
-        CPC_UP(w.b_pre[l], t);
-        if (x.ar_mode == 1) {
-            t3.assign(t2.begin() + 2 * H, t2.end());
-            CPC_UP(w.b_hn[l], t3);
-        }
-    }
-#undef CPC_GET
-#undef CPC_UP
+    for (int l = 0; l < x.ar_layers; ++l)  // layer 0 reads the encoder output: C == H
+        if (load_rnn_layer(ck, "gAR.baseNet.", "_l" + std::to_string(l), G, H, H, w)) return 1;
     return 0;
 }
 
@@ -314,34 +262,20 @@ int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     const s3enc_cpc_config& x = e->cpc_cfg;
     const CpcW& w = *e->cpc;
     const int C = c.conv_dim, H = x.ar_hidden, G = x.ar_mode == 0 ? 4 : 3, NC = c.n_conv, NL = x.ar_layers;
-    if (B <= 0) return fail("s3enc_forward: B must be positive");
     if (fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: feature_selection is not defined for modified CPC (the reference expert has one hidden_states list)");
     if (fo.featurize && !fo.w) return fail("s3enc_forward: featurize needs feat_w");
     if (!fo.featurize && fo.out_dtype != F32) return fail("s3enc_forward: out_dtype must be S3ENC_F32 for a modified-CPC handle");
     if (e->aux_codewords || e->aux_codeids) return fail("s3enc_forward_aux: codewords / codeids are outputs of a wav2vec handle with a vector quantizer");
-    long n_max = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] <= 0) return fail("s3enc_forward: empty utterance");
-        if (lengths[b] > n_max) n_max = lengths[b];
-        if (!wav_ptrs_host[b]) return fail("s3enc_forward: null waveform pointer");
-    }
-    if (n_max_in > 0) {
-        if (n_max_in < n_max) return fail("s3enc_forward: n_max is smaller than the longest utterance");
-        n_max = n_max_in;
-    }
+    long n_max;
+    if (batch_n_max(wav_ptrs_host, lengths, B, n_max_in, n_max)) return 1;
     std::vector<long> L(NC);
     for (int i = 0; i < NC; ++i) L[i] = cpc_conv_len(c, x, n_max, i + 1);
     const long T = L[NC - 1];
     if (T < 1) return fail("s3enc_forward: input shorter than the receptive field of the conv stack (modified CPC needs 159 samples)");
     const long M = (long)B * T;
     if (B > 65535) return fail("s3enc_forward: batch too large");
-    if (!out) return fail("s3enc_forward: null output");
-    if (!fo.featurize) {
-        if (layer_stride < M * C) return fail("s3enc_forward: layer_stride < B*T*D");
-        if (layer_stride & 3) return fail("s3enc_forward: layer_stride must be a multiple of 4 elements (vector stores)");
-    }
-    if ((uintptr_t)out & 15) return fail("s3enc_forward: out must be 16-byte aligned");
+    if (check_out(out, fo, layer_stride, M * C)) return 1;
     // operand i (i = 1 .. NC - 1): conv i's input, (B, pad_i + L[i-1] + pad_i, C)
     long op_max = 0, raw_max = 0;
     for (int i = 1; i < NC; ++i) {
@@ -356,23 +290,11 @@ int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     const size_t tbl_bytes = (size_t)B * 16;
     HIP_TRY(e->small.ensure_on_stream(tbl_bytes + 1024, st));
     char* d_tbl = (char*)e->small.p;
-    if (tbl_bytes > e->slot_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (e->pinned) HIP_TRY(hipHostFree(e->pinned));
-        e->pinned = nullptr;
-        e->slot_bytes = tbl_bytes * 4 + 4096;
-        HIP_TRY(hipHostMalloc(&e->pinned, e->slot_bytes * s3enc_encoder::RING, hipHostMallocDefault));
-    }
-    {
-        const int slot = e->slot_next;
-        e->slot_next = (slot + 1) % s3enc_encoder::RING;
-        HIP_TRY(hipEventSynchronize(e->slot_ev[slot]));
-        char* hp = (char*)e->pinned + (size_t)slot * e->slot_bytes;
-        memcpy(hp, wav_ptrs_host, (size_t)B * 8);
-        for (int b = 0; b < B; ++b) ((long*)(hp + (size_t)B * 8))[b] = (long)lengths[b];
-        HIP_TRY(hipMemcpyAsync(d_tbl, hp, tbl_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(e->slot_ev[slot], st));
-    }
+    char* hp;
+    if (stage_begin(e, tbl_bytes, st, hp)) return 1;
+    memcpy(hp, wav_ptrs_host, (size_t)B * 8);
+    for (int b = 0; b < B; ++b) ((long*)(hp + (size_t)B * 8))[b] = (long)lengths[b];
+    if (stage_commit(e, hp, d_tbl, tbl_bytes, st)) return 1;
     WavTable wt{(const float* const*)d_tbl, (const long*)(d_tbl + (size_t)B * 8), B, n_max};
 
     // ---- workspace ----
@@ -391,25 +313,8 @@ int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     e->taps.clear();
 
     // ---- where the states go ----
-    const bool feat = fo.featurize;
-    bool first = true;
-    if (feat && fo.w[0] == 0.f && fo.w[1] == 0.f) HIP_TRY(hipMemsetAsync(out, 0, (size_t)M * C * 4, st));
-    auto emit = [&](int si, const float* state) -> hipError_t {  // featurize: the state's term of the weighted sum
-        if (!feat || fo.w[si] == 0.f) return hipSuccess;
-        LnAcc a;
-        a.acc = (float*)out;
-        a.w = fo.w[si];
-        a.mode = 1;
-        a.norm = fo.feat_norm;
-        a.init = first;
-        first = false;
-        Prof pr(e, st, "emit_state", 0, 4.0 * M * C * 2);
-        return launch_emit_state(F32, state, M, C, nullptr, a, st);
-    };
-    auto done = [&](int si) -> hipError_t {
-        if (feat || e->layer_events.empty() || si >= (int)e->layer_events.size()) return hipSuccess;
-        return hipEventRecord(e->layer_events[si], st);
-    };
+    Sink sink{e, st, fo.featurize ? 2 : 0, out, (long)layer_stride, F32, M, C, fo.w, fo.feat_norm};
+    HIP_TRY(sink.zero_without_terms(2, M));
 
     // ---- conv0 into conv1's zero-bordered operand ----
     {
@@ -430,7 +335,7 @@ int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     }
     // ---- conv1..: implicit GEMM on the bordered rows, then ChannelNorm + ReLU into the next operand ----
     float* cur = opA;
-    float* state0 = feat ? enc : (float*)out;
+    float* state0 = sink.slot32(0) ? sink.slot32(0) : enc;
     for (int i = 1; i < NC; ++i) {
         const bool last = i == NC - 1;
         const int k = c.conv_kernel[i], pad = x.conv_pad[i];
@@ -473,8 +378,11 @@ int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
         }
         cur = nxt;
     }
-    HIP_TRY(emit(0, state0));
-    HIP_TRY(done(0));
+    if (sink.term(0)) {  // featurize: the state's term of the weighted sum
+        Prof pr(e, st, "emit_state", 0, 4.0 * M * C * 2);
+        HIP_TRY(sink.emit(0, state0));
+    }
+    HIP_TRY(sink.done(0));
 
     // ---- recurrent layers ----
     const float* xin = state0;
@@ -495,7 +403,7 @@ int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
             Prof pr(e, st, "gemm:cpc_ar_in", 2.0 * M * G * H * H, 4.0 * ((double)M * H + (double)G * H * H + (double)M * G * H));
             HIP_TRY(launch_gemm(F32, g, st));
         }
-        float* hout = (last && !feat) ? (float*)out + layer_stride : ((l & 1) ? hB : hA);
+        float* hout = (last && sink.slot32(1)) ? sink.slot32(1) : ((l & 1) ? hB : hA);
         RnnParams r{};
         r.cell = x.ar_mode;
         r.pre = pre;
@@ -513,8 +421,11 @@ int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
         }
         xin = hout;
     }
-    HIP_TRY(emit(1, xin));
-    HIP_TRY(done(1));
+    if (sink.term(1)) {  // featurize: the state's term of the weighted sum
+        Prof pr(e, st, "emit_state", 0, 4.0 * M * C * 2);
+        HIP_TRY(sink.emit(1, xin));
+    }
+    HIP_TRY(sink.done(1));
     return 0;
 }
 

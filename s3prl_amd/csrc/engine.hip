@@ -38,36 +38,98 @@ int num_states(const s3enc_config& c, int selection) {
     if (selection == S3ENC_SEL_HIDDEN) return c.encoder_layers + 1 + (c.family == S3ENC_DISTILLER ? c.pred_heads : 0);
     return c.encoder_layers;
 }
+
+// ---- the plumbing every family shares (engine_internal.h) ----------------------------------------------------------------------------
+int Ckpt::get(const std::string& name, long expect, std::vector<float>& out) const {
+    auto it = m.find(name);
+    if (it == m.end()) return fail("checkpoint is missing tensor '" + name + "'");
+    long n = 1;
+    for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
+    if (n != expect) return fail("tensor '" + name + "' has " + std::to_string(n) + " elements, expected " + std::to_string(expect));
+    out.assign(it->second->data, it->second->data + expect);
+    return 0;
+}
+
+void tap_major(const std::vector<float>& t, int cout, int cin, int k, std::vector<float>& o) {
+    o.resize(t.size());
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int j = 0; j < k; ++j) o[((long)co * k + j) * cin + ci] = t[((long)co * cin + ci) * k + j];
+}
+
+int load_rnn_layer(const Ckpt& ck, const std::string& prefix, const std::string& suffix, int G, int H, int I, RnnW& w) {
+    std::vector<float> t, t2;
+    w.w_ih.emplace_back();
+    w.w_hh.emplace_back();
+    w.b_pre.emplace_back();
+    w.b_hn.emplace_back();
+    GET(prefix + "weight_ih" + suffix, (long)G * H * I, t);
+    UP(upload_f32(w.w_ih.back(), t));
+    GET(prefix + "weight_hh" + suffix, (long)G * H * H, t);
+    pack_rnn_whh(t.data(), G, H, t2);
+    UP(upload_f32(w.w_hh.back(), t2));
+    GET(prefix + "bias_ih" + suffix, (long)G * H, t);
+    GET(prefix + "bias_hh" + suffix, (long)G * H, t2);
+    // the input projection's bias: b_ih plus the part of b_hh outside a product — all of it for an LSTM, the r and z parts for
+    // a GRU (b_hn stays inside r * (W_hn h + b_hn))
+    const int fold = G == 4 ? G * H : 2 * H;
+    for (int i = 0; i < fold; ++i) t[i] += t2[i];
+    UP(upload_f32(w.b_pre.back(), t));
+    if (G == 3) {
+        t.assign(t2.begin() + 2 * H, t2.end());
+        UP(upload_f32(w.b_hn.back(), t));
+    }
+    return 0;
+}
+
+int batch_n_max(const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in, long& n_max) {
+    if (B <= 0) return fail("s3enc_forward: B must be positive");
+    n_max = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] <= 0) return fail("s3enc_forward: empty utterance");
+        if (lengths[b] > n_max) n_max = lengths[b];
+        if (!wav_ptrs_host[b]) return fail("s3enc_forward: null waveform pointer");
+    }
+    if (n_max_in > 0) {
+        if (n_max_in < n_max) return fail("s3enc_forward: n_max is smaller than the longest utterance");
+        n_max = n_max_in;
+    }
+    return 0;
+}
+
+int check_out(const void* out, const FwdOpts& fo, int64_t layer_stride, long min_stride) {
+    if (!out) return fail("s3enc_forward: null output");
+    if (!fo.featurize) {
+        if (layer_stride < min_stride) return fail("s3enc_forward: layer_stride < B*T*D");
+        if (layer_stride & 3) return fail("s3enc_forward: layer_stride must be a multiple of 4 elements (vector stores)");
+    }
+    if ((uintptr_t)out & 15) return fail("s3enc_forward: out must be 16-byte aligned");
+    return 0;
+}
+
+int stage_begin(s3enc_encoder* e, size_t bytes, hipStream_t st, char*& hp) {
+    if (bytes > e->slot_bytes) {
+        HIP_TRY(hipStreamSynchronize(st));
+        if (e->pinned) HIP_TRY(hipHostFree(e->pinned));
+        e->pinned = nullptr;
+        e->slot_bytes = bytes * 4 + 4096;
+        HIP_TRY(hipHostMalloc(&e->pinned, e->slot_bytes * s3enc_encoder::RING, hipHostMallocDefault));
+    }
+    const int slot = e->slot_next;
+    e->slot_next = (slot + 1) % s3enc_encoder::RING;
+    HIP_TRY(hipEventSynchronize(e->slot_ev[slot]));
+    hp = (char*)e->pinned + (size_t)slot * e->slot_bytes;
+    return 0;
+}
+int stage_commit(s3enc_encoder* e, const char* hp, void* dst, size_t bytes, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(dst, hp, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(e->slot_ev[(hp - (const char*)e->pinned) / e->slot_bytes], st));
+    return 0;
+}
 }  // namespace s3e
 
 namespace {
 
-// ---- checkpoint lookup ---------------------------------------------------------------------------------------
-struct Ckpt {
-    std::map<std::string, const s3enc_tensor*> m;
-    const s3enc_tensor* get(const std::string& n) const {
-        auto it = m.find(n);
-        return it == m.end() ? nullptr : it->second;
-    }
-};
-long numel(const s3enc_tensor* t) {
-    long n = 1;
-    for (int i = 0; i < t->ndim; ++i) n *= t->shape[i];
-    return n;
-}
-bool fetch(const Ckpt& c, const std::string& name, long expect, std::vector<float>& out, std::string& err) {
-    const s3enc_tensor* t = c.get(name);
-    if (!t) {
-        err = "checkpoint is missing tensor '" + name + "'";
-        return false;
-    }
-    if (numel(t) != expect) {
-        err = "tensor '" + name + "' has " + std::to_string(numel(t)) + " elements, expected " + std::to_string(expect);
-        return false;
-    }
-    out.assign(t->data, t->data + expect);
-    return true;
-}
 // WavLM bucket table (wavlm/modules.py:418-462): table[h][rel + R] = E[bucket(rel)][h] for rel = key - query in [-R, R]
 void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R, std::vector<float>& table) {
     const int H = c.heads, nb = c.num_buckets / 2, max_exact = nb / 2;
@@ -152,23 +214,38 @@ int check_config(const s3enc_config& c) {
 }  // namespace
 
 // the handle's own device state behind the weights: staging-ring events and the status word of s3enc_forward_status
-static int finish_create(s3enc_encoder* e, s3enc_handle* out) {
-    for (int i = 0; i < s3enc_encoder::RING; ++i) {
-        if (hipEventCreateWithFlags(&e->slot_ev[i], hipEventDisableTiming) != hipSuccess) {
-            delete e;
-            return fail("hipEventCreate failed");
-        }
-    }
+static int finish_create(std::unique_ptr<s3enc_encoder> e, s3enc_handle* out) {
+    for (int i = 0; i < s3enc_encoder::RING; ++i)
+        if (hipEventCreateWithFlags(&e->slot_ev[i], hipEventDisableTiming) != hipSuccess) return fail("hipEventCreate failed");
     // the status word of s3enc_forward_status: device int + pinned host copy + the event behind the copy
     bool st_ok = e->status_dev.ensure(64) == hipSuccess && hipMemset(e->status_dev.p, 0, 64) == hipSuccess &&
                  hipHostMalloc((void**)&e->status_host, s3enc_encoder::STATUS_RING * sizeof(int), hipHostMallocDefault) == hipSuccess;
     for (int i = 0; st_ok && i < s3enc_encoder::STATUS_RING; ++i)
         st_ok = hipEventCreateWithFlags(&e->status_ev[i], hipEventDisableTiming) == hipSuccess;
-    if (!st_ok) {
-        delete e;
-        return fail("s3enc_create: status word allocation failed");
-    }
-    *out = e;
+    if (!st_ok) return fail("s3enc_create: status word allocation failed");
+    *out = e.release();
+    return 0;
+}
+
+// The families that come with a second configuration block, each through the entry point that takes it.  `own`: the family whose
+// block the calling entry takes (-1: none).  An entry refuses the families whose entry was added after it by name (`entry` prefixes
+// those refusals), and any other family than its own as not its block's.
+static int wrong_entry(const char* entry, int own, int family) {
+    static const struct {
+        int family;
+        const char *block, *name, *entry, *needs;
+    } F[] = {
+        {S3ENC_WAV2VEC, "wav2vec", "S3ENC_WAV2VEC", "s3enc_create_ex", "the wav2vec family needs its aggregator / quantizer block"},
+        {S3ENC_CPC, "cpc", "S3ENC_CPC", "s3enc_create_cpc", "the modified-CPC family needs its padding / recurrent-network block"},
+        {S3ENC_APC, "apc", "S3ENC_APC", "s3enc_create_apc", "the APC family needs its front-end / GRU block"},
+        {S3ENC_MOCKINGJAY, "mockingjay", "S3ENC_MOCKINGJAY", "s3enc_create_mockingjay",
+         "the Mockingjay / TERA / AudioALBERT family needs its front-end block"},
+    };
+    if (family == own) return 0;
+    for (const auto& f : F)
+        if (f.family == family && family > own) return fail(std::string(entry) + ": " + f.needs + ": use " + f.entry);
+    for (const auto& f : F)
+        if (f.family == own) return fail(std::string(f.entry) + ": the " + f.block + " block belongs to family " + f.name + " only");
     return 0;
 }
 
@@ -182,76 +259,55 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out,
-                       const s3enc_mockingjay_config* mj = nullptr);
+                       const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
+                       int32_t device, s3enc_handle* out);
 
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out) {
-    if (cfg && cfg->family == S3ENC_CPC) {
+    if (cfg && cfg->family > S3ENC_WAV2VEC && wrong_entry("s3enc_create", -1, cfg->family)) {  // a later family: needs its own entry
         if (out) *out = nullptr;
-        return fail("s3enc_create: the modified-CPC family needs its padding / recurrent-network block: use s3enc_create_cpc");
+        return 1;
     }
-    if (cfg && cfg->family == S3ENC_APC) {
-        if (out) *out = nullptr;
-        return fail("s3enc_create: the APC family needs its front-end / GRU block: use s3enc_create_apc");
-    }
-    if (cfg && cfg->family == S3ENC_MOCKINGJAY) {
-        if (out) *out = nullptr;
-        return fail("s3enc_create: the Mockingjay / TERA / AudioALBERT family needs its front-end block: use s3enc_create_mockingjay");
-    }
-    return create_impl(cfg, w2v, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, w2v, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out) {
     if (!cfg || !cpc || !tensors || !out) return fail("s3enc_create_cpc: null argument");
     *out = nullptr;
-    if (cfg->family == S3ENC_APC) return fail("s3enc_create_cpc: the APC family needs its front-end / GRU block: use s3enc_create_apc");
-    if (cfg->family == S3ENC_MOCKINGJAY)
-        return fail("s3enc_create_cpc: the Mockingjay / TERA / AudioALBERT family needs its front-end block: use s3enc_create_mockingjay");
-    if (cfg->family != S3ENC_CPC) return fail("s3enc_create_cpc: the cpc block belongs to family S3ENC_CPC only");
-    return create_impl(cfg, nullptr, cpc, nullptr, tensors, n_tensors, device, out);
+    if (wrong_entry("s3enc_create_cpc", S3ENC_CPC, cfg->family)) return 1;
+    return create_impl(cfg, nullptr, cpc, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out) {
     if (!cfg || !apc || !tensors || !out) return fail("s3enc_create_apc: null argument");
     *out = nullptr;
-    if (cfg->family == S3ENC_MOCKINGJAY)
-        return fail("s3enc_create_apc: the Mockingjay / TERA / AudioALBERT family needs its front-end block: use s3enc_create_mockingjay");
-    if (cfg->family != S3ENC_APC) return fail("s3enc_create_apc: the apc block belongs to family S3ENC_APC only");
-    return create_impl(cfg, nullptr, nullptr, apc, tensors, n_tensors, device, out);
+    if (wrong_entry("s3enc_create_apc", S3ENC_APC, cfg->family)) return 1;
+    return create_impl(cfg, nullptr, nullptr, apc, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
                             int32_t device, s3enc_handle* out) {
     if (!cfg || !mj || !tensors || !out) return fail("s3enc_create_mockingjay: null argument");
     *out = nullptr;
-    if (cfg->family != S3ENC_MOCKINGJAY) return fail("s3enc_create_mockingjay: the mockingjay block belongs to family S3ENC_MOCKINGJAY only");
-    return create_impl(cfg, nullptr, nullptr, nullptr, tensors, n_tensors, device, out, mj);
+    if (wrong_entry("s3enc_create_mockingjay", S3ENC_MOCKINGJAY, cfg->family)) return 1;
+    return create_impl(cfg, nullptr, nullptr, nullptr, mj, tensors, n_tensors, device, out);
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out,
-                       const s3enc_mockingjay_config* mj) {
+                       const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
+                       int32_t device, s3enc_handle* out) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
-    if (cfg->family == S3ENC_CPC) {
-        if (cpc_check_config(*cfg, *cpc)) return 1;
-    }
-    if (cfg->family == S3ENC_APC) {
-        if (apc_check_config(*cfg, *apc)) return 1;
-    }
-    if (cfg->family == S3ENC_MOCKINGJAY) {
-        if (!mj) return fail("s3enc_create: the Mockingjay / TERA / AudioALBERT family needs its front-end block: use s3enc_create_mockingjay");
-        if (mj_check_config(*cfg, *mj)) return 1;
-    }
-    if (cfg->family == S3ENC_WAV2VEC) {
-        if (!w2v) return fail("s3enc_create: the wav2vec family needs its aggregator / quantizer block: use s3enc_create_ex");
-        if (wav2vec_check_config(W2vCfg(*cfg, *w2v))) return 1;
-    } else if (w2v) {
-        return fail("s3enc_create_ex: the wav2vec block belongs to family S3ENC_WAV2VEC only");
+    // s3enc_create_ex: a wav2vec block with another family, the wav2vec family without its block
+    if ((w2v || cfg->family == S3ENC_WAV2VEC) && wrong_entry("s3enc_create", w2v ? S3ENC_WAV2VEC : -1, cfg->family)) return 1;
+    switch (cfg->family) {  // (the entry points have refused every other family that came without its own block)
+        case S3ENC_WAV2VEC: if (wav2vec_check_config(W2vCfg(*cfg, *w2v))) return 1; break;
+        case S3ENC_CPC: if (cpc_check_config(*cfg, *cpc)) return 1; break;
+        case S3ENC_APC: if (apc_check_config(*cfg, *apc)) return 1; break;
+        case S3ENC_MOCKINGJAY: if (mj_check_config(*cfg, *mj)) return 1; break;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -264,68 +320,27 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(std::string("s3enc_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
 
-    Ckpt ck;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name && tensors[i].data) ck.m[tensors[i].name] = &tensors[i];
-
-    s3enc_encoder* e = new s3enc_encoder();
+    const Ckpt ck(tensors, n_tensors);
+    std::unique_ptr<s3enc_encoder> e(new s3enc_encoder());  // (freed on every failing path below)
     e->cfg = *cfg;
     e->device = device;
     e->x3 = cfg->compute_dtype == 3;  // S3ENC_F32X3: the fp32 data flow, GEMMs through gemm_x3.hip
     e->x2 = cfg->compute_dtype == 4;  // S3ENC_F16X2: the fp16 data flow, GEMM weights split into two fp16 terms
     e->dtype = e->x3 ? (int)F32 : (e->x2 ? (int)F16 : cfg->compute_dtype);
     e->es = e->dtype == F32 ? 4 : 2;
-    if (cfg->family == S3ENC_WAV2VEC) {
-        e->w2v_cfg = *w2v;
-        if (wav2vec_create(e, tensors, n_tensors)) {
-            delete e;
-            return 1;
-        }
-        return finish_create(e, out);
+    int family_rc = -1;  // stays -1 for the Transformer families, whose weights are packed below
+    switch (cfg->family) {
+        case S3ENC_WAV2VEC: e->w2v_cfg = *w2v; family_rc = wav2vec_create(e.get(), ck); break;
+        case S3ENC_CPC: e->cpc_cfg = *cpc; family_rc = cpc_create(e.get(), ck); break;
+        case S3ENC_APC: e->apc_cfg = *apc; family_rc = apc_create(e.get(), ck); break;
+        case S3ENC_MOCKINGJAY: e->mj_cfg = *mj; family_rc = mj_create(e.get(), ck); break;
     }
-    if (cfg->family == S3ENC_CPC) {
-        e->cpc_cfg = *cpc;
-        if (cpc_create(e, tensors, n_tensors)) {
-            delete e;
-            return 1;
-        }
-        return finish_create(e, out);
-    }
-    if (cfg->family == S3ENC_APC) {
-        e->apc_cfg = *apc;
-        if (apc_create(e, tensors, n_tensors)) {
-            delete e;
-            return 1;
-        }
-        return finish_create(e, out);
-    }
-    if (cfg->family == S3ENC_MOCKINGJAY) {
-        e->mj_cfg = *mj;
-        if (mj_create(e, tensors, n_tensors)) {
-            delete e;
-            return 1;
-        }
-        return finish_create(e, out);
-    }
+    if (family_rc >= 0) return family_rc ? 1 : finish_create(std::move(e), out);
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads;
     const bool multires = c.family == S3ENC_MULTIRES;
     const std::string enc0 = multires ? "encoders.0" : "encoder";  // only the first block keeps its positional conv
-    std::string err;
     std::vector<float> t, t2;
-#define GET(name, n, vec)                  \
-    if (!fetch(ck, name, n, vec, err)) {   \
-        delete e;                          \
-        return fail(err);                  \
-    }
-#define UP(call)                                                     \
-    do {                                                             \
-        hipError_t _e = (call);                                      \
-        if (_e != hipSuccess) {                                      \
-            delete e;                                                \
-            return fail(std::string("weight upload failed: ") + hipGetErrorString(_e)); \
-        }                                                            \
-    } while (0)
 
     // a GEMM weight in the handle's operand format; S3ENC_F16X2: + the MX-fp4 image of its lo term for the weights gemm16.hip's MXW K
     // step pays for (gemm16_mx_weight_rule: decided per weight, never per batch; wsplit_of finds the image by the weight's pointer).
@@ -366,11 +381,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         if (i == 0) {
             UP(upload_f32(e->conv[i].w, t));  // [C][k]
         } else {
-            // re-lay (Cout, Cin, k) tap-major: W'[co][j*Cin + ci], the K order of the channel-last implicit GEMM
-            t2.resize(t.size());
-            for (int co = 0; co < C; ++co)
-                for (int ci = 0; ci < cin; ++ci)
-                    for (int j = 0; j < k; ++j) t2[((long)co * k + j) * cin + ci] = t[((long)co * cin + ci) * k + j];
+            tap_major(t, C, cin, k, t2);  // W'[co][j*Cin + ci], the K order of the channel-last implicit GEMM
             if (e->x2_conv_f32_from && i >= e->x2_conv_f32_from) {
                 UP(upload_gemm_w(e->conv[i].w, t2, C, (long)k * cin, e->dtype, e->x2));  // (read only if the three-term path declines)
             } else {
@@ -491,7 +502,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
     // of the weight to the operand type either way.  The exact-fp32 and split-precision handles keep the power-of-two scale.
     const float qscale = (1.0f / std::sqrt((float)(D / H))) * (e->dtype != F32 ? 1.44269504088896340736f : 1.0f);
     e->x2_attn_f32 = e->x2 && !multires && x3_shape_ok(D, D, D);  // (the U-net keeps 16-bit)
-    // one TransformerSentenceEncoderLayer named `p` (…layers.N); returns non-zero after fail() (e is already deleted)
+    // one TransformerSentenceEncoderLayer named `p` (…layers.N); returns non-zero after fail()
     auto load_layer = [&](const std::string& p, LayerW& L) -> int {
         std::vector<float> w(3L * D * D), bb(3L * D);
         const char* names[3] = {"q_proj", "k_proj", "v_proj"};
@@ -538,7 +549,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         }
         return 0;
     };
-    // one ConformerEncoderLayer (wav2vec2_model.py:440-578) named `p`; returns non-zero after fail() (e is already deleted)
+    // one ConformerEncoderLayer (wav2vec2_model.py:440-578) named `p`; returns non-zero after fail()
     auto load_conformer = [&](const std::string& p, ConformerLayerW& L) -> int {
         const int K = c.dw_kernel;
         auto ffn = [&](const std::string& f, DevBuf& lng, DevBuf& lnb, DevBuf& w1, DevBuf& b1, DevBuf& w2, DevBuf& b2) -> int {
@@ -658,10 +669,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
             if (!transposed) {
                 N = D;
                 K = (long)k * D;
-                pk.assign((size_t)N * K, 0.f);
-                for (int co = 0; co < D; ++co)
-                    for (int ci = 0; ci < D; ++ci)
-                        for (int j = 0; j < k; ++j) pk[(long)co * K + (long)j * D + ci] = w[((long)co * D + ci) * k + j];
+                tap_major(w, D, D, k, pk);
             } else {
                 const int KT = (k + stride - 1) / stride;
                 N = (long)stride * D;
@@ -730,10 +738,8 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         GET("output_layer.2.bias", (long)NH * D, t);
         UP(upload_f32(e->head_b2, t));
     }
-#undef GET
 #undef UPW
-#undef UP
-    return finish_create(e, out);
+    return finish_create(std::move(e), out);
 }
 
 int s3enc_destroy(s3enc_handle h) {
@@ -790,49 +796,6 @@ int s3enc_valid_frames(s3enc_handle h, int64_t length, int64_t n_max, int32_t* v
 }  // extern "C"
 
 namespace {
-
-// Where the selected states go: straight into the caller's fp32 slab (the producing kernel writes the slot, nothing is
-// copied), as 16-bit copies next to an internal fp32 residual stream, or only as their term of the Featurizer sum.
-struct Sink {
-    s3enc_encoder* e;
-    hipStream_t st;
-    int mode;  // 0 fp32 slab, 1 16-bit slab, 2 featurize
-    void* out;
-    long stride;
-    int dt;  // the handle's compute dtype (the 16-bit slab's type)
-    long M;
-    int D;
-    const float* w;
-    int norm;
-    bool first = true;
-
-    float* slot32(int si) const { return (mode == 0 && si >= 0) ? (float*)out + (long)si * stride : nullptr; }
-    void* slot16(int si) const { return (mode == 1 && si >= 0) ? (void*)((u16*)out + (long)si * stride) : nullptr; }
-    bool wanted(int si) const { return si >= 0 && (mode != 2 || w[si] != 0.f); }
-    // Featurizer term of state `si`, fused into a row kernel that holds the state as its input (1) or output (2)
-    LnAcc acc(int si, int where) {
-        LnAcc a;
-        if (mode != 2 || si < 0 || w[si] == 0.f) return a;
-        a.acc = (float*)out;
-        a.w = w[si];
-        a.mode = where;
-        a.norm = norm;
-        a.init = first;
-        first = false;
-        return a;
-    }
-    // a state a non-LayerNorm kernel left in fp32 outside the slab: its 16-bit copy / its Featurizer term
-    hipError_t emit(int si, const float* x, bool copy16 = true) {
-        if (si < 0) return hipSuccess;
-        if (mode == 1 && copy16) return launch_emit_state(dt, x, M, D, slot16(si), LnAcc(), st);
-        if (mode == 2 && w[si] != 0.f) return launch_emit_state(F32, x, M, D, nullptr, acc(si, 1), st);
-        return hipSuccess;
-    }
-    hipError_t done(int si) {
-        if (si < 0 || mode == 2 || e->layer_events.empty() || si >= (int)e->layer_events.size()) return hipSuccess;
-        return hipEventRecord(e->layer_events[si], st);
-    }
-};
 
 int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                  const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
@@ -1093,10 +1056,12 @@ int forward_impl(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
 
 int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                  const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
-    if (e->cfg.family == S3ENC_WAV2VEC) return wav2vec_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-    if (e->cfg.family == S3ENC_CPC) return cpc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-    if (e->cfg.family == S3ENC_APC) return apc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-    if (e->cfg.family == S3ENC_MOCKINGJAY) return mj_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+    switch (e->cfg.family) {
+        case S3ENC_WAV2VEC: return wav2vec_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+        case S3ENC_CPC: return cpc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+        case S3ENC_APC: return apc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+        case S3ENC_MOCKINGJAY: return mj_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+    }
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
     const int dt = e->dtype, es = e->es;
@@ -1104,7 +1069,6 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     const bool dist = c.family == S3ENC_DISTILLER;
     const bool mr = c.family == S3ENC_MULTIRES;
     const int NH = dist ? c.pred_heads : 0;
-    if (B <= 0) return fail("s3enc_forward: B must be positive");
     if (fo.selection < 0 || fo.selection > 2) return fail("s3enc_forward: unknown selection");
     if ((dist || mr) && fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: DistilHuBERT / multires-HuBERT have one selection (their hidden_states list)");
@@ -1116,31 +1080,19 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     if (fo.featurize && !fo.w) return fail("s3enc_forward: featurize needs feat_w");
     if (!fo.featurize && fo.out_dtype != F32 && (fo.out_dtype != dt || dt == F32))
         return fail("s3enc_forward: out_dtype must be S3ENC_F32 or the handle's own 16-bit compute dtype");
-    long n_max = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] <= 0) return fail("s3enc_forward: empty utterance");
-        if (lengths[b] > n_max) n_max = lengths[b];
-        if (!wav_ptrs_host[b]) return fail("s3enc_forward: null waveform pointer");
-    }
-    if (n_max_in > 0) {
-        if (n_max_in < n_max) return fail("s3enc_forward: n_max is smaller than the longest utterance");
-        n_max = n_max_in;
-    }
+    long n_max;
+    if (batch_n_max(wav_ptrs_host, lengths, B, n_max_in, n_max)) return 1;
     std::vector<long> L(c.n_conv);
     for (int i = 0; i < c.n_conv; ++i) L[i] = conv_len(c, n_max, i + 1);
     const long T = L[c.n_conv - 1];
     if (T < 1) return fail("s3enc_forward: input shorter than the receptive field of the conv stack");
     const long M = (long)B * T;
-    if (!out) return fail("s3enc_forward: null output");
     MrPlan plan;  // multires-HuBERT: the frame geometry of the U-net; the states are (B, plan.T_out, D)
     if (mr) mr_plan(c, T, plan);
     for (const auto& bp : plan.blocks)
         if (bp.T < 1 || plan.T_out < 1) return fail("s3enc_forward: input too short for the coarsest resolution of the U-net");
-    if (!fo.featurize) {
-        if (layer_stride < (mr ? (long)B * plan.T_out : M) * D) return fail("s3enc_forward: layer_stride < B*T*D");
-        if (layer_stride & 3) return fail("s3enc_forward: layer_stride must be a multiple of 4 elements (vector stores)");
-    }
-    if ((uintptr_t)out & 15) return fail("s3enc_forward: out must be 16-byte aligned");
+    const long out_rows = mr ? (long)B * plan.T_out : M;  // rows of every state the forward writes
+    if (check_out(out, fo, layer_stride, out_rows * D)) return 1;
     if (c.rel_pos && T > 6000) return fail("s3enc_forward: WavLM relative-position window limited to 6000 frames (120 s) per batch");
     if (conf && T > 100000) return fail("s3enc_forward: Conformer position tables are limited to 100000 frames (max_source_positions)");
     std::vector<int> valid(B);
@@ -1188,26 +1140,13 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     const long* d_lens = (const long*)(d_tbl + (size_t)B * 8);
     const int* d_valid = (const int*)(d_tbl + (size_t)B * 16);
 
-    // pinned staging ring (so the async H2D copy never reads freed / overwritten host memory)
-    if (tbl_bytes > e->slot_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (e->pinned) HIP_TRY(hipHostFree(e->pinned));
-        e->pinned = nullptr;
-        e->slot_bytes = tbl_bytes * 4 + 4096;
-        HIP_TRY(hipHostMalloc(&e->pinned, e->slot_bytes * s3enc_encoder::RING, hipHostMallocDefault));
-    }
-    {
-        const int slot = e->slot_next;
-        e->slot_next = (slot + 1) % s3enc_encoder::RING;
-        HIP_TRY(hipEventSynchronize(e->slot_ev[slot]));
-        char* hp = (char*)e->pinned + (size_t)slot * e->slot_bytes;
-        memcpy(hp, wav_ptrs_host, (size_t)B * 8);
-        for (int b = 0; b < B; ++b) ((long*)(hp + (size_t)B * 8))[b] = (long)lengths[b];
-        memcpy(hp + (size_t)B * 16, valid.data(), (size_t)B * 4);
-        if (!valid_blk.empty()) memcpy(hp + (size_t)B * 20, valid_blk.data(), valid_blk.size() * 4);
-        HIP_TRY(hipMemcpyAsync(d_tbl, hp, tbl_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(e->slot_ev[slot], st));
-    }
+    char* hp;
+    if (stage_begin(e, tbl_bytes, st, hp)) return 1;
+    memcpy(hp, wav_ptrs_host, (size_t)B * 8);
+    for (int b = 0; b < B; ++b) ((long*)(hp + (size_t)B * 8))[b] = (long)lengths[b];
+    memcpy(hp + (size_t)B * 16, valid.data(), (size_t)B * 4);
+    if (!valid_blk.empty()) memcpy(hp + (size_t)B * 20, valid_blk.data(), valid_blk.size() * 4);
+    if (stage_commit(e, hp, d_tbl, tbl_bytes, st)) return 1;
 
     // ---- workspace ----
     const bool lnmode = c.extractor_layer_norm != 0;
@@ -1250,11 +1189,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     e->taps.clear();
 
     Sink sink{e, st, fo.featurize ? 2 : (fo.out_dtype != F32 ? 1 : 0), out, (long)layer_stride, dt, M, D, fo.w, fo.feat_norm};
-    if (fo.featurize) {
-        bool any = false;
-        for (int i = 0; i < NS; ++i) any = any || fo.w[i] != 0.f;
-        if (!any) HIP_TRY(hipMemsetAsync(out, 0, (size_t)(mr ? (long)B * plan.T_out : M) * D * 4, st));
-    }
+    HIP_TRY(sink.zero_without_terms(NS, out_rows));
     // state index of each tensor of the forward under this selection (-1: not a state)
     const bool hid = fo.selection == S3ENC_SEL_HIDDEN && !dist;
     const bool lay = fo.selection == S3ENC_SEL_LAYER_OUT;

@@ -1,8 +1,13 @@
 // engine_internal.h — what the translation units of the engine share: error reporting, device buffers, the weight containers,
-// the handle (struct s3enc_encoder), per-kernel profiling, the workspace allocator and the multires-HuBERT plan.
-//   engine.hip    s3enc_create (weight packing), the single-resolution forward schedule, the handle's C ABI
+// the checkpoint reader (Ckpt, GET / UP), the handle (struct s3enc_encoder), per-kernel profiling, the plumbing every family's
+// forward starts with (batch checks, the pinned staging ring, Sink: where the states go), the workspace allocator and the
+// multires-HuBERT plan.
+//   engine.hip    s3enc_create (weight packing), the single-resolution forward schedule, the handle's C ABI, and the shared
+//                 plumbing's definitions (Ckpt::get, tap_major, load_rnn_layer, batch_n_max, check_out, stage_begin / stage_commit)
 //   multires.hip  the multires-HuBERT U-net behind post_extract_proj
 //   wav2vec.hip / cpc.hip  the convolutional families (wav2vec, modified CPC); rnn.hip: the LSTM / GRU recurrence
+//   apc.hip / mockingjay.hip  the log-mel families (APC / VQ-APC on GRU layers; Mockingjay / TERA / AudioALBERT on BERT layers)
+//   (a family file holds its configuration check, its weights and its forward schedule: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
 #pragma once
 #include <hip/hip_runtime.h>
@@ -41,6 +46,26 @@ inline int fail(const std::string& msg) {
             return fail(_b);                                                                           \
         }                                                                                              \
     } while (0)
+
+// ---- checkpoint lookup: the tensors of s3enc_create* by name ------------------------------------------------------------------
+struct Ckpt {
+    std::map<std::string, const s3enc_tensor*> m;
+    Ckpt(const s3enc_tensor* tensors, int n_tensors) {
+        for (int i = 0; i < n_tensors; ++i)
+            if (tensors[i].name && tensors[i].data) m[tensors[i].name] = &tensors[i];
+    }
+    int get(const std::string& name, long expect, std::vector<float>& out) const;  // non-zero after fail(): missing / wrong size
+};
+// inside a creator (or a lambda of one) that returns int and has the reader as `ck`: fetch a tensor / run an upload, or return 1
+#define GET(name, n, vec) \
+    if (ck.get(name, n, vec)) return 1
+#define UP(call)                                                                                          \
+    do {                                                                                                  \
+        hipError_t _e = (call);                                                                           \
+        if (_e != hipSuccess) return fail(std::string("weight upload failed: ") + hipGetErrorString(_e)); \
+    } while (0)
+// (Cout, Cin, k) as nn.Conv1d holds it -> tap-major [co][j * Cin + ci]: the K order of the channel-last implicit GEMM
+void tap_major(const std::vector<float>& t, int cout, int cin, int k, std::vector<float>& o);
 
 // ---- host-side dtype conversion -------------------------------------------------------------------------
 inline uint16_t h_bf16(float f) {
@@ -369,19 +394,22 @@ struct W2vW {
     DevBuf table;
 };
 
-// modified CPC (cpc.hip): conv0 [C][10]; conv1.. tap-major (C, k * C); every convolution's bias and ChannelNorm affine; per recurrent
-// layer weight_ih (G H, H) as the input projection's GEMM operand, its bias b_ih + the foldable part of b_hh, weight_hh in
-// rnn.hip's k-quad-major layout and, for a GRU, b_hn
-struct CpcW {
-    std::vector<DevBuf> conv_w, conv_b, cn_g, cn_b;
+// LSTM (G = 4 gates) / GRU (G = 3) layers: per layer weight_ih (G H, I) as the input projection's GEMM operand, its bias b_ih + the
+// foldable part of b_hh, weight_hh in rnn.hip's k-quad-major layout and, for a GRU, b_hn
+struct RnnW {
     std::vector<DevBuf> w_ih, b_pre, w_hh, b_hn;
+};
+// appends the layer whose tensors are named `prefix` + {weight_ih, weight_hh, bias_ih, bias_hh} + `suffix` (I: its input width)
+int load_rnn_layer(const Ckpt& ck, const std::string& prefix, const std::string& suffix, int G, int H, int I, RnnW& w);
+
+// modified CPC (cpc.hip): conv0 [C][10]; conv1.. tap-major (C, k * C); every convolution's bias and ChannelNorm affine; the
+// recurrent layers (layer 0 reads the encoder output: I = H)
+struct CpcW : RnnW {
+    std::vector<DevBuf> conv_w, conv_b, cn_g, cn_b;
 };
 
-// APC / VQ-APC (apc.hip): per GRU layer weight_ih (3 H, I) as the input projection's GEMM operand (I = the mel bins for layer 0),
-// its bias b_ih + the r and z parts of b_hh, weight_hh in rnn.hip's k-quad-major layout, and b_hn
-struct ApcW {
-    std::vector<DevBuf> w_ih, b_pre, w_hh, b_hn;
-};
+// APC / VQ-APC (apc.hip): GRU layers (I = the mel bins for layer 0)
+using ApcW = RnnW;
 
 // Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table, and per layer (ONE layer with
 // share_layer) q|k|v stacked as one (3 D, D) operand with q pre-scaled by head_dim^-0.5, the other projections and LayerNorm affines
@@ -582,6 +610,75 @@ struct Prof {
     }
 };
 
+struct FwdOpts {
+    int selection = S3ENC_SEL_HIDDEN;
+    int out_dtype = F32;
+    bool featurize = false;
+    int feat_norm = 0;
+    const float* w = nullptr;  // host, one per state
+};
+
+// ---- what every family's forward starts with ----------------------------------------------------------------------------------------
+// B, the waveform pointers, the lengths and the caller's n_max (0: none); n_max: the batch's padded length in samples
+int batch_n_max(const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in, long& n_max);
+// the caller's output: non-null, 16-byte aligned and — for a slab of states — a layer_stride of at least `min_stride` elements
+int check_out(const void* out, const FwdOpts& fo, int64_t layer_stride, long min_stride);
+// Pinned staging ring (so the async H2D copy never reads freed / overwritten host memory).  stage_begin hands out the next slot's
+// host pointer once the copy that last read it has finished (growing the ring when `bytes` outgrow a slot); the caller fills `bytes`
+// there and stage_commit enqueues their copy to `dst` on `st` with the slot's event behind it.
+int stage_begin(s3enc_encoder* e, size_t bytes, hipStream_t st, char*& hp);
+int stage_commit(s3enc_encoder* e, const char* hp, void* dst, size_t bytes, hipStream_t st);
+
+// Where the selected states go: straight into the caller's fp32 slab (the producing kernel writes the slot, nothing is
+// copied), as 16-bit copies next to an internal fp32 residual stream, or only as their term of the Featurizer sum.
+struct Sink {
+    s3enc_encoder* e;
+    hipStream_t st;
+    int mode;  // 0 fp32 slab, 1 16-bit slab, 2 featurize
+    void* out;
+    long stride;
+    int dt;  // the handle's compute dtype (the 16-bit slab's type)
+    long M;
+    int D;
+    const float* w;
+    int norm;
+    bool first = true;
+
+    float* slot32(int si) const { return (mode == 0 && si >= 0) ? (float*)out + (long)si * stride : nullptr; }
+    void* slot16(int si) const { return (mode == 1 && si >= 0) ? (void*)((u16*)out + (long)si * stride) : nullptr; }
+    bool term(int si) const { return mode == 2 && si >= 0 && w[si] != 0.f; }  // state `si` adds a term to the Featurizer sum
+    bool wanted(int si) const { return si >= 0 && (mode != 2 || w[si] != 0.f); }
+    // featurize with no non-zero weight among the NS states: no kernel writes the (rows, D) sum, it is zeroed here
+    hipError_t zero_without_terms(int NS, long rows) const {
+        for (int i = 0; mode == 2 && i < NS; ++i)
+            if (w[i] != 0.f) return hipSuccess;
+        return mode == 2 ? hipMemsetAsync(out, 0, (size_t)rows * D * 4, st) : hipSuccess;
+    }
+    // Featurizer term of state `si`, fused into a row kernel that holds the state as its input (1) or output (2)
+    LnAcc acc(int si, int where) {
+        LnAcc a;
+        if (!term(si)) return a;
+        a.acc = (float*)out;
+        a.w = w[si];
+        a.mode = where;
+        a.norm = norm;
+        a.init = first;
+        first = false;
+        return a;
+    }
+    // a state a non-LayerNorm kernel left in fp32 outside the slab: its 16-bit copy / its Featurizer term
+    hipError_t emit(int si, const float* x, bool copy16 = true) {
+        if (si < 0) return hipSuccess;
+        if (mode == 1 && copy16) return launch_emit_state(dt, x, M, D, slot16(si), LnAcc(), st);
+        if (term(si)) return launch_emit_state(F32, x, M, D, nullptr, acc(si, 1), st);
+        return hipSuccess;
+    }
+    hipError_t done(int si) {
+        if (si < 0 || mode == 2 || e->layer_events.empty() || si >= (int)e->layer_events.size()) return hipSuccess;
+        return hipEventRecord(e->layer_events[si], st);
+    }
+};
+
 // S3ENC_F16X2 hybrids: would the three-term GEMM take an (N, K) product whose A rows are `lda` fp32 elements apart?  The REAL
 // predicate (gemm_x3_eligible) on a representative call — 256-byte aligned operands as the workspace allocator hands them out, a
 // dense fp32 output — instead of a hand-copied subset of it: s3enc_create decides the hybrids with this, so the forward's
@@ -648,13 +745,6 @@ struct Bump {
     }
 };
 
-struct FwdOpts {
-    int selection = S3ENC_SEL_HIDDEN;
-    int out_dtype = F32;
-    bool featurize = false;
-    int feat_norm = 0;
-    const float* w = nullptr;  // host, one per state
-};
 int num_states(const s3enc_config& c, int selection);
 // multires.hip: the U-net behind post_extract_proj (xproj: (B, T0, D) fp32, padded frames zero)
 int multires_tail(s3enc_handle e, hipStream_t st, int B, const MrPlan& plan, const std::vector<const int*>& d_valid, float* xproj,
@@ -666,26 +756,26 @@ struct W2vCfg : s3enc_config, s3enc_wav2vec_config {
     W2vCfg(const s3enc_config& a, const s3enc_wav2vec_config& b) : s3enc_config(a), s3enc_wav2vec_config(b) {}
 };
 int wav2vec_check_config(const W2vCfg& c);
-int wav2vec_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
+int wav2vec_create(s3enc_encoder* e, const Ckpt& ck);
 int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                     const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
 // cpc.hip: the S3ENC_CPC family (its own configuration check, weights and forward schedule); frames through the padded conv stack
 long cpc_conv_len(const s3enc_config& c, const s3enc_cpc_config& x, long n, int upto /*exclusive*/);
 int cpc_check_config(const s3enc_config& c, const s3enc_cpc_config& x);
-int cpc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
+int cpc_create(s3enc_encoder* e, const Ckpt& ck);
 int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
 // apc.hip: the S3ENC_APC family (kaldi log-mel front end + GRU layers on packed sequences)
 int apc_check_config(const s3enc_config& c, const s3enc_apc_config& x);
-int apc_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
+int apc_create(s3enc_encoder* e, const Ckpt& ck);
 int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
 // mockingjay.hip: the S3ENC_MOCKINGJAY family (spectrogram front end + input representation + post-LN BERT layers, chunked)
 int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x);
-int mj_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors);
+int mj_create(s3enc_encoder* e, const Ckpt& ck);
 long mj_num_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long n);
 int mj_valid_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long length, long n_max);
 int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,

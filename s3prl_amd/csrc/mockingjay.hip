@@ -185,48 +185,22 @@ int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x) {
     return 0;
 }
 
-namespace {
-struct MjFetch {
-    std::map<std::string, const s3enc_tensor*> m;
-    int get(const std::string& name, long expect, std::vector<float>& out) const {
-        auto it = m.find(name);
-        if (it == m.end()) return fail("checkpoint is missing tensor '" + name + "'");
-        long n = 1;
-        for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
-        if (n != expect)
-            return fail("tensor '" + name + "' has " + std::to_string(n) + " elements, expected " + std::to_string(expect));
-        out.assign(it->second->data, it->second->data + expect);
-        return 0;
-    }
-};
-}  // namespace
-
-int mj_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors) {
+int mj_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_mockingjay_config& x = e->mj_cfg;
     const s3enc_config& c = e->cfg;
     const int D = c.embed_dim, FF = c.ffn_dim, F = x.input_dim;
-    MjFetch ck;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name && tensors[i].data) ck.m[tensors[i].name] = &tensors[i];
     e->mj.reset(new MjW());
     MjW& w = *e->mj;
     std::vector<float> t, t2;
-#define MJ_GET(name, n, vec) \
-    if (ck.get(name, n, vec)) return 1
-#define MJ_UP(buf, vec)                                                                        \
-    do {                                                                                       \
-        hipError_t _e = upload_f32(buf, vec);                                                  \
-        if (_e != hipSuccess) return fail(std::string("weight upload failed: ") + hipGetErrorString(_e)); \
-    } while (0)
     const std::string ir = "input_representations.";
-    MJ_GET(ir + "spec_transform.weight", (long)D * F, t);
-    MJ_UP(w.in_w, t);
-    MJ_GET(ir + "spec_transform.bias", D, t);
-    MJ_UP(w.in_b, t);
-    MJ_GET(ir + "LayerNorm.weight", D, t);
-    MJ_UP(w.in_g, t);
-    MJ_GET(ir + "LayerNorm.bias", D, t);
-    MJ_UP(w.in_beta, t);
+    GET(ir + "spec_transform.weight", (long)D * F, t);
+    UP(upload_f32(w.in_w, t));
+    GET(ir + "spec_transform.bias", D, t);
+    UP(upload_f32(w.in_b, t));
+    GET(ir + "LayerNorm.weight", D, t);
+    UP(upload_f32(w.in_g, t));
+    GET(ir + "LayerNorm.bias", D, t);
+    UP(upload_f32(w.in_beta, t));
     const int NW = x.share_layer ? 1 : c.encoder_layers;  // share_layer: the ModuleList holds ONE module (model.py:343-344)
     w.layers.resize(NW);
     for (int l = 0; l < NW; ++l) {
@@ -235,40 +209,38 @@ int mj_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors) {
         std::vector<float> qkv((size_t)3 * D * D), bqkv((size_t)3 * D);
         const char* part[3] = {"query", "key", "value"};
         for (int k = 0; k < 3; ++k) {
-            MJ_GET(n + "attention.self." + part[k] + ".weight", (long)D * D, t);
-            MJ_GET(n + "attention.self." + part[k] + ".bias", D, t2);
+            GET(n + "attention.self." + part[k] + ".weight", (long)D * D, t);
+            GET(n + "attention.self." + part[k] + ".bias", D, t2);
             const float sc = k == 0 ? 0.125f : 1.f;  // 1 / sqrt(64): exact
             for (size_t i = 0; i < t.size(); ++i) qkv[(size_t)k * D * D + i] = t[i] * sc;
             for (int i = 0; i < D; ++i) bqkv[(size_t)k * D + i] = t2[i] * sc;
         }
-        MJ_UP(L.wqkv, qkv);
-        MJ_UP(L.bqkv, bqkv);
-        MJ_GET(n + "attention.output.dense.weight", (long)D * D, t);
-        MJ_UP(L.wo, t);
-        MJ_GET(n + "attention.output.dense.bias", D, t);
-        MJ_UP(L.bo, t);
-        MJ_GET(n + "attention.output.LayerNorm.weight", D, t);
-        MJ_UP(L.g1, t);
-        MJ_GET(n + "attention.output.LayerNorm.bias", D, t);
-        MJ_UP(L.b1n, t);
-        MJ_GET(n + "intermediate.dense.weight", (long)FF * D, t);
-        MJ_UP(L.w1, t);
-        MJ_GET(n + "intermediate.dense.bias", FF, t);
-        MJ_UP(L.b1, t);
-        MJ_GET(n + "output.dense.weight", (long)D * FF, t);
-        MJ_UP(L.w2, t);
-        MJ_GET(n + "output.dense.bias", D, t);
-        MJ_UP(L.b2, t);
-        MJ_GET(n + "output.LayerNorm.weight", D, t);
-        MJ_UP(L.g2, t);
-        MJ_GET(n + "output.LayerNorm.bias", D, t);
-        MJ_UP(L.b2n, t);
+        UP(upload_f32(L.wqkv, qkv));
+        UP(upload_f32(L.bqkv, bqkv));
+        GET(n + "attention.output.dense.weight", (long)D * D, t);
+        UP(upload_f32(L.wo, t));
+        GET(n + "attention.output.dense.bias", D, t);
+        UP(upload_f32(L.bo, t));
+        GET(n + "attention.output.LayerNorm.weight", D, t);
+        UP(upload_f32(L.g1, t));
+        GET(n + "attention.output.LayerNorm.bias", D, t);
+        UP(upload_f32(L.b1n, t));
+        GET(n + "intermediate.dense.weight", (long)FF * D, t);
+        UP(upload_f32(L.w1, t));
+        GET(n + "intermediate.dense.bias", FF, t);
+        UP(upload_f32(L.b1, t));
+        GET(n + "output.dense.weight", (long)D * FF, t);
+        UP(upload_f32(L.w2, t));
+        GET(n + "output.dense.bias", D, t);
+        UP(upload_f32(L.b2, t));
+        GET(n + "output.LayerNorm.weight", D, t);
+        UP(upload_f32(L.g2, t));
+        GET(n + "output.LayerNorm.bias", D, t);
+        UP(upload_f32(L.b2n, t));
     }
     w.pos_rows = x.sequence_length > 0 ? x.sequence_length : 3008;  // a chunk never has more rows than sequence_length
     mj_position_rows(w.pos_rows, D, t);
-    MJ_UP(w.pos, t);
-#undef MJ_GET
-#undef MJ_UP
+    UP(upload_f32(w.pos, t));
     return 0;
 }
 
@@ -279,25 +251,17 @@ int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t*
     MjW& w = *e->mj;
     const int D = c.embed_dim, FF = c.ffn_dim, F = x.input_dim, NL = c.encoder_layers, H = c.heads;
     const bool mel = x.frontend == 1;
-    if (B <= 0) return fail("s3enc_forward: B must be positive");
     if (fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: feature_selection is not defined for Mockingjay / TERA / AudioALBERT (the reference expert has one hidden_states list)");
     if (fo.featurize && !fo.w) return fail("s3enc_forward: featurize needs feat_w");
     if (!fo.featurize && fo.out_dtype != F32) return fail("s3enc_forward: out_dtype must be S3ENC_F32 for a Mockingjay handle");
     if (e->aux_codewords || e->aux_codeids) return fail("s3enc_forward_aux: codewords / codeids are outputs of a wav2vec handle with a vector quantizer");
     if (B > 65535) return fail("s3enc_forward: batch too large");
-    long n_max = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] <= 0) return fail("s3enc_forward: empty utterance");
-        if (lengths[b] > n_max) n_max = lengths[b];
-        if (!wav_ptrs_host[b]) return fail("s3enc_forward: null waveform pointer");
-        if (mel && lengths[b] <= 200)
+    long n_max;
+    if (batch_n_max(wav_ptrs_host, lengths, B, n_max_in, n_max)) return 1;
+    for (int b = 0; mel && b < B; ++b)
+        if (lengths[b] <= 200)
             return fail("s3enc_forward: an utterance of at most 200 samples has no reflect-padded centred frame (torch.stft refuses it)");
-    }
-    if (n_max_in > 0) {
-        if (n_max_in < n_max) return fail("s3enc_forward: n_max is smaller than the longest utterance");
-        n_max = n_max_in;
-    }
     const long T = mj_num_frames(c, x, n_max);
     if (T < 1) return fail("s3enc_forward: the batch is shorter than one analysis window");
     std::vector<int> frames(B);
@@ -316,12 +280,7 @@ int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t*
     }
     const long Tp = n * Tc, M = (long)B * T, Mp = (long)B * Tp, NS = (long)B * n;
     if (Mp > 0x7fffffffL / 4 || NS > 0x7fffffffL) return fail("s3enc_forward: batch too large");
-    if (!out) return fail("s3enc_forward: null output");
-    if (!fo.featurize) {
-        if (layer_stride < M * D) return fail("s3enc_forward: layer_stride < B*T*D");
-        if (layer_stride & 3) return fail("s3enc_forward: layer_stride must be a multiple of 4 elements (vector stores)");
-    }
-    if ((uintptr_t)out & 15) return fail("s3enc_forward: out must be 16-byte aligned");
+    if (check_out(out, fo, layer_stride, M * D)) return 1;
     DeviceGuard dg(e->device);
     if (!dg.ok) return fail("s3enc_forward: hipSetDevice failed");
     if (Tc > w.pos_rows) {  // only without a sequence_length: grow the position table (synchronising, once per new maximum)
@@ -337,31 +296,19 @@ int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t*
     const size_t tbl_bytes = o_kv + (size_t)NS * 4;
     HIP_TRY(e->small.ensure_on_stream(tbl_bytes + 1024, st));
     char* dsm = (char*)e->small.p;
-    if (tbl_bytes > e->slot_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (e->pinned) HIP_TRY(hipHostFree(e->pinned));
-        e->pinned = nullptr;
-        e->slot_bytes = tbl_bytes * 4 + 4096;
-        HIP_TRY(hipHostMalloc(&e->pinned, e->slot_bytes * s3enc_encoder::RING, hipHostMallocDefault));
-    }
-    {
-        const int slot = e->slot_next;
-        e->slot_next = (slot + 1) % s3enc_encoder::RING;
-        HIP_TRY(hipEventSynchronize(e->slot_ev[slot]));
-        char* hp = (char*)e->pinned + (size_t)slot * e->slot_bytes;
-        for (int b = 0; b < B; ++b) {
-            ((const float**)(hp + o_ptr))[b] = wav_ptrs_host[b];
-            ((long*)(hp + o_len))[b] = (long)lengths[b];
-            ((int*)(hp + o_cnt))[b] = frames[b];
-            for (long ch = 0; ch < n; ++ch) {
-                const long rows = std::min(Tc, T - ch * Tc);  // the last chunk is shorter
-                long kv = std::min(std::max((long)frames[b] - ch * Tc, 0L), rows);
-                ((int*)(hp + o_kv))[b * n + ch] = (int)std::max(kv, 1L);  // a chunk without a live key: key 0 alone (finite rows)
-            }
+    char* hp;
+    if (stage_begin(e, tbl_bytes, st, hp)) return 1;
+    for (int b = 0; b < B; ++b) {
+        ((const float**)(hp + o_ptr))[b] = wav_ptrs_host[b];
+        ((long*)(hp + o_len))[b] = (long)lengths[b];
+        ((int*)(hp + o_cnt))[b] = frames[b];
+        for (long ch = 0; ch < n; ++ch) {
+            const long rows = std::min(Tc, T - ch * Tc);  // the last chunk is shorter
+            long kv = std::min(std::max((long)frames[b] - ch * Tc, 0L), rows);
+            ((int*)(hp + o_kv))[b * n + ch] = (int)std::max(kv, 1L);  // a chunk without a live key: key 0 alone (finite rows)
         }
-        HIP_TRY(hipMemcpyAsync(dsm, hp, tbl_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(e->slot_ev[slot], st));
     }
+    if (stage_commit(e, hp, dsm, tbl_bytes, st)) return 1;
     const float* const* d_ptr = (const float* const*)(dsm + o_ptr);
     const long* d_len = (const long*)(dsm + o_len);
     const int* d_cnt = (const int*)(dsm + o_cnt);
@@ -390,28 +337,16 @@ int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t*
     e->taps.clear();
 
     // ---- where the states go ----
-    bool first = true;
-    if (feat_sum) {
-        bool any = false;
-        for (int i = 0; i <= NL; ++i) any = any || fo.w[i] != 0.f;
-        if (!any) HIP_TRY(hipMemsetAsync(out, 0, (size_t)M * D * 4, st));
-    }
-    auto state_dst = [&](int si) -> float* { return feat_sum ? stc : (float*)out + (long)si * layer_stride; };
-    auto emit = [&](int si) -> hipError_t {  // featurize: the state's term of the weighted sum
-        if (!feat_sum || fo.w[si] == 0.f) return hipSuccess;
-        LnAcc a;
-        a.acc = (float*)out;
-        a.w = fo.w[si];
-        a.mode = 1;
-        a.norm = fo.feat_norm;
-        a.init = first;
-        first = false;
-        Prof pr(e, st, "emit_state", 0, 4.0 * M * D * 2);
-        return launch_emit_state(F32, stc, M, D, nullptr, a, st);
-    };
-    auto done = [&](int si) -> hipError_t {
-        if (feat_sum || e->layer_events.empty() || si >= (int)e->layer_events.size()) return hipSuccess;
-        return hipEventRecord(e->layer_events[si], st);
+    Sink sink{e, st, feat_sum ? 2 : 0, out, (long)layer_stride, F32, M, D, fo.w, fo.feat_norm};
+    HIP_TRY(sink.zero_without_terms(NL + 1, M));
+    // a state leaves its LayerNorm as compact (B, T, D) rows: into its slot of the slab, or into `stc` for its Featurizer term
+    auto state_done = [&](int si) -> int {
+        if (sink.term(si)) {
+            Prof pr(e, st, "emit_state", 0, 4.0 * M * D * 2);
+            HIP_TRY(sink.emit(si, stc));
+        }
+        HIP_TRY(sink.done(si));
+        return 0;
     };
     auto gemm = [&](const char* kind, const float* A, int K, const DevBuf& W, const DevBuf& bias, int N, int act, const float* res,
                     float* o) -> hipError_t {
@@ -442,7 +377,7 @@ int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t*
         p.rows = Mp;
         p.C = D;
         p.out = o;
-        p.out2 = si >= 0 ? state_dst(si) : nullptr;
+        p.out2 = si < 0 ? nullptr : (sink.slot32(si) ? sink.slot32(si) : stc);
         p.Tp = (int)Tp;
         p.T = (int)T;
         Prof pr(e, st, "layernorm_eps", 0, 4.0 * Mp * D * (si >= 0 ? 3 : 2));
@@ -478,8 +413,7 @@ int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t*
     // ---- input representation: state 0 ----
     HIP_TRY(gemm("gemm:mj_in", feat, F, w.in_w, w.in_b, D, 0, nullptr, tmp));
     HIP_TRY(ln(tmp, (const float*)w.pos.p, w.in_g, w.in_beta, xa, 0));
-    HIP_TRY(emit(0));
-    HIP_TRY(done(0));
+    if (state_done(0)) return 1;
 
     // ---- post-LN BERT layers over B * n sequences of Tc rows ----
     for (int l = 0; l < NL; ++l) {
@@ -501,8 +435,7 @@ int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t*
         HIP_TRY(gemm("gemm:fc1", xb, D, L.w1, L.b1, FF, 1, nullptr, hbuf));
         HIP_TRY(gemm("gemm:fc2", hbuf, FF, L.w2, L.b2, D, 0, xb, tmp));
         HIP_TRY(ln(tmp, nullptr, L.g2, L.b2n, xa, l + 1));
-        HIP_TRY(emit(l + 1));
-        HIP_TRY(done(l + 1));
+        if (state_done(l + 1)) return 1;
     }
     return 0;
 }

@@ -327,45 +327,12 @@ int wav2vec_check_config(const W2vCfg& c) {
     return 0;
 }
 
-namespace {
-struct Fetch {
-    std::map<std::string, const s3enc_tensor*> m;
-    int get(const std::string& name, long expect, std::vector<float>& out) const {
-        auto it = m.find(name);
-        if (it == m.end()) return fail("checkpoint is missing tensor '" + name + "'");
-        long n = 1;
-        for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
-        if (n != expect)
-            return fail("tensor '" + name + "' has " + std::to_string(n) + " elements, expected " + std::to_string(expect));
-        out.assign(it->second->data, it->second->data + expect);
-        return 0;
-    }
-};
-// (Cout, Cin, k) -> [co][j * Cin + ci]: the K order of the channel-last implicit GEMM
-void tap_major(const std::vector<float>& t, int cout, int cin, int k, std::vector<float>& o) {
-    o.resize(t.size());
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int j = 0; j < k; ++j) o[((long)co * k + j) * cin + ci] = t[((long)co * cin + ci) * k + j];
-}
-}  // namespace
-
-int wav2vec_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors) {
+int wav2vec_create(s3enc_encoder* e, const Ckpt& ck) {
     const W2vCfg c(e->cfg, e->w2v_cfg);
     const int C = c.conv_dim;
-    Fetch ck;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name && tensors[i].data) ck.m[tensors[i].name] = &tensors[i];
     e->w2v.reset(new W2vW());
     W2vW& w = *e->w2v;
     std::vector<float> t, t2;
-#define W2V_GET(name, n, vec) \
-    if (ck.get(name, n, vec)) return 1
-#define W2V_UP(buf, vec)                                                                       \
-    do {                                                                                       \
-        hipError_t _e = upload_f32(buf, vec);                                                  \
-        if (_e != hipSuccess) return fail(std::string("weight upload failed: ") + hipGetErrorString(_e)); \
-    } while (0)
     const bool affine = !c.non_affine_group_norm;
     w.ext_w.resize(c.n_conv);
     w.ext_g.resize(c.n_conv);
@@ -373,18 +340,18 @@ int wav2vec_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors)
     for (int i = 0; i < c.n_conv; ++i) {
         const std::string p = "feature_extractor.conv_layers." + std::to_string(i);
         const int cin = i == 0 ? 1 : C, k = c.conv_kernel[i];
-        W2V_GET(p + ".0.weight", (long)C * cin * k, t);
+        GET(p + ".0.weight", (long)C * cin * k, t);
         if (i == 0) {
-            W2V_UP(w.ext_w[i], t);  // [C][k]
+            UP(upload_f32(w.ext_w[i], t));  // [C][k]
         } else {
             tap_major(t, C, cin, k, t2);
-            W2V_UP(w.ext_w[i], t2);
+            UP(upload_f32(w.ext_w[i], t2));
         }
         if (affine) {
-            W2V_GET(p + ".2.weight", C, t);
-            W2V_UP(w.ext_g[i], t);
-            W2V_GET(p + ".2.bias", C, t);
-            W2V_UP(w.ext_b[i], t);
+            GET(p + ".2.weight", C, t);
+            UP(upload_f32(w.ext_g[i], t));
+            GET(p + ".2.bias", C, t);
+            UP(upload_f32(w.ext_b[i], t));
         }
     }
     w.agg_w.resize(c.n_agg);
@@ -394,18 +361,18 @@ int wav2vec_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors)
     for (int j = 0; j < c.n_agg; ++j) {
         const std::string p = "feature_aggregator.conv_layers." + std::to_string(j);
         const int k = c.agg_kernel[j];
-        W2V_GET(p + ".1.weight", (long)C * C * k, t);
+        GET(p + ".1.weight", (long)C * C * k, t);
         tap_major(t, C, C, k, t2);
-        W2V_UP(w.agg_w[j], t2);
+        UP(upload_f32(w.agg_w[j], t2));
         if (!c.no_conv_bias) {
-            W2V_GET(p + ".1.bias", C, t);
-            W2V_UP(w.agg_bias[j], t);
+            GET(p + ".1.bias", C, t);
+            UP(upload_f32(w.agg_bias[j], t));
         }
         if (affine) {
-            W2V_GET(p + ".3.weight", C, t);
-            W2V_UP(w.agg_g[j], t);
-            W2V_GET(p + ".3.bias", C, t);
-            W2V_UP(w.agg_b[j], t);
+            GET(p + ".3.weight", C, t);
+            UP(upload_f32(w.agg_g[j], t));
+            GET(p + ".3.bias", C, t);
+            UP(upload_f32(w.agg_b[j], t));
         }
     }
     const int G = c.vq_groups, V = c.vq_vars, Gt = c.combine_groups ? 1 : G;
@@ -419,38 +386,36 @@ int wav2vec_create(s3enc_encoder* e, const s3enc_tensor* tensors, int n_tensors)
             const long in = i == 0 ? C : 2L * C, outn = last ? (long)G * V : 2L * C;
             const std::string p = d == 1 ? std::string("vector_quantizer.weight_proj")
                                          : "vector_quantizer.weight_proj." + std::to_string(i) + (last ? "" : ".0");
-            W2V_GET(p + ".weight", outn * in, t);
-            W2V_UP(w.vq_w[i], t);
-            W2V_GET(p + ".bias", outn, t);
-            W2V_UP(w.vq_b[i], t);
+            GET(p + ".weight", outn * in, t);
+            UP(upload_f32(w.vq_w[i], t));
+            GET(p + ".bias", outn, t);
+            UP(upload_f32(w.vq_b[i], t));
         }
-        W2V_GET("vector_quantizer.vars", (long)Gt * V * Dv, t);  // (1, Gt * V, Dv)
-        W2V_UP(w.table, t);
+        GET("vector_quantizer.vars", (long)Gt * V * Dv, t);  // (1, Gt * V, Dv)
+        UP(upload_f32(w.table, t));
     } else if (c.vq_type == 2) {
-        W2V_GET("vector_quantizer.embedding", (long)V * Gt * Dv, t);  // (V, Gt, Dv)
+        GET("vector_quantizer.embedding", (long)V * Gt * Dv, t);  // (V, Gt, Dv)
         t2.resize(t.size());
         for (int v = 0; v < V; ++v)
             for (int g = 0; g < Gt; ++g)
                 for (int j = 0; j < Dv; ++j) t2[((long)g * V + v) * Dv + j] = t[((long)v * Gt + g) * Dv + j];
-        W2V_UP(w.table, t2);  // (Gt, V, Dv): the gather table
+        UP(upload_f32(w.table, t2));  // (Gt, V, Dv): the gather table
         std::vector<float> et((size_t)G * Dv * V);  // (G, Dv, V), shared variables repeated: the distance kernel's operand
         for (int g = 0; g < G; ++g)
             for (int j = 0; j < Dv; ++j)
                 for (int v = 0; v < V; ++v) et[((long)g * Dv + j) * V + v] = t[((long)v * Gt + (c.combine_groups ? 0 : g)) * Dv + j];
-        W2V_UP(w.emb_t, et);
-        W2V_GET("vector_quantizer.projection.0.weight", (long)C * Dv, t);  // Conv1d(C, C, 1, groups = G): (C, C / G, 1)
+        UP(upload_f32(w.emb_t, et));
+        GET("vector_quantizer.projection.0.weight", (long)C * Dv, t);  // Conv1d(C, C, 1, groups = G): (C, C / G, 1)
         w.km_w.resize(G);
         for (int g = 0; g < G; ++g) {
             t2.assign(t.begin() + (long)g * Dv * Dv, t.begin() + (long)(g + 1) * Dv * Dv);
-            W2V_UP(w.km_w[g], t2);
+            UP(upload_f32(w.km_w[g], t2));
         }
-        W2V_GET("vector_quantizer.projection.1.weight", C, t);
-        W2V_UP(w.km_g, t);
-        W2V_GET("vector_quantizer.projection.1.bias", C, t);
-        W2V_UP(w.km_b, t);
+        GET("vector_quantizer.projection.1.weight", C, t);
+        UP(upload_f32(w.km_g, t));
+        GET("vector_quantizer.projection.1.bias", C, t);
+        UP(upload_f32(w.km_b, t));
     }
-#undef W2V_GET
-#undef W2V_UP
     return 0;
 }
 
@@ -459,34 +424,20 @@ int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int
     const W2vCfg c(e->cfg, e->w2v_cfg);
     const W2vW& w = *e->w2v;
     const int C = c.conv_dim, NA = c.n_agg, NS = NA + 1;
-    if (B <= 0) return fail("s3enc_forward: B must be positive");
     if (fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: feature_selection is not defined for wav2vec / vq-wav2vec (the reference expert has one hidden_states list)");
     if (fo.featurize && !fo.w) return fail("s3enc_forward: featurize needs feat_w");
     if (!fo.featurize && fo.out_dtype != F32) return fail("s3enc_forward: out_dtype must be S3ENC_F32 for a wav2vec handle");
     if ((e->aux_codewords || e->aux_codeids) && !c.vq_type)
         return fail("s3enc_forward_aux: codewords / codeids need a vector quantizer (vq_type gumbel or kmeans)");
-    long n_max = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] <= 0) return fail("s3enc_forward: empty utterance");
-        if (lengths[b] > n_max) n_max = lengths[b];
-        if (!wav_ptrs_host[b]) return fail("s3enc_forward: null waveform pointer");
-    }
-    if (n_max_in > 0) {
-        if (n_max_in < n_max) return fail("s3enc_forward: n_max is smaller than the longest utterance");
-        n_max = n_max_in;
-    }
+    long n_max;
+    if (batch_n_max(wav_ptrs_host, lengths, B, n_max_in, n_max)) return 1;
     std::vector<long> L(c.n_conv);
     for (int i = 0; i < c.n_conv; ++i) L[i] = conv_len(c, n_max, i + 1);
     const long T = L[c.n_conv - 1];
     if (T < 1) return fail("s3enc_forward: input shorter than the receptive field of the conv stack");
     const long M = (long)B * T;
-    if (!out) return fail("s3enc_forward: null output");
-    if (!fo.featurize) {
-        if (layer_stride < M * C) return fail("s3enc_forward: layer_stride < B*T*D");
-        if (layer_stride & 3) return fail("s3enc_forward: layer_stride must be a multiple of 4 elements (vector stores)");
-    }
-    if ((uintptr_t)out & 15) return fail("s3enc_forward: out must be 16-byte aligned");
+    if (check_out(out, fo, layer_stride, M * C)) return 1;
     if (((uintptr_t)e->aux_codewords & 15) || ((uintptr_t)e->aux_codeids & 7)) return fail("s3enc_forward_aux: misaligned output");
     long max_rows = 0;
     for (int i = 0; i < c.n_conv; ++i) max_rows = std::max(max_rows, L[i]);
@@ -511,23 +462,11 @@ int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int
         d_kst = (float2*)sb.take((size_t)B * (G > 0 ? G : 1) * sizeof(float2));
         if (!pass) HIP_TRY(e->small.ensure_on_stream(sb.off + 1024, st));
     }
-    if (tbl_bytes > e->slot_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (e->pinned) HIP_TRY(hipHostFree(e->pinned));
-        e->pinned = nullptr;
-        e->slot_bytes = tbl_bytes * 4 + 4096;
-        HIP_TRY(hipHostMalloc(&e->pinned, e->slot_bytes * s3enc_encoder::RING, hipHostMallocDefault));
-    }
-    {
-        const int slot = e->slot_next;
-        e->slot_next = (slot + 1) % s3enc_encoder::RING;
-        HIP_TRY(hipEventSynchronize(e->slot_ev[slot]));
-        char* hp = (char*)e->pinned + (size_t)slot * e->slot_bytes;
-        memcpy(hp, wav_ptrs_host, (size_t)B * 8);
-        for (int b = 0; b < B; ++b) ((long*)(hp + (size_t)B * 8))[b] = (long)lengths[b];
-        HIP_TRY(hipMemcpyAsync(d_tbl, hp, tbl_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(e->slot_ev[slot], st));
-    }
+    char* hp;
+    if (stage_begin(e, tbl_bytes, st, hp)) return 1;
+    memcpy(hp, wav_ptrs_host, (size_t)B * 8);
+    for (int b = 0; b < B; ++b) ((long*)(hp + (size_t)B * 8))[b] = (long)lengths[b];
+    if (stage_commit(e, hp, d_tbl, tbl_bytes, st)) return 1;
     const float* const* d_ptrs = (const float* const*)d_tbl;
     const long* d_lens = (const long*)(d_tbl + (size_t)B * 8);
 
@@ -562,29 +501,8 @@ int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int
     if (e->aux_codeids) ids = e->aux_codeids;
 
     // ---- where the states go ----
-    const int mode = fo.featurize ? 2 : 0;
-    bool first = true;
-    if (fo.featurize) {
-        bool any = false;
-        for (int i = 0; i < NS; ++i) any = any || fo.w[i] != 0.f;
-        if (!any) HIP_TRY(hipMemsetAsync(out, 0, (size_t)M * C * 4, st));
-    }
-    auto slot = [&](int si) -> float* { return mode == 0 ? (float*)out + (long)si * layer_stride : nullptr; };
-    auto acc = [&](int si) {
-        LnAcc a;
-        if (mode != 2 || fo.w[si] == 0.f) return a;
-        a.acc = (float*)out;
-        a.w = fo.w[si];
-        a.mode = 2;
-        a.norm = fo.feat_norm;
-        a.init = first;
-        first = false;
-        return a;
-    };
-    auto done = [&](int si) -> hipError_t {
-        if (mode == 2 || e->layer_events.empty() || si >= (int)e->layer_events.size()) return hipSuccess;
-        return hipEventRecord(e->layer_events[si], st);
-    };
+    Sink sink{e, st, fo.featurize ? 2 : 0, out, (long)layer_stride, F32, M, C, fo.w, fo.feat_norm};
+    HIP_TRY(sink.zero_without_terms(NS, M));
     auto stats = [&](const float* x, long rows) -> hipError_t {
         Prof pr(e, st, "gn1_stats", 0, 4.0 * B * rows * C);
         return launch_group1_stats(x, rows * C, rows * C, B, d_gpart, st);
@@ -664,8 +582,8 @@ int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int
                 a.pad_zero = c.agg_zero_pad;
                 a.dst_bs = (long)(pad0 + T) * C;
             }
-            a.state = slot(0);
-            a.acc = acc(0);
+            a.state = sink.slot32(0);
+            a.acc = sink.acc(0, 2);
         }
         {
             Prof pr(e, st, "gn1_apply", 0, 4.0 * B * L[i] * C * (last ? 3 : 2));
@@ -673,7 +591,7 @@ int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int
         }
         cur = raw;
     }
-    HIP_TRY(done(0));
+    HIP_TRY(sink.done(0));
 
     // ---- vector quantizer: codewords replace z as the aggregator's input ----
     if (c.vq_type) {
@@ -782,13 +700,13 @@ int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int
             a.pad_zero = c.agg_zero_pad;
             a.dst_bs = (long)(npad + T) * C;
         }
-        a.state = slot(j + 1);
-        a.acc = acc(j + 1);
+        a.state = sink.slot32(j + 1);
+        a.acc = sink.acc(j + 1, 2);
         {
             Prof pr(e, st, "gn1_apply", 0, 4.0 * M * C * (2 + (a.res ? 1 : 0) + (a.dst ? 1 : 0)));
             HIP_TRY(launch_gn1_apply(a, st));
         }
-        HIP_TRY(done(j + 1));
+        HIP_TRY(sink.done(j + 1));
         pin = pout;
     }
     return 0;
