@@ -61,7 +61,12 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * post-LN BERT layers (optionally one layer's weights run encoder_layers times), inputs over `sequence_length` frames
         * forwarded in chunks.  encoder_layers + 1 states of (B, T, embed_dim).  compute_dtype S3ENC_F32 only; built by
         * s3enc_create_mockingjay. */
-       S3ENC_MOCKINGJAY = 8 };
+       S3ENC_MOCKINGJAY = 8,
+       /* DeCoAR / DeCoAR-layers (upstream/decoar/{decoar,audio,expert}.py, upstream/decoar_layers/): a kaldi log-mel front end
+        * (hamming window, no deltas, CMVN over time), Linear 80 -> hidden, then a forward and a backward stack of unidirectional
+        * nn.LSTM layers on PACKED sequences, their outputs concatenated.  One state of (B, T, 2 hidden) — the last layer — or one per
+        * layer.  compute_dtype S3ENC_F32 only; built by s3enc_create_decoar. */
+       S3ENC_DECOAR = 9 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -253,6 +258,29 @@ typedef struct s3enc_mockingjay_config {
     float fbank_cmvn_eps;
 } s3enc_mockingjay_config;
 
+/* S3ENC_DECOAR only (decoar/decoar.py:9-83, decoar/audio.py:41-97, decoar_layers/decoar.py): the second configuration block of
+ * s3enc_create_decoar.  s3enc_config carries the frame geometry as a one-layer "conv stack": n_conv = 1, conv_kernel[0] /
+ * conv_stride[0] = the analysis window / the frame shift in samples (400 / 160; both multiples of 4), conv_dim = embed_dim =
+ * 2 hidden (the width of a state), encoder_layers = the number of states - 1 (0, or num_layers - 1 with per_layer_states).
+ * Front end: torchaudio.compliance.kaldi.fbank(num_mel_bins, window_type = hamming) at 16 kHz -> CMVN over time (unbiased std, eps
+ * 1e-10 added to the std), then every `subsample`-th frame: f fbank frames give ceil(f / subsample) model frames.  The reference's
+ * decoar / decoar_layers front end keeps every frame (subsample 1); 2 is the front end of DeCoAR 2.0 (decoar2/audio.py:84) and
+ * costs nothing here: the projection reads its rows at twice the stride.  Model: post_extract_proj (Linear), then per layer and
+ * direction an nn.LSTM layer on packed sequences — the backward stack on every utterance's own rows in reverse — and the two
+ * outputs side by side.  Checkpoint tensors, reference state_dict names: post_extract_proj.{weight,bias},
+ * {forward,backward}_lstm.{weight_ih,weight_hh,bias_ih,bias_hh}_lN, every one of them required.  Refused by name: every compute
+ * dtype but fp32, num_layers outside 1..4, hidden not a multiple of 64 or above 1024, subsample other than 1 or 2, window / shift
+ * that are not multiples of 4 samples. */
+typedef struct s3enc_decoar_config {
+    int32_t num_mel_bins;                           /* 80 */
+    int32_t hidden;                                 /* 1024 */
+    int32_t num_layers;                             /* 4 */
+    float frame_length_ms;                          /* 25 */
+    float frame_shift_ms;                           /* 10 */
+    int32_t subsample;                              /* 1 (decoar, decoar_layers) or 2 */
+    int32_t per_layer_states;                       /* 0: one state, the last layer (decoar); 1: one per layer (decoar_layers) */
+} s3enc_decoar_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -300,6 +328,15 @@ int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const
  * inside the buffer, and not the reference's values. */
 int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
                             int32_t device, s3enc_handle* out);
+/* The S3ENC_DECOAR family: s3enc_config beside its own block (the other create entries refuse the family by name).  Replaces
+ * UpstreamExpert.__init__ of upstream/decoar/expert.py and upstream/decoar_layers/expert.py (same checkpoint file and tensor names;
+ * the latter only renames them).  On the handle: s3enc_num_frames is ceil(fbank frames / subsample); an utterance with fewer than
+ * 2 fbank frames is refused by the forward (the reference's unbiased std over one frame is NaN); s3enc_downsample_rate is the
+ * frame shift in samples, 160, what the reference's get_downsample_rates returns whatever `subsample` is; s3enc_num_states is 1 or
+ * num_layers for S3ENC_SEL_HIDDEN (the other selections are refused), out_dtype must be S3ENC_F32, B <= 128.  Every state row
+ * behind an utterance's frame count is exactly 0. */
+int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* decoar, const s3enc_tensor* tensors, int32_t n_tensors,
+                        int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -633,6 +670,23 @@ int s3enc_op_rnn(int32_t cell, const float* pre, const float* w_hh_host, const f
 int s3enc_op_rnn_len(int32_t cell, const float* pre, const float* w_hh_host, const float* b_hn, const int32_t* len_host,
                      const float* res, int64_t ld_res, int32_t B, int32_t T, int32_t H, int64_t ld_pre, float* out, int64_t ldo,
                      void* stream);
+
+/* A forward and a backward unidirectional nn.LSTM on packed sequences, side by side, on the batch-shared kernel: one launch per
+ * time step for both directions, W_hh read once per step for the whole batch (fp32 MFMA).  pre_fwd / pre_bwd: device fp32, row
+ * (b, t) at pre + (b * T + t) * ld_pre, 4 H values (i, f, g, o) of x W_ih^T + b_ih + b_hh, both in the utterance's own time order.
+ * The forward direction runs rows 0 .. len - 1, the backward direction rows len - 1 .. 0 (what the reference gets by flipping
+ * every utterance before and after its backward stack); no flipped copy is made.  w_hh_fwd_host / w_hh_bwd_host: HOST fp32
+ * (4 H, H), packed and uploaded inside.  len_host: HOST int32 (B), each in 1..T.  out: device fp32, 16-byte aligned, row (b, t)
+ * at out + (b * T + t) * ldo: the forward h in columns [0, H), the backward h in [H, 2 H); rows [len, T) of both halves are
+ * written as zeros.  ldo % 4 == 0, ldo >= 2 H, ld_pre >= 4 H, H % 64 == 0, H <= 1024, B <= 128.  An utterance's bits depend
+ * neither on B, nor on its place in the batch, nor on the other lengths.  Synchronises. */
+int s3enc_op_lstm_bidir(const float* pre_fwd, const float* pre_bwd, const float* w_hh_fwd_host, const float* w_hh_bwd_host,
+                        const int32_t* len_host, int32_t B, int32_t T, int32_t H, int64_t ld_pre, float* out, int64_t ldo,
+                        void* stream);
+/* The host-side packer of that kernel's W_hh image, for tests: w_hh_host (4 H, H) -> out_host, 4 H * H floats laid out
+ * [H / 8 slices][H / 8 k blocks][64 lanes][4]: lane l of slice s and k block kb holds
+ * w[((l & 31) / 8) * H + 8 s + (l & 7)][8 kb + 4 (l >> 5) + j], j = 0..3.  Needs no device. */
+int s3enc_pack_lstm_bidir_whh(const float* w_hh_host, int32_t H, float* out_host);
 
 /* Convolutional position embedding + residual: out = x + GELU(SamePad(Conv1d(D, D, K, padding=K/2, groups=G)(x)) + bias)
  * (make_conv_pos / SamePad, wav2vec2_model.py:2937-2953,1797-1808).  x, out: device fp32 (B, T, D); w_host: HOST fp32

@@ -19,7 +19,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -88,6 +88,14 @@ class S3MockingjayConfig(C.Structure):
     ]
 
 
+class S3DecoarConfig(C.Structure):
+    """s3enc_decoar_config: the front-end / LSTM block of a DeCoAR handle (s3enc_create_decoar)."""
+    _fields_ = [
+        ("num_mel_bins", C.c_int32), ("hidden", C.c_int32), ("num_layers", C.c_int32), ("frame_length_ms", C.c_float),
+        ("frame_shift_ms", C.c_float), ("subsample", C.c_int32), ("per_layer_states", C.c_int32),
+    ]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -119,6 +127,7 @@ _PROTOS = {
     "s3enc_create_apc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3ApcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_mockingjay": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3MockingjayConfig), C.POINTER(S3Tensor), _I32, _I32,
                                           C.POINTER(_VP)]),
+    "s3enc_create_decoar": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3DecoarConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -164,6 +173,8 @@ _PROTOS = {
     "s3enc_op_channelnorm_relu": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_rnn": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I64, _VP, _I64, _VP]),
     "s3enc_op_rnn_len": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I64, _VP, _I64, _VP]),
+    "s3enc_op_lstm_bidir": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I64, _VP, _I64, _VP]),
+    "s3enc_pack_lstm_bidir_whh": (C.c_int, [_VP, _I32, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
@@ -341,4 +352,15 @@ def make_mockingjay_config(cfg) -> S3MockingjayConfig:
     c.fbank_preemphasis = float(cfg.mj_kaldi_preemphasis)
     c.fbank_delta_order, c.fbank_delta_win_length = int(cfg.mj_delta_order), int(cfg.mj_delta_win)
     c.fbank_use_cmvn, c.fbank_cmvn_eps = int(cfg.mj_cmvn), 1e-10
+    return c
+
+
+def make_decoar_config(cfg) -> S3DecoarConfig:
+    """The second configuration block of a ``family="decoar"`` EncoderConfig (``s3enc_create_decoar``)."""
+    if cfg.family != "decoar":
+        raise S3EncError("make_decoar_config needs a decoar configuration")
+    c = S3DecoarConfig()
+    c.num_mel_bins, c.hidden, c.num_layers = int(cfg.decoar_feat_dim), int(cfg.decoar_hidden), int(cfg.decoar_layers)
+    c.frame_length_ms, c.frame_shift_ms = float(cfg.decoar_frame_length), float(cfg.decoar_frame_shift)
+    c.subsample, c.per_layer_states = int(cfg.decoar_subsample), int(cfg.decoar_per_layer)
     return c

@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, config_from_apc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, decoar_config, config_from_apc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -70,6 +70,29 @@ def load_apc_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]
             raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: {key} is missing")
     cfg = config_from_apc(state["config"])
     return cfg, _hot_path_weights(ckpt, cfg, state["model"])
+
+
+def load_decoar_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"model": state_dict}`` (upstream/decoar/expert.py:30-36; decoar_layers/expert.py:30-47 reads the same file and renames
+    ``{forward,backward}_lstm.X_lN`` to its per-layer modules).  The file carries no configuration — the reference's ``Decoar()``
+    hard-codes 80 / 1024 / 4 — so the widths and the depth are read off the tensors.  The reference loads with ``strict=False``: a
+    missing tensor would silently keep its random initialisation, so every tensor the forward reads is required here."""
+    import re
+
+    import torch
+
+    state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    if "model" not in state:
+        raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: model is missing")
+    sd = state["model"]
+    if "post_extract_proj.weight" not in sd:
+        raise ValueError(f"{ckpt}: missing parameter post_extract_proj.weight")
+    hidden, feat_dim = (int(v) for v in sd["post_extract_proj.weight"].shape)
+    layers = {int(m.group(1)) for m in (re.fullmatch(r"forward_lstm\.weight_hh_l(\d+)", k) for k in sd) if m}
+    if not layers or layers != set(range(len(layers))):
+        raise ValueError(f"{ckpt}: missing parameter forward_lstm.weight_hh_l{min(set(range(len(layers) + 1)) - layers)}")
+    cfg = decoar_config(hidden, len(layers), False, feat_dim)
+    return cfg, _hot_path_weights(ckpt, cfg, sd)
 
 
 def mockingjay_state_dict(sd) -> Dict:
@@ -157,6 +180,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_apc_checkpoint(ckpt)
     if family == "mockingjay":
         return load_mockingjay_checkpoint(ckpt)
+    if family == "decoar":
+        return load_decoar_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -207,6 +232,9 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
     if cfg.family == "mockingjay":  # upstream/mockingjay/builder.py:59-76
         # new-style files keep the runner's config under "Config" and the reference's builder reads that key first
         torch.save({"Transformer": sd, "Upstream_Config": mockingjay_upstream_config(cfg), "Config": {"runner": {}}}, path)
+        return
+    if cfg.family == "decoar":  # upstream/decoar/expert.py:30-36
+        torch.save({"model": sd}, path)
         return
     if cfg.family == "apc":  # upstream/apc/expert.py:22-27
         audio = dict(feat_type=cfg.apc_feat_type, feat_dim=cfg.apc_feat_dim, frame_length=cfg.apc_frame_length,

@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -164,6 +164,17 @@ class EncoderConfig:
     mj_kaldi_preemphasis: float = 0.97
     mj_delta_order: int = 2           # audio.delta.order (kaldi)
     mj_delta_win: int = 5             # audio.delta.win_length
+    # DeCoAR / DeCoAR-layers (family "decoar", upstream/decoar/{decoar,audio,expert}.py, upstream/decoar_layers/): a kaldi log-mel
+    # front end (hamming, CMVN over time), Linear feat_dim -> hidden, a forward and a backward stack of ``decoar_layers``
+    # unidirectional LSTM layers on packed sequences, concatenated.  ``conv_layers`` = [(2 * hidden, window, shift)] in samples
+    # carries the frame geometry and the state width; ``encoder_layers`` = the number of states - 1
+    decoar_feat_dim: int = 80           # num_mel_bins
+    decoar_hidden: int = 1024           # d
+    decoar_layers: int = 4              # encoder_layers of the reference's Decoar()
+    decoar_frame_length: float = 25.0   # ms (kaldi.fbank's default)
+    decoar_frame_shift: float = 10.0    # ms
+    decoar_subsample: int = 1           # every n-th frame: 1 (decoar/audio.py keeps them all) or 2 (decoar2/audio.py:84)
+    decoar_per_layer: bool = False      # False: one state, the last layer (decoar); True: one per layer (decoar_layers)
 
     # ---- derived -------------------------------------------------------------------------
     @property
@@ -205,6 +216,8 @@ class EncoderConfig:
     def num_frames(self, n: int) -> int:
         if self.family == "mockingjay" and self.mj_frontend == "mel":  # centred STFT frames; torch.stft refuses n <= 200
             return 1 + n // 160 if n > 200 else 0
+        if self.family == "decoar":  # ceil(fbank frames / subsample)
+            return -(-self.conv_lengths(n)[-1] // self.decoar_subsample)
         return self.conv_lengths(n)[-1]
 
     def valid_frames(self, length: int, n_max: int) -> int:
@@ -223,7 +236,7 @@ class EncoderConfig:
             return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
         if self.family == "mockingjay":
             return min(T, max(self.num_frames(length), 0))
-        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length
+        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -328,6 +341,8 @@ class EncoderConfig:
             return self._validate_apc()
         if self.family == "mockingjay":
             return self._validate_mockingjay()
+        if self.family == "decoar":
+            return self._validate_decoar()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -429,6 +444,29 @@ class EncoderConfig:
             raise ValueError(f"apc feat_dim must be a multiple of 4, at most 256, got {self.apc_feat_dim}")
         if self.encoder_layers != 2 or self.encoder_embed_dim != H:
             raise ValueError("apc: encoder_layers / encoder_embed_dim must be 2 / hidden_size (apc_config sets them)")
+
+    def _validate_decoar(self) -> None:
+        """What the HIP path builds of DeCoAR; everything else is refused by name (s3enc_create_decoar repeats it)."""
+        H = self.decoar_hidden
+        if not 1 <= self.decoar_layers <= 4:
+            raise ValueError(f"decoar num_layers must be 1..4, got {self.decoar_layers}")
+        if H % 64 or not 64 <= H <= 1024:
+            raise ValueError(f"decoar hidden must be a multiple of 64, at most 1024 (the batch-shared recurrent kernel's limit), got {H}")
+        if self.decoar_subsample not in (1, 2):
+            raise ValueError(f"decoar subsample must be 1 or 2, got {self.decoar_subsample}")
+        if self.decoar_feat_dim % 4 or not 4 <= self.decoar_feat_dim <= 256:
+            raise ValueError(f"decoar num_mel_bins must be a multiple of 4, at most 256, got {self.decoar_feat_dim}")
+        if len(self.conv_layers) != 1:
+            raise ValueError("decoar: conv_layers carries the frame geometry as one (2 * hidden, window, shift) entry (decoar_config sets it)")
+        D, size, shift = self.conv_layers[0]
+        if (size, shift) != (int(16000 * self.decoar_frame_length * 0.001), int(16000 * self.decoar_frame_shift * 0.001)):
+            raise ValueError("decoar: conv_layers does not match frame_length / frame_shift (decoar_config sets it)")
+        if size < 4 or shift < 4 or size % 4 or shift % 4:
+            raise ValueError(f"decoar frame_length / frame_shift of {size} / {shift} samples are not built: both must be a multiple of 4 "
+                             "samples (the front end's GEMM reads 16-byte vectors)")
+        if D != 2 * H or self.encoder_embed_dim != 2 * H or self.encoder_layers != (self.decoar_layers - 1 if self.decoar_per_layer else 0):
+            raise ValueError("decoar: conv_dim / encoder_embed_dim must be 2 * hidden and encoder_layers the number of states - 1 "
+                             "(decoar_config sets them)")
 
     def _validate_mockingjay(self) -> None:
         """What the HIP path builds of the Mockingjay configuration; everything else is refused by name (s3enc_create_mockingjay
@@ -601,6 +639,20 @@ def config_from_apc(config: Dict) -> EncoderConfig:
             raise ValueError(f"apc checkpoint: model.paras.{key} is missing")
     return apc_config(paras["hidden_size"], paras["num_layers"], paras["residual"], feat_dim, frame_length, frame_shift, cmvn,
                       paras.get("vq"), apc_feat_type=str(feat_type))
+
+
+def decoar_config(hidden: int = 1024, num_layers: int = 4, per_layer: bool = False, feat_dim: int = 80, subsample: int = 1,
+                  frame_length: float = 25.0, frame_shift: float = 10.0, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "decoar" (decoar/decoar.py:9-39: the reference hard-codes 80 / 1024 / 4)."""
+    H = int(hidden)
+    size, shift = int(16000 * float(frame_length) * 0.001), int(16000 * float(frame_shift) * 0.001)
+    cfg = EncoderConfig(family="decoar", conv_layers=[(2 * H, size, shift)], encoder_embed_dim=2 * H,
+                        encoder_layers=int(num_layers) - 1 if per_layer else 0, decoar_feat_dim=int(feat_dim), decoar_hidden=H,
+                        decoar_layers=int(num_layers), decoar_frame_length=float(frame_length),
+                        decoar_frame_shift=float(frame_shift), decoar_subsample=int(subsample), decoar_per_layer=bool(per_layer),
+                        **flags)
+    cfg.validate()
+    return cfg
 
 
 def mockingjay_config(hidden: int = 768, layers: int = 3, heads: int = 12, intermediate: int = 3072, input_dim: int = 80,

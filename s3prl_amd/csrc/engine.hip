@@ -155,11 +155,12 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 8) return fail("config: unknown family");
+    if (c.family < 0 || c.family > 9) return fail("config: unknown family");
     if (c.family == S3ENC_WAV2VEC) return 0;  // s3enc_create_ex: wav2vec_check_config on both configuration blocks
     if (c.family == S3ENC_CPC) return 0;      // s3enc_create_cpc: cpc_check_config on both configuration blocks
     if (c.family == S3ENC_APC) return 0;      // s3enc_create_apc: apc_check_config on both configuration blocks
     if (c.family == S3ENC_MOCKINGJAY) return 0;  // s3enc_create_mockingjay: mj_check_config on both configuration blocks
+    if (c.family == S3ENC_DECOAR) return 0;      // s3enc_create_decoar: decoar_check_config on both configuration blocks
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
         const int k = c.mr_kernel;
@@ -240,6 +241,7 @@ static int wrong_entry(const char* entry, int own, int family) {
         {S3ENC_APC, "apc", "S3ENC_APC", "s3enc_create_apc", "the APC family needs its front-end / GRU block"},
         {S3ENC_MOCKINGJAY, "mockingjay", "S3ENC_MOCKINGJAY", "s3enc_create_mockingjay",
          "the Mockingjay / TERA / AudioALBERT family needs its front-end block"},
+        {S3ENC_DECOAR, "decoar", "S3ENC_DECOAR", "s3enc_create_decoar", "the DeCoAR family needs its front-end / LSTM block"},
     };
     if (family == own) return 0;
     for (const auto& f : F)
@@ -259,8 +261,8 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
-                       int32_t device, s3enc_handle* out);
+                       const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_decoar_config* dc,
+                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
 
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out) {
@@ -268,7 +270,7 @@ int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, co
         if (out) *out = nullptr;
         return 1;
     }
-    return create_impl(cfg, w2v, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, w2v, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -276,7 +278,7 @@ int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const
     if (!cfg || !cpc || !tensors || !out) return fail("s3enc_create_cpc: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_cpc", S3ENC_CPC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, cpc, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, cpc, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -284,7 +286,7 @@ int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const
     if (!cfg || !apc || !tensors || !out) return fail("s3enc_create_apc: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_apc", S3ENC_APC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, apc, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, apc, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -292,12 +294,20 @@ int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_conf
     if (!cfg || !mj || !tensors || !out) return fail("s3enc_create_mockingjay: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_mockingjay", S3ENC_MOCKINGJAY, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, mj, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, nullptr, mj, nullptr, tensors, n_tensors, device, out);
+}
+
+int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* decoar, const s3enc_tensor* tensors, int32_t n_tensors,
+                        int32_t device, s3enc_handle* out) {
+    if (!cfg || !decoar || !tensors || !out) return fail("s3enc_create_decoar: null argument");
+    *out = nullptr;
+    if (wrong_entry("s3enc_create_decoar", S3ENC_DECOAR, cfg->family)) return 1;
+    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, decoar, tensors, n_tensors, device, out);
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
-                       int32_t device, s3enc_handle* out) {
+                       const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_decoar_config* dc,
+                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
@@ -308,6 +318,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         case S3ENC_CPC: if (cpc_check_config(*cfg, *cpc)) return 1; break;
         case S3ENC_APC: if (apc_check_config(*cfg, *apc)) return 1; break;
         case S3ENC_MOCKINGJAY: if (mj_check_config(*cfg, *mj)) return 1; break;
+        case S3ENC_DECOAR: if (decoar_check_config(*cfg, *dc)) return 1; break;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -334,6 +345,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         case S3ENC_CPC: e->cpc_cfg = *cpc; family_rc = cpc_create(e.get(), ck); break;
         case S3ENC_APC: e->apc_cfg = *apc; family_rc = apc_create(e.get(), ck); break;
         case S3ENC_MOCKINGJAY: e->mj_cfg = *mj; family_rc = mj_create(e.get(), ck); break;
+        case S3ENC_DECOAR: e->decoar_cfg = *dc; family_rc = decoar_create(e.get(), ck); break;
     }
     if (family_rc >= 0) return family_rc ? 1 : finish_create(std::move(e), out);
     const s3enc_config& c = e->cfg;
@@ -756,6 +768,10 @@ int s3enc_num_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
         *T = (int32_t)mj_num_frames(h->cfg, h->mj_cfg, n_samples);
         return 0;
     }
+    if (h->cfg.family == S3ENC_DECOAR) {
+        *T = (int32_t)decoar_num_frames(h->cfg, h->decoar_cfg, n_samples);
+        return 0;
+    }
     *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
                                               : conv_len(h->cfg, n_samples, h->cfg.n_conv));
     return 0;
@@ -764,6 +780,10 @@ int s3enc_num_output_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
     if (!h || !T) return fail("s3enc_num_output_frames: null argument");
     if (h->cfg.family == S3ENC_MOCKINGJAY) {
         *T = (int32_t)mj_num_frames(h->cfg, h->mj_cfg, n_samples);
+        return 0;
+    }
+    if (h->cfg.family == S3ENC_DECOAR) {
+        *T = (int32_t)decoar_num_frames(h->cfg, h->decoar_cfg, n_samples);
         return 0;
     }
     *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
@@ -787,6 +807,11 @@ int s3enc_valid_frames(s3enc_handle h, int64_t length, int64_t n_max, int32_t* v
     }
     if (h->cfg.family == S3ENC_MOCKINGJAY) {  // mel + CMVN: round(length / (n_max / T)), batch-dependent
         *valid = mj_valid_frames(h->cfg, h->mj_cfg, length, n_max);
+        return 0;
+    }
+    if (h->cfg.family == S3ENC_DECOAR) {  // the utterance's own frame count (its packed length)
+        const long T = decoar_num_frames(h->cfg, h->decoar_cfg, n_max), v = decoar_num_frames(h->cfg, h->decoar_cfg, length);
+        *valid = (int32_t)(T <= 0 ? 0 : std::max(0L, std::min(v, T)));
         return 0;
     }
     *valid = valid_frames(h->cfg, length, n_max);
@@ -1061,6 +1086,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         case S3ENC_CPC: return cpc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
         case S3ENC_APC: return apc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
         case S3ENC_MOCKINGJAY: return mj_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+        case S3ENC_DECOAR: return decoar_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     }
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
@@ -1809,6 +1835,8 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
         return fail("s3enc_num_states: feature_selection is not defined for APC (one hidden_states list of 3 states)");
     if (h->cfg.family == S3ENC_MOCKINGJAY && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: feature_selection is not defined for Mockingjay / TERA / AudioALBERT (one hidden_states list)");
+    if (h->cfg.family == S3ENC_DECOAR && selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_num_states: feature_selection is not defined for DeCoAR (one hidden_states list)");
     *n = num_states(h->cfg, selection);
     return 0;
 }

@@ -7,6 +7,7 @@
 //   multires.hip  the multires-HuBERT U-net behind post_extract_proj
 //   wav2vec.hip / cpc.hip  the convolutional families (wav2vec, modified CPC); rnn.hip: the LSTM / GRU recurrence
 //   apc.hip / mockingjay.hip  the log-mel families (APC / VQ-APC on GRU layers; Mockingjay / TERA / AudioALBERT on BERT layers)
+//   decoar.hip  DeCoAR: the log-mel front end, a projection and two LSTM stacks on rnnb.hip's batch-shared step
 //   (a family file holds its configuration check, its weights and its forward schedule: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
 #pragma once
@@ -411,6 +412,14 @@ struct CpcW : RnnW {
 // APC / VQ-APC (apc.hip): GRU layers (I = the mel bins for layer 0)
 using ApcW = RnnW;
 
+// DeCoAR (decoar.hip): post_extract_proj; per layer the input projections of both stacks and their weight_hh in rnnb.hip's layout.
+// Layer 0's two projections read the same rows and are stacked as one (8 H, H) operand; the later layers keep one per direction.
+struct DecoarW {
+    DevBuf proj_w, proj_b;
+    std::vector<DevBuf> w_ih[2], b_pre[2], w_hh[2];  // [0] forward_lstm, [1] backward_lstm
+    DevBuf w_ih0, b_pre0;                            // layer 0: forward rows, then backward rows
+};
+
 // Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table, and per layer (ONE layer with
 // share_layer) q|k|v stacked as one (3 D, D) operand with q pre-scaled by head_dim^-0.5, the other projections and LayerNorm affines
 struct MjLayerW {
@@ -484,6 +493,8 @@ struct s3enc_encoder {
     s3enc_apc_config apc_cfg = {};      // ... and its second configuration block (s3enc_create_apc)
     std::unique_ptr<MjW> mj;            // S3ENC_MOCKINGJAY
     s3enc_mockingjay_config mj_cfg = {};  // ... and its second configuration block (s3enc_create_mockingjay)
+    std::unique_ptr<DecoarW> decoar;    // S3ENC_DECOAR
+    s3enc_decoar_config decoar_cfg = {};  // ... and its second configuration block (s3enc_create_decoar)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -773,6 +784,12 @@ int apc_create(s3enc_encoder* e, const Ckpt& ck);
 int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 
+// decoar.hip: the S3ENC_DECOAR family (kaldi log-mel front end + Linear + forward / backward LSTM stacks on packed sequences)
+int decoar_check_config(const s3enc_config& c, const s3enc_decoar_config& x);
+int decoar_create(s3enc_encoder* e, const Ckpt& ck);
+long decoar_num_frames(const s3enc_config& c, const s3enc_decoar_config& x, long n_samples);  // ceil(fbank frames / subsample)
+int decoar_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 // mockingjay.hip: the S3ENC_MOCKINGJAY family (spectrogram front end + input representation + post-LN BERT layers, chunked)
 int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x);
 int mj_create(s3enc_encoder* e, const Ckpt& ck);

@@ -469,6 +469,32 @@ bool rnn_split_ok(int H, int B, int S);
 int rnn_split_pick(int cell, int H, int B);  // tuning().rnn_split, or its default rule: 0 = launch_rnn_len, S = launch_rnn_step
 hipError_t launch_rnn_step(const RnnStepParams& p, hipStream_t s);
 
+// ---- rnnb.hip (the batch-shared bidirectional LSTM step: W_hh read once per step for the whole batch, fp32 MFMA) ------------
+constexpr int RNNB_H_MAX = 1024;  // hidden width limit (a multiple of 64)
+constexpr int RNNB_B_MAX = 128;   // four 32-wide batch tiles per workgroup
+struct RnnbParams {
+    const float* pre_fwd;  // row (b, t) at pre + (b * T + t) * ld_pre: 4 H values (i, f, g, o), x W_ih^T + b_ih + b_hh
+    const float* pre_bwd;  // the backward stack's, in the utterance's own time order (no flip)
+    const float* w_fwd;    // pack_rnnb_whh image of the forward stack's weight_hh
+    const float* w_bwd;
+    const int* len;        // device [B], each in 1..T
+    int B, T, H;
+    long ld_pre;
+    float* out;            // row (b, t) at out + (b * T + t) * ldo: forward h in columns [0, H), backward h in [H, 2 H)
+    long ldo;              // a multiple of 4, at least 2 H
+    int max_len;           // the largest len[b] (host): the number of launches
+    int t;                 // (set per launch)
+    float* hbuf;           // device, 2 * rnnb_state_elems floats: h ping-pong of both directions; need not be initialised
+    float* cbuf;           // device, rnnb_state_elems floats
+};
+// host: weight_hh (4 H, H) -> [H / 8 slices][H / 8 k blocks][64 lanes][4]: lane l of slice s, k block kb holds
+// w[(l & 31) / 8 * H + 8 s + (l & 7)][8 kb + 4 (l >> 5) + j], j = 0..3 — a workgroup's 32 rows are contiguous
+void pack_rnnb_whh(const float* w, int H, std::vector<float>& out);
+int rnnb_batch_pad(int B);                  // columns of the state buffers: 32, 64 or 128
+size_t rnnb_state_elems(int B, int H);      // floats of cbuf (hbuf: twice that)
+const char* rnnb_refusal(const RnnbParams& p);  // null, or why launch_rnnb would refuse
+hipError_t launch_rnnb(const RnnbParams& p, hipStream_t s);
+
 // ---- featurizer.hip (weighted sum over layers, the consumer of hidden_states) ---------------------
 #define S3_WS_MAX_LAYERS 32
 // out[row] = sum_l w[l] * (normalize ? layer_norm(hs[l][row]) : hs[l][row]);  w: HOST array (softmax already applied,

@@ -385,6 +385,58 @@ int s3enc_op_rnn_len(int32_t cell, const float* pre, const float* w_hh_host, con
     return 0;
 }
 
+int s3enc_pack_lstm_bidir_whh(const float* w_hh_host, int32_t H, float* out_host) {
+    if (!w_hh_host || !out_host) return fail("s3enc_pack_lstm_bidir_whh: null argument");
+    if (H < 64 || H % 64 || H > RNNB_H_MAX) return fail("s3enc_pack_lstm_bidir_whh: H must be a multiple of 64, at most 1024");
+    std::vector<float> packed;
+    pack_rnnb_whh(w_hh_host, H, packed);
+    std::copy(packed.begin(), packed.end(), out_host);
+    return 0;
+}
+
+int s3enc_op_lstm_bidir(const float* pre_fwd, const float* pre_bwd, const float* w_hh_fwd_host, const float* w_hh_bwd_host,
+                        const int32_t* len_host, int32_t B, int32_t T, int32_t H, int64_t ld_pre, float* out, int64_t ldo, void* stream) {
+    if (!pre_fwd || !pre_bwd || !w_hh_fwd_host || !w_hh_bwd_host || !len_host || !out) return fail("s3enc_op_lstm_bidir: null argument");
+    if (B <= 0 || T <= 0) return fail("s3enc_op_lstm_bidir: bad shape");
+    RnnbParams p{};
+    p.pre_fwd = pre_fwd;
+    p.pre_bwd = pre_bwd;
+    p.B = B;
+    p.T = T;
+    p.H = H;
+    p.ld_pre = ld_pre;
+    p.out = out;
+    p.ldo = ldo;
+    // the checks that need no device memory first: placeholders stand in for the buffers allocated below
+    alignas(16) static float stand_in[4];
+    p.w_fwd = p.w_bwd = stand_in;
+    p.len = (const int*)len_host;
+    p.hbuf = p.cbuf = stand_in;
+    if (const char* why = rnnb_refusal(p)) return fail(std::string("s3enc_op_lstm_bidir: ") + why);
+    for (int b = 0; b < B; ++b)
+        if (len_host[b] < 1 || len_host[b] > T) return fail("s3enc_op_lstm_bidir: every length must be in 1..T");
+    std::vector<float> packed;
+    DevBuf dwf, dwb, dl, dh, dc;
+    pack_rnnb_whh(w_hh_fwd_host, H, packed);
+    HIP_TRY(upload_f32(dwf, packed));
+    pack_rnnb_whh(w_hh_bwd_host, H, packed);
+    HIP_TRY(upload_f32(dwb, packed));
+    HIP_TRY(dl.ensure((size_t)B * sizeof(int)));
+    HIP_TRY(hipMemcpy(dl.p, len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(dh.ensure(2 * rnnb_state_elems(B, H) * sizeof(float)));
+    HIP_TRY(dc.ensure(rnnb_state_elems(B, H) * sizeof(float)));
+    p.w_fwd = (const float*)dwf.p;
+    p.w_bwd = (const float*)dwb.p;
+    p.len = (const int*)dl.p;
+    p.hbuf = (float*)dh.p;
+    p.cbuf = (float*)dc.p;
+    p.max_len = *std::max_element(len_host, len_host + B);
+    if (const char* why = rnnb_refusal(p)) return fail(std::string("s3enc_op_lstm_bidir: ") + why);
+    HIP_TRY(launch_rnnb(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights, the lengths and the state are freed on return
+    return 0;
+}
+
 int s3enc_op_argmax_gather(const float* scores, const float* table, int32_t shared, int64_t rows, int32_t G, int32_t V, int32_t Dv,
                            int64_t* ids, float* out, void* stream) {
     if (!scores || (!ids && !out) || (out && !table)) return fail("s3enc_op_argmax_gather: null argument");

@@ -36,6 +36,8 @@ class HipEncoder:
             raise ValueError(f"APC / VQ-APC are built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "mockingjay" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             raise ValueError(f"Mockingjay / TERA / AudioALBERT are built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "decoar" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"DeCoAR is built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -73,6 +75,9 @@ class HipEncoder:
             elif cfg.family == "mockingjay":  # its front end and input representation travel beside the (unchanged) s3enc_config
                 mj = _lib.make_mockingjay_config(cfg)
                 rc = self._lib.s3enc_create_mockingjay(C.byref(ccfg), C.byref(mj), tensors, len(weights), self.device, C.byref(h))
+            elif cfg.family == "decoar":  # its front end and LSTM stacks travel beside the (unchanged) s3enc_config
+                dc = _lib.make_decoar_config(cfg)
+                rc = self._lib.s3enc_create_decoar(C.byref(ccfg), C.byref(dc), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")
@@ -181,6 +186,12 @@ class HipEncoder:
         if self.cfg.family == "apc" and min(self.num_frames(n) for n in lengths) < 1:
             raise ValueError(f"an utterance of {min(lengths)} samples is shorter than one analysis window of the APC front end "
                              f"({self.cfg.conv_layers[0][1]} samples)")
+        if self.cfg.family == "decoar":
+            if B > 128:
+                raise ValueError(f"a DeCoAR batch holds at most 128 utterances (the batch-shared recurrent kernel's limit), got {B}")
+            if min(self.cfg.conv_lengths(n)[-1] for n in lengths) < 2:
+                raise ValueError(f"an utterance of {min(lengths)} samples has fewer than 2 analysis windows (DeCoAR's front end "
+                                 "normalises by the standard deviation over time: one frame has none)")
         if self.cfg.family == "mockingjay" and self.cfg.mj_frontend == "mel" and min(lengths) <= 200:
             raise ValueError(f"an utterance of {min(lengths)} samples has no reflect-padded centred STFT frame (torch.stft refuses "
                              "n <= 200 samples)")

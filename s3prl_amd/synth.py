@@ -28,6 +28,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _apc_shapes(cfg)
     if cfg.family == "mockingjay":
         return _mockingjay_shapes(cfg)
+    if cfg.family == "decoar":
+        return _decoar_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -203,6 +205,20 @@ def _apc_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     return s
 
 
+def _decoar_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """Decoar (upstream/decoar/decoar.py:21-39), the checkpoint's names: the projection and the two multi-layer nn.LSTM modules
+    (decoar_layers/expert.py:35-47 renames them to its per-layer modules; both experts read this one file)."""
+    H = cfg.decoar_hidden
+    s: Dict[str, tuple] = {"post_extract_proj.weight": (H, cfg.decoar_feat_dim), "post_extract_proj.bias": (H,)}
+    for stack in ("forward_lstm", "backward_lstm"):
+        for l in range(cfg.decoar_layers):
+            s[f"{stack}.weight_ih_l{l}"] = (4 * H, H)
+            s[f"{stack}.weight_hh_l{l}"] = (4 * H, H)
+            s[f"{stack}.bias_ih_l{l}"] = (4 * H,)
+            s[f"{stack}.bias_hh_l{l}"] = (4 * H,)
+    return s
+
+
 def _mockingjay_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     """TransformerModel (upstream/mockingjay/model.py:102-386), reference state_dict names of the checkpoint's ``Transformer``.
     With ``share_layer`` the ModuleList holds one module under every index: only ``encoder.layer.0`` is a hot-path parameter."""
@@ -367,6 +383,13 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
             gain = 1.5 if "weight_hh" in name else (2.5 if name.startswith("rnn_layers.0.") else 4.0)
             w = rng.standard_normal(shape) * (gain / np.sqrt(shape[1]))
         elif name.startswith("rnn_layers.") and ".bias_" in name:
+            w = 0.1 * rng.standard_normal(shape)
+        elif name.startswith(("forward_lstm.weight", "backward_lstm.weight")):
+            # DeCoAR's LSTM stacks, by the rule above: layer 0 reads the projection (unit variance: 2.5 / sqrt(fan_in)), the layers
+            # behind read hidden states of RMS 0.2-0.5
+            gain = 1.5 if "weight_hh" in name else (2.5 if name.endswith("_l0") else 6.0)
+            w = rng.standard_normal(shape) * (gain / np.sqrt(shape[1]))
+        elif name.startswith(("forward_lstm.bias", "backward_lstm.bias")):
             w = 0.1 * rng.standard_normal(shape)
         elif name in ("vector_quantizer.embedding", "vector_quantizer.vars"):
             # codebooks at the scale of what they are compared with / replace (a trained k-means embedding lives where the
@@ -544,6 +567,21 @@ def named_config(name: str) -> EncoderConfig:
         from .config import apc_config
 
         return apc_config(**apc[name])
+    # DeCoAR / DeCoAR-layers: the same front end, Linear 80 -> H, a forward and a backward LSTM stack on packed sequences
+    decoar = {
+        "tiny_decoar": dict(hidden=64, num_layers=2),
+        "tiny_decoar_layers": dict(hidden=64, num_layers=3, per_layer=True),
+        "tiny_decoar_l1": dict(hidden=64, num_layers=1),
+        "tiny_decoar_h192": dict(hidden=192, num_layers=2, per_layer=True),
+        "tiny_decoar_sub2": dict(hidden=64, num_layers=2, per_layer=True, subsample=2),
+        # the released shape (decoar/decoar.py hard-codes it): one state for `decoar`, four for `decoar_layers`
+        "decoar": dict(hidden=1024, num_layers=4),
+        "decoar_layers": dict(hidden=1024, num_layers=4, per_layer=True),
+    }
+    if name in decoar:
+        from .config import decoar_config
+
+        return decoar_config(**decoar[name])
     # Mockingjay / TERA / AudioALBERT: a log-mel (or kaldi fbank) front end into post-LN BERT layers, long inputs in chunks
     tiny_mj = dict(hidden=128, layers=2, heads=2, intermediate=256, input_dim=16, sequence_length=0)
     mj = {
@@ -566,7 +604,7 @@ def named_config(name: str) -> EncoderConfig:
 
         return mockingjay_config(**mj[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(mj))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(mj))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
