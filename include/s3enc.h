@@ -66,7 +66,13 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * (hamming window, no deltas, CMVN over time), Linear 80 -> hidden, then a forward and a backward stack of unidirectional
         * nn.LSTM layers on PACKED sequences, their outputs concatenated.  One state of (B, T, 2 hidden) — the last layer — or one per
         * layer.  compute_dtype S3ENC_F32 only; built by s3enc_create_decoar. */
-       S3ENC_DECOAR = 9 };
+       S3ENC_DECOAR = 9,
+       /* NPC (upstream/npc/{npc,audio,expert}.py): APC's kaldi log-mel front end (hamming window, CMVN over time), then n_blocks
+        * ConvBlocks (Conv1d k = 3 -> BatchNorm -> act -> Conv1d k = 1 -> BatchNorm -> + input -> act) each followed by a masked
+        * Conv1d (kernel_size taps with a hole of mask_size + 2 (i + 1) in the middle) -> tanh, summed over the blocks.  No length
+        * masking anywhere: 2 n_blocks + 1 states of (B, T, hidden) (n_blocks + 2 with disable_cross_layer) whose rows behind an
+        * utterance's own frames are the reference's values, not zeros.  compute_dtype S3ENC_F32 only; built by s3enc_create_npc. */
+       S3ENC_NPC = 10 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -281,6 +287,40 @@ typedef struct s3enc_decoar_config {
     int32_t per_layer_states;                       /* 0: one state, the last layer (decoar); 1: one per layer (decoar_layers) */
 } s3enc_decoar_config;
 
+/* S3ENC_NPC only (npc/npc.py:21-248, npc/audio.py:53-115, npc/expert.py:18-53): the second configuration block of
+ * s3enc_create_npc.  s3enc_config carries the frame geometry as APC does: n_conv = 1, conv_kernel[0] / conv_stride[0] = the
+ * analysis window / the frame shift in samples (400 / 160; both multiples of 4), conv_dim = embed_dim = hidden, encoder_layers =
+ * the number of states - 1 (2 n_blocks, or n_blocks + 1 with disable_cross_layer).  Front end: APC's (s3enc_apc_config).
+ * Model, eval mode: block i is x' = act(BN2(Conv1d_1(act(BN1(Conv1d_3(x))))) [+ x when residual and i > 0]) with BatchNorm on its
+ * running statistics (eps 1e-5) when `batch_norm`, folded into the convolutions at load; masked conv i is
+ * tanh(Conv1d(hidden, hidden, kernel_size, padding = (kernel_size - 1) / 2)) with taps [head, head + m_i) zeroed, m_i = mask_size
+ * + 2 (i + 1), head = (kernel_size - m_i) / 2 — those taps are never read; the running sum of the masked outputs is the last
+ * state.  With disable_cross_layer only the last block has a masked conv.  States in the reference's hook order: blocks[0],
+ * masked_convs[0], blocks[1], masked_convs[1], ..., the sum (disable_cross_layer: the blocks, the last masked conv, and that
+ * tensor again).  Checkpoint tensors, reference state_dict names: blocks.N.{conv,linear}.{weight,bias},
+ * blocks.N.{bn1,bn2}.{weight,bias,running_mean,running_var} (batch_norm), masked_convs.N.conv.{weight,bias}, every one required;
+ * masked_convs.N.conv_mask is optional and, when given, must equal the mask computed from this block; vq_layers.* and postnet.*
+ * feed only the prediction the upstream discards: accepted and not uploaded.  s3enc_create_npc refuses by name: every compute
+ * dtype but fp32, even kernel_size or mask_size, a mask that leaves no tap in some block, n_blocks outside 1..8, hidden not a
+ * multiple of 64 or above 1024, num_mel_bins not a multiple of 16, activate other than 0 / 1, window / shift that are not
+ * multiples of 4 samples, dim_bottleneck (a last state of another width). */
+typedef struct s3enc_npc_config {
+    int32_t num_mel_bins;                           /* feat_dim: 80 */
+    float frame_length_ms;                          /* 25 */
+    float frame_shift_ms;                           /* 10 */
+    int32_t window;                                 /* 0 povey, 1 hamming (the reference's WINDOW_TYPE) */
+    int32_t cmvn;                                   /* apply_cmvn */
+    int32_t hidden;                                 /* hidden_size: 512 */
+    int32_t n_blocks;                               /* 4 */
+    int32_t kernel_size;                            /* 15 */
+    int32_t mask_size;                              /* 5 */
+    int32_t residual;                               /* 1 */
+    int32_t batch_norm;                             /* 1 */
+    int32_t activate;                               /* 0 relu, 1 tanh */
+    int32_t disable_cross_layer;                    /* 0 */
+    int32_t dim_bottleneck;                         /* 0: none; the auto-encoder bottleneck gives the last state another width (refused) */
+} s3enc_npc_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -337,6 +377,16 @@ int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_conf
  * behind an utterance's frame count is exactly 0. */
 int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* decoar, const s3enc_tensor* tensors, int32_t n_tensors,
                         int32_t device, s3enc_handle* out);
+/* The S3ENC_NPC family: s3enc_config beside its own block (the other create entries refuse the family by name).  Replaces
+ * UpstreamExpert.__init__ of upstream/npc/expert.py.  On the handle: s3enc_num_frames is the fbank frame count; an utterance
+ * shorter than one window is refused by the forward; s3enc_downsample_rate is the frame shift in samples, 160;
+ * s3enc_num_states is encoder_layers + 1 for S3ENC_SEL_HIDDEN (the other selections are refused), out_dtype must be S3ENC_F32.
+ * s3enc_valid_frames is the utterance's own frame count, BUT — the one place this family differs from APC — the rows behind it
+ * are NOT zeros: the reference runs its convolutions over all T rows of the padded batch, bias and BatchNorm make the padded
+ * rows loud from the first block on, and they reach the utterance's last valid frames.  Every row of every state is the
+ * reference's value for this T; an utterance's rows depend on T and on nothing else of the batch. */
+int s3enc_create_npc(const s3enc_config* cfg, const s3enc_npc_config* npc, const s3enc_tensor* tensors, int32_t n_tensors,
+                     int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -554,6 +604,10 @@ int s3enc_debug_clock_sample(uint64_t* out3_device, void* stream);
  *                   (s, b) owning hidden / S units of utterance b (hidden / S a multiple of 64, S * B <= 256; refused otherwise) —
  *                   the same bits for every S; -1 (default) = S = 8 for a GRU at hidden = 512 with 8 B <= 256, where it was measured
  *                   to win (27.0 against 88.8 ms per 32 x 10 s apc_360hr forward, profiles/apc_360hr_fp32.md), one launch elsewhere;
+ *   "npc_skip_taps": S3ENC_NPC handles: 1 (default) = the masked convolutions walk their two runs of live taps only (convtaps.hip: the
+ *                   masked taps are neither fetched nor multiplied), 0 = the same kernel over all kernel_size taps on weights whose
+ *                   masked taps are stored as zeros — equal values; measured 6.13 against 10.55 ms per 32 x 10 s npc_360hr forward
+ *                   (profiles/npc_360hr_fp32.md);
  *   "conv_f22":     S3ENC_F32: 1 (default) = conv layers 1.. with kernel 3 and stride 2 (conv1-4 of every extractor) run in the
  *                   two-output form (convf22.hip: 5 block products per pair of outputs instead of 6, fp32 operands and accumulation,
  *                   a different association — results differ in the last bits), 0 = the implicit GEMM;
@@ -670,6 +724,21 @@ int s3enc_op_rnn(int32_t cell, const float* pre, const float* w_hh_host, const f
 int s3enc_op_rnn_len(int32_t cell, const float* pre, const float* w_hh_host, const float* b_hn, const int32_t* len_host,
                      const float* res, int64_t ld_res, int32_t B, int32_t T, int32_t H, int64_t ld_pre, float* out, int64_t ldo,
                      void* stream);
+
+/* Stride-1 nn.Conv1d(C, N, k, padding = (k - 1) / 2) on channel-last rows, exact fp32, with `mask` taps in the middle of the
+ * kernel zeroed — taps [(k - mask) / 2, (k + mask) / 2), NPC's MaskConvBlock — and never read (convtaps.hip):
+ *   v[b][t][:] = act(sum_{j live} W[:, :, j] x[b][t + j - P] + bias [+ res[b][t]]),  P = (k - 1) / 2,  act 0 none / 1 ReLU / 2 tanh.
+ * x: device fp32, the BORDERED operand (B, T + 2 P, C): per utterance P zero rows, the T data rows, P zero rows (the caller zeroes
+ * the borders).  w_host: HOST fp32 (N, C, k), nn.Conv1d's layout; packed (live taps only, tap-major) and uploaded inside.  bias:
+ * device fp32 [N] or null.  mask: 0 or an odd number below k (k odd).  res: optional device fp32, row (b, t) at res + (b * T + t) *
+ * ld_res, added BEFORE the activation.  Up to three destinations, at least one: dst, a bordered (B, T + 2 dst_pad, ldo) buffer of
+ * which only rows [dst_pad, dst_pad + T) and columns [0, N) of each utterance are written; state, (B, T, N) contiguous; sum, (B, T,
+ * N) contiguous: sum = sum_init ? v : sum + v.  dense != 0 runs the same kernel over all k taps on weights whose masked taps are
+ * stored as zeros: equal values.  C % 16 == 0, N % 4 == 0, ldo % 4 == 0, ldo >= N, ld_res % 4 == 0, 16-byte aligned pointers.  A
+ * row's bits depend neither on B, nor on its place in the batch, nor on T's tiling.  Synchronises. */
+int s3enc_op_conv_taps(const float* x, const float* w_host, const float* bias, int32_t B, int32_t T, int32_t C, int32_t N, int32_t k,
+                       int32_t mask, int32_t act, const float* res, int64_t ld_res, float* dst, int32_t dst_pad, int64_t ldo,
+                       float* state, float* sum, int32_t sum_init, int32_t dense, void* stream);
 
 /* A forward and a backward unidirectional nn.LSTM on packed sequences, side by side, on the batch-shared kernel: one launch per
  * time step for both directions, W_hh read once per step for the whole batch (fp32 MFMA).  pre_fwd / pre_bwd: device fp32, row

@@ -19,7 +19,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -96,6 +96,16 @@ class S3DecoarConfig(C.Structure):
     ]
 
 
+class S3NpcConfig(C.Structure):
+    """s3enc_npc_config: the front-end / convolution block of an NPC handle (s3enc_create_npc)."""
+    _fields_ = [
+        ("num_mel_bins", C.c_int32), ("frame_length_ms", C.c_float), ("frame_shift_ms", C.c_float), ("window", C.c_int32),
+        ("cmvn", C.c_int32), ("hidden", C.c_int32), ("n_blocks", C.c_int32), ("kernel_size", C.c_int32), ("mask_size", C.c_int32),
+        ("residual", C.c_int32), ("batch_norm", C.c_int32), ("activate", C.c_int32), ("disable_cross_layer", C.c_int32),
+        ("dim_bottleneck", C.c_int32),
+    ]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -128,6 +138,7 @@ _PROTOS = {
     "s3enc_create_mockingjay": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3MockingjayConfig), C.POINTER(S3Tensor), _I32, _I32,
                                           C.POINTER(_VP)]),
     "s3enc_create_decoar": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3DecoarConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    "s3enc_create_npc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3NpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -175,6 +186,8 @@ _PROTOS = {
     "s3enc_op_rnn_len": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I64, _VP, _I64, _VP]),
     "s3enc_op_lstm_bidir": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I64, _VP, _I64, _VP]),
     "s3enc_pack_lstm_bidir_whh": (C.c_int, [_VP, _I32, _VP]),
+    "s3enc_op_conv_taps": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _I64, _VP, _VP,
+                                     _I32, _I32, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
@@ -363,4 +376,25 @@ def make_decoar_config(cfg) -> S3DecoarConfig:
     c.num_mel_bins, c.hidden, c.num_layers = int(cfg.decoar_feat_dim), int(cfg.decoar_hidden), int(cfg.decoar_layers)
     c.frame_length_ms, c.frame_shift_ms = float(cfg.decoar_frame_length), float(cfg.decoar_frame_shift)
     c.subsample, c.per_layer_states = int(cfg.decoar_subsample), int(cfg.decoar_per_layer)
+    return c
+
+
+NPC_ACTIVATE = {"relu": 0, "tanh": 1}                                              # s3enc_npc_config.activate
+
+
+def make_npc_config(cfg) -> S3NpcConfig:
+    """The second configuration block of a ``family="npc"`` EncoderConfig (``s3enc_create_npc``)."""
+    if cfg.family != "npc":
+        raise S3EncError("make_npc_config needs an npc configuration")
+    c = S3NpcConfig()
+    c.num_mel_bins = int(cfg.apc_feat_dim)
+    c.frame_length_ms, c.frame_shift_ms = float(cfg.apc_frame_length), float(cfg.apc_frame_shift)
+    c.window = APC_WINDOW.get(cfg.apc_window, -1)
+    c.cmvn = int(cfg.apc_cmvn)
+    c.hidden, c.n_blocks = int(cfg.conv_dim), int(cfg.npc_blocks)
+    c.kernel_size, c.mask_size = int(cfg.npc_kernel_size), int(cfg.npc_mask_size)
+    c.residual, c.batch_norm = int(cfg.npc_residual), int(cfg.npc_batch_norm)
+    c.activate = NPC_ACTIVATE.get(cfg.npc_activate, -1)
+    c.disable_cross_layer = int(cfg.npc_disable_cross_layer)
+    c.dim_bottleneck = int(cfg.npc_dim_bottleneck or 0)
     return c

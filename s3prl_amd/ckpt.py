@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, decoar_config, config_from_apc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, decoar_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -70,6 +70,37 @@ def load_apc_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]
             raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: {key} is missing")
     cfg = config_from_apc(state["config"])
     return cfg, _hot_path_weights(ckpt, cfg, state["model"])
+
+
+def load_npc_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"config": {"data": {"audio": ...}, "model": {"paras": ...}}, "model": state_dict}`` (upstream/npc/expert.py:22-26).  Every
+    convolution and BatchNorm tensor is required; ``postnet.*`` and ``vq_layers.*`` feed only the prediction the upstream discards
+    and are left in the file.  ``masked_convs.N.conv_mask`` is a registered buffer, not a parameter: a file that carries it must
+    carry the mask this configuration computes (a wrong one is refused by name; the HIP path never reads masked taps, so a mask it
+    did not apply would be a silent difference); ``bnN.num_batches_tracked`` is training state."""
+    import torch
+
+    state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    for key in ("config", "model"):
+        if key not in state:
+            raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: {key} is missing")
+    cfg = config_from_npc(state["config"])
+    sd = state["model"]
+    weights = _hot_path_weights(ckpt, cfg, sd)
+    H, k = cfg.conv_dim, cfg.npc_kernel_size
+    for i in range(cfg.npc_blocks):
+        name = f"masked_convs.{i}.conv_mask"
+        if not cfg.npc_has_mask(i) or name not in sd:
+            continue
+        m = sd[name]
+        m = m.detach().cpu().float().numpy() if hasattr(m, "detach") else np.asarray(m, dtype=np.float32)
+        head = (k - cfg.npc_mask(i)) // 2
+        want = np.ones((H, H, k), dtype=np.float32)
+        want[:, :, head:head + cfg.npc_mask(i)] = 0
+        if m.shape != want.shape or not np.array_equal(m, want):
+            raise ValueError(f"{ckpt}: {name} is not the mask of kernel_size {k} / mask_size {cfg.npc_mask_size} (block {i}: taps "
+                             f"[{head}, {head + cfg.npc_mask(i)}) zeroed)")
+    return cfg, weights
 
 
 def load_decoar_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
@@ -182,6 +213,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_mockingjay_checkpoint(ckpt)
     if family == "decoar":
         return load_decoar_checkpoint(ckpt)
+    if family == "npc":
+        return load_npc_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -235,6 +268,18 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
         return
     if cfg.family == "decoar":  # upstream/decoar/expert.py:30-36
         torch.save({"model": sd}, path)
+        return
+    if cfg.family == "npc":  # upstream/npc/expert.py:22-26
+        audio = dict(feat_type=cfg.apc_feat_type, feat_dim=cfg.apc_feat_dim, frame_length=cfg.apc_frame_length,
+                     frame_shift=cfg.apc_frame_shift, decode_wav=False, cmvn=cfg.apc_cmvn)
+        paras = dict(kernel_size=cfg.npc_kernel_size, mask_size=cfg.npc_mask_size, n_blocks=cfg.npc_blocks, hidden_size=cfg.conv_dim,
+                     dropout=0.0, residual=cfg.npc_residual, batch_norm=cfg.npc_batch_norm, activate=cfg.npc_activate,
+                     disable_cross_layer=cfg.npc_disable_cross_layer)
+        if cfg.npc_vq is not None:
+            paras["vq"] = dict(cfg.npc_vq)
+        if cfg.npc_dim_bottleneck is not None:
+            paras["dim_bottleneck"] = cfg.npc_dim_bottleneck
+        torch.save({"config": {"data": {"audio": audio}, "model": {"paras": paras}}, "model": sd}, path)
         return
     if cfg.family == "apc":  # upstream/apc/expert.py:22-27
         audio = dict(feat_type=cfg.apc_feat_type, feat_dim=cfg.apc_feat_dim, frame_length=cfg.apc_frame_length,

@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -176,6 +176,19 @@ class EncoderConfig:
     decoar_subsample: int = 1           # every n-th frame: 1 (decoar/audio.py keeps them all) or 2 (decoar2/audio.py:84)
     decoar_per_layer: bool = False      # False: one state, the last layer (decoar); True: one per layer (decoar_layers)
 
+    # NPC (family "npc", upstream/npc/npc.py:21-248): APC's front end — the ``apc_*`` fields above are its ``data.audio`` — and
+    # ``npc_blocks`` ConvBlocks, each (or, with ``npc_disable_cross_layer``, only the last) followed by a masked convolution.
+    # ``conv_layers`` = [(hidden, window, shift)] in samples; ``encoder_layers`` = the number of states - 1
+    npc_blocks: int = 4               # paras.n_blocks
+    npc_kernel_size: int = 15         # paras.kernel_size of the masked convolutions
+    npc_mask_size: int = 5            # paras.mask_size: block i masks mask_size + 2 (i + 1) taps in the middle
+    npc_residual: bool = True         # paras.residual (blocks 1..)
+    npc_batch_norm: bool = True       # paras.batch_norm
+    npc_activate: str = "relu"        # paras.activate: relu | tanh
+    npc_disable_cross_layer: bool = False  # paras.disable_cross_layer
+    npc_vq: Dict | None = None        # paras.vq: feeds only the discarded prediction; kept for the checkpoint round trip
+    npc_dim_bottleneck: int | None = None  # paras.dim_bottleneck: the last state would have another width (refused)
+
     # ---- derived -------------------------------------------------------------------------
     @property
     def conv_dim(self) -> int:
@@ -236,7 +249,7 @@ class EncoderConfig:
             return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
         if self.family == "mockingjay":
             return min(T, max(self.num_frames(length), 0))
-        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length
+        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "npc"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -343,6 +356,8 @@ class EncoderConfig:
             return self._validate_mockingjay()
         if self.family == "decoar":
             return self._validate_decoar()
+        if self.family == "npc":
+            return self._validate_npc()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -444,6 +459,52 @@ class EncoderConfig:
             raise ValueError(f"apc feat_dim must be a multiple of 4, at most 256, got {self.apc_feat_dim}")
         if self.encoder_layers != 2 or self.encoder_embed_dim != H:
             raise ValueError("apc: encoder_layers / encoder_embed_dim must be 2 / hidden_size (apc_config sets them)")
+
+    def npc_mask(self, i: int) -> int:
+        """Masked taps of block ``i``'s masked convolution (npc.py:133-148)."""
+        return self.npc_mask_size + 2 * (i + 1)
+
+    def npc_has_mask(self, i: int) -> bool:
+        return not self.npc_disable_cross_layer or i == self.npc_blocks - 1
+
+    def _validate_npc(self) -> None:
+        """What the HIP path builds of the NPC configuration; everything else is refused by name (s3enc_create_npc repeats it)."""
+        if self.apc_feat_type != "fbank":
+            raise ValueError(f"npc feat_type={self.apc_feat_type!r} is not built: only 'fbank' (the reference implements nothing else)")
+        if self.apc_window not in ("hamming", "povey"):
+            raise ValueError(f"npc window_type={self.apc_window!r} is not built: only 'hamming' and 'povey'")
+        if self.npc_dim_bottleneck is not None:
+            raise ValueError(f"npc dim_bottleneck={self.npc_dim_bottleneck} is not built: the last state would have another width")
+        if not 1 <= self.npc_blocks <= 8:
+            raise ValueError(f"npc n_blocks must be 1..8, got {self.npc_blocks}")
+        k = self.npc_kernel_size
+        if k < 1 or k % 2 == 0:
+            raise ValueError(f"npc kernel_size must be odd, got {k}")
+        if self.npc_mask_size < 1 or self.npc_mask_size % 2 == 0:
+            raise ValueError(f"npc mask_size must be odd, got {self.npc_mask_size}")
+        if k > 63:
+            raise ValueError(f"npc kernel_size above 63 is not built, got {k}")
+        for i in range(self.npc_blocks):
+            if self.npc_has_mask(i) and k - self.npc_mask(i) <= 0:
+                raise ValueError(f"npc mask leaves no tap in block {i} (mask {self.npc_mask(i)} of kernel_size {k})")
+        if self.npc_activate not in ("relu", "tanh"):
+            raise ValueError(f"npc activate={self.npc_activate!r} is not built: only 'relu' and 'tanh' (the reference implements nothing else)")
+        if len(self.conv_layers) != 1:
+            raise ValueError("npc: conv_layers carries the frame geometry as one (hidden, window, shift) entry (npc_config sets it)")
+        H, size, shift = self.conv_layers[0]
+        if H % 64 or not 64 <= H <= 1024:
+            raise ValueError(f"npc hidden_size must be a multiple of 64, at most 1024, got {H}")
+        if (size, shift) != (int(16000 * self.apc_frame_length * 0.001), int(16000 * self.apc_frame_shift * 0.001)):
+            raise ValueError("npc: conv_layers does not match frame_length / frame_shift (npc_config sets it)")
+        if size < 4 or shift < 4 or size % 4 or shift % 4:
+            raise ValueError(f"npc frame_length / frame_shift of {size} / {shift} samples are not built: both must be a multiple of 4 "
+                             "samples (the front end's GEMM reads 16-byte vectors)")
+        if self.apc_feat_dim % 16 or not 16 <= self.apc_feat_dim <= 256:
+            raise ValueError(f"npc feat_dim must be a multiple of 16, at most 256 (a tap is a whole number of 64-byte K steps), got "
+                             f"{self.apc_feat_dim}")
+        states = self.npc_blocks + 2 if self.npc_disable_cross_layer else 2 * self.npc_blocks + 1
+        if self.encoder_layers != states - 1 or self.encoder_embed_dim != H:
+            raise ValueError("npc: encoder_layers / encoder_embed_dim must be the number of states - 1 / hidden_size (npc_config sets them)")
 
     def _validate_decoar(self) -> None:
         """What the HIP path builds of DeCoAR; everything else is refused by name (s3enc_create_decoar repeats it)."""
@@ -639,6 +700,45 @@ def config_from_apc(config: Dict) -> EncoderConfig:
             raise ValueError(f"apc checkpoint: model.paras.{key} is missing")
     return apc_config(paras["hidden_size"], paras["num_layers"], paras["residual"], feat_dim, frame_length, frame_shift, cmvn,
                       paras.get("vq"), apc_feat_type=str(feat_type))
+
+
+def npc_config(hidden: int = 512, n_blocks: int = 4, kernel_size: int = 15, mask_size: int = 5, residual: bool = True,
+               batch_norm: bool = True, activate: str = "relu", disable_cross_layer: bool = False, feat_dim: int = 80,
+               frame_length: float = 25.0, frame_shift: float = 10.0, cmvn: bool = True, vq: Dict | None = None,
+               dim_bottleneck: int | None = None, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "npc" (npc/npc.py:99-171, npc/audio.py:107-115)."""
+    H, nb = int(hidden), int(n_blocks)
+    size, shift = int(16000 * float(frame_length) * 0.001), int(16000 * float(frame_shift) * 0.001)
+    cfg = EncoderConfig(family="npc", conv_layers=[(H, size, shift)], encoder_layers=nb + 1 if disable_cross_layer else 2 * nb,
+                        encoder_embed_dim=H, apc_feat_dim=int(feat_dim), apc_frame_length=float(frame_length),
+                        apc_frame_shift=float(frame_shift), apc_cmvn=bool(cmvn), npc_blocks=nb, npc_kernel_size=int(kernel_size),
+                        npc_mask_size=int(mask_size), npc_residual=bool(residual), npc_batch_norm=bool(batch_norm),
+                        npc_activate=str(activate), npc_disable_cross_layer=bool(disable_cross_layer),
+                        npc_vq=None if vq is None else dict(vq),
+                        npc_dim_bottleneck=None if dim_bottleneck is None else int(dim_bottleneck), **flags)
+    cfg.validate()
+    return cfg
+
+
+def config_from_npc(config: Dict) -> EncoderConfig:
+    """The checkpoint's ``config``: ``data.audio`` as ``create_transform`` reads it (npc/audio.py:107-115) and ``model.paras`` as
+    ``NPC(feat_dim, **paras)`` does (npc/npc.py:99-113: batch_norm, activate, disable_cross_layer, vq and dim_bottleneck have
+    defaults)."""
+    audio = dict(config["data"]["audio"])
+    feat_type, feat_dim = audio.pop("feat_type"), audio.pop("feat_dim")
+    audio.pop("decode_wav", None)  # how a FILE is read; the upstream is handed waveforms
+    cmvn = audio.pop("cmvn", True)
+    frame_length, frame_shift = audio.pop("frame_length", 25.0), audio.pop("frame_shift", 10.0)
+    if audio:
+        raise ValueError(f"npc audio options {sorted(audio)} are not built: only frame_length / frame_shift reach kaldi.fbank here")
+    paras = dict(config["model"]["paras"])
+    for key in ("hidden_size", "n_blocks", "residual", "kernel_size", "mask_size"):
+        if key not in paras:
+            raise ValueError(f"npc checkpoint: model.paras.{key} is missing")
+    return npc_config(paras["hidden_size"], paras["n_blocks"], paras["kernel_size"], paras["mask_size"], paras["residual"],
+                      paras.get("batch_norm", True), paras.get("activate", "relu"), paras.get("disable_cross_layer", False),
+                      feat_dim, frame_length, frame_shift, cmvn, paras.get("vq"), paras.get("dim_bottleneck"),
+                      apc_feat_type=str(feat_type))
 
 
 def decoar_config(hidden: int = 1024, num_layers: int = 4, per_layer: bool = False, feat_dim: int = 80, subsample: int = 1,

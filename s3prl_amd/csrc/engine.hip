@@ -21,7 +21,7 @@ int valid_frames(const s3enc_config& c, long length, long n_max) {
     const long T = conv_len(c, n_max, c.n_conv);
     if (T <= 0) return 0;
     long v;
-    if (c.family == S3ENC_WAV2VEC2 || c.family == S3ENC_DISTILLER || c.family == S3ENC_WAV2VEC || c.family == S3ENC_APC) {
+    if (c.family == S3ENC_WAV2VEC2 || c.family == S3ENC_DISTILLER || c.family == S3ENC_WAV2VEC || c.family == S3ENC_APC || c.family == S3ENC_NPC) {
         // wav2vec2_model.py:2652-2669; distiller/model.py:271-285; wav2vec has no mask: the frames an utterance's own samples reach;
         // APC: the utterance's own whole analysis windows (its packed length)
         v = conv_len(c, length, c.n_conv);
@@ -155,12 +155,13 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 9) return fail("config: unknown family");
+    if (c.family < 0 || c.family > 10) return fail("config: unknown family");
     if (c.family == S3ENC_WAV2VEC) return 0;  // s3enc_create_ex: wav2vec_check_config on both configuration blocks
     if (c.family == S3ENC_CPC) return 0;      // s3enc_create_cpc: cpc_check_config on both configuration blocks
     if (c.family == S3ENC_APC) return 0;      // s3enc_create_apc: apc_check_config on both configuration blocks
     if (c.family == S3ENC_MOCKINGJAY) return 0;  // s3enc_create_mockingjay: mj_check_config on both configuration blocks
     if (c.family == S3ENC_DECOAR) return 0;      // s3enc_create_decoar: decoar_check_config on both configuration blocks
+    if (c.family == S3ENC_NPC) return 0;         // s3enc_create_npc: npc_check_config on both configuration blocks
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
         const int k = c.mr_kernel;
@@ -242,6 +243,7 @@ static int wrong_entry(const char* entry, int own, int family) {
         {S3ENC_MOCKINGJAY, "mockingjay", "S3ENC_MOCKINGJAY", "s3enc_create_mockingjay",
          "the Mockingjay / TERA / AudioALBERT family needs its front-end block"},
         {S3ENC_DECOAR, "decoar", "S3ENC_DECOAR", "s3enc_create_decoar", "the DeCoAR family needs its front-end / LSTM block"},
+        {S3ENC_NPC, "npc", "S3ENC_NPC", "s3enc_create_npc", "the NPC family needs its front-end / convolution block"},
     };
     if (family == own) return 0;
     for (const auto& f : F)
@@ -262,7 +264,7 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
                        const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_decoar_config* dc,
-                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
+                       const s3enc_npc_config* npc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
 
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out) {
@@ -270,7 +272,7 @@ int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, co
         if (out) *out = nullptr;
         return 1;
     }
-    return create_impl(cfg, w2v, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, w2v, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -278,7 +280,7 @@ int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const
     if (!cfg || !cpc || !tensors || !out) return fail("s3enc_create_cpc: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_cpc", S3ENC_CPC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, cpc, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, cpc, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -286,7 +288,7 @@ int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const
     if (!cfg || !apc || !tensors || !out) return fail("s3enc_create_apc: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_apc", S3ENC_APC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, apc, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, apc, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -294,7 +296,7 @@ int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_conf
     if (!cfg || !mj || !tensors || !out) return fail("s3enc_create_mockingjay: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_mockingjay", S3ENC_MOCKINGJAY, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, mj, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, nullptr, mj, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* decoar, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -302,12 +304,20 @@ int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* deco
     if (!cfg || !decoar || !tensors || !out) return fail("s3enc_create_decoar: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_decoar", S3ENC_DECOAR, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, decoar, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, decoar, nullptr, tensors, n_tensors, device, out);
+}
+
+int s3enc_create_npc(const s3enc_config* cfg, const s3enc_npc_config* npc, const s3enc_tensor* tensors, int32_t n_tensors,
+                     int32_t device, s3enc_handle* out) {
+    if (!cfg || !npc || !tensors || !out) return fail("s3enc_create_npc: null argument");
+    *out = nullptr;
+    if (wrong_entry("s3enc_create_npc", S3ENC_NPC, cfg->family)) return 1;
+    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, npc, tensors, n_tensors, device, out);
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
                        const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_decoar_config* dc,
-                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
+                       const s3enc_npc_config* npc, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
@@ -319,6 +329,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         case S3ENC_APC: if (apc_check_config(*cfg, *apc)) return 1; break;
         case S3ENC_MOCKINGJAY: if (mj_check_config(*cfg, *mj)) return 1; break;
         case S3ENC_DECOAR: if (decoar_check_config(*cfg, *dc)) return 1; break;
+        case S3ENC_NPC: if (npc_check_config(*cfg, *npc)) return 1; break;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -346,6 +357,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         case S3ENC_APC: e->apc_cfg = *apc; family_rc = apc_create(e.get(), ck); break;
         case S3ENC_MOCKINGJAY: e->mj_cfg = *mj; family_rc = mj_create(e.get(), ck); break;
         case S3ENC_DECOAR: e->decoar_cfg = *dc; family_rc = decoar_create(e.get(), ck); break;
+        case S3ENC_NPC: e->npc_cfg = *npc; family_rc = npc_create(e.get(), ck); break;
     }
     if (family_rc >= 0) return family_rc ? 1 : finish_create(std::move(e), out);
     const s3enc_config& c = e->cfg;
@@ -1087,6 +1099,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         case S3ENC_APC: return apc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
         case S3ENC_MOCKINGJAY: return mj_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
         case S3ENC_DECOAR: return decoar_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+        case S3ENC_NPC: return npc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     }
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
@@ -1837,6 +1850,8 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
         return fail("s3enc_num_states: feature_selection is not defined for Mockingjay / TERA / AudioALBERT (one hidden_states list)");
     if (h->cfg.family == S3ENC_DECOAR && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: feature_selection is not defined for DeCoAR (one hidden_states list)");
+    if (h->cfg.family == S3ENC_NPC && selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_num_states: feature_selection is not defined for NPC (one hidden_states list)");
     *n = num_states(h->cfg, selection);
     return 0;
 }

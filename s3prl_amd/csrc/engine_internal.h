@@ -8,6 +8,7 @@
 //   wav2vec.hip / cpc.hip  the convolutional families (wav2vec, modified CPC); rnn.hip: the LSTM / GRU recurrence
 //   apc.hip / mockingjay.hip  the log-mel families (APC / VQ-APC on GRU layers; Mockingjay / TERA / AudioALBERT on BERT layers)
 //   decoar.hip  DeCoAR: the log-mel front end, a projection and two LSTM stacks on rnnb.hip's batch-shared step
+//   npc.hip     NPC: the log-mel front end, ConvBlocks and masked convolutions on convtaps.hip's two-run implicit GEMM
 //   (a family file holds its configuration check, its weights and its forward schedule: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
 #pragma once
@@ -420,6 +421,13 @@ struct DecoarW {
     DevBuf w_ih0, b_pre0;                            // layer 0: forward rows, then backward rows
 };
 
+// NPC (npc.hip): per block the k = 3 and 1 x 1 convolutions with their BatchNorms folded in, and (where the block has one) the masked
+// convolution packed twice: the live taps only, and all k taps with the masked ones stored as zeros (tuning key npc_skip_taps)
+struct NpcW {
+    std::vector<DevBuf> w3, b3, w1, b1, wm, wm_dense, bm;
+    std::vector<int> has_mask;
+};
+
 // Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table, and per layer (ONE layer with
 // share_layer) q|k|v stacked as one (3 D, D) operand with q pre-scaled by head_dim^-0.5, the other projections and LayerNorm affines
 struct MjLayerW {
@@ -495,6 +503,8 @@ struct s3enc_encoder {
     s3enc_mockingjay_config mj_cfg = {};  // ... and its second configuration block (s3enc_create_mockingjay)
     std::unique_ptr<DecoarW> decoar;    // S3ENC_DECOAR
     s3enc_decoar_config decoar_cfg = {};  // ... and its second configuration block (s3enc_create_decoar)
+    std::unique_ptr<NpcW> npc;          // S3ENC_NPC
+    s3enc_npc_config npc_cfg = {};      // ... and its second configuration block (s3enc_create_npc)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -790,6 +800,11 @@ int decoar_create(s3enc_encoder* e, const Ckpt& ck);
 long decoar_num_frames(const s3enc_config& c, const s3enc_decoar_config& x, long n_samples);  // ceil(fbank frames / subsample)
 int decoar_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+// npc.hip: the S3ENC_NPC family (kaldi log-mel front end + ConvBlocks + masked convolutions; no length masking)
+int npc_check_config(const s3enc_config& c, const s3enc_npc_config& x);
+int npc_create(s3enc_encoder* e, const Ckpt& ck);
+int npc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 // mockingjay.hip: the S3ENC_MOCKINGJAY family (spectrogram front end + input representation + post-LN BERT layers, chunked)
 int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x);
 int mj_create(s3enc_encoder* e, const Ckpt& ck);

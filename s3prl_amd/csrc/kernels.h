@@ -88,6 +88,8 @@ struct Tuning {
                            // the step-split form with that many workgroups per utterance, one launch per step (bit-identical);
                            // -1 (default) = the step form with S = 8 where it was measured to win (a GRU at H = 512 with
                            // 8 B <= 256: 27.0 against 88.8 ms per apc_360hr forward, profiles/apc_360hr_fp32.md), else one launch
+    int npc_skip_taps = 1; // npc.hip: 1 = the masked convolutions walk their two runs of live taps only (convtaps.hip), 0 = the same kernel over
+                           // all k taps on weights whose masked taps are stored as zeros (equal values; the A/B of profiles/npc_360hr_fp32.md)
     int comm_self_p2p = 0; // comm.hip, S3ENC_EXCHANGE_DIRECT: 1 = a rank's OWN block also travels as an ncclSend-to-self / ncclRecv-from-self
                            // pair inside the state's group instead of a device copy — on a one-GPU box this is the only way the
                            // all-pairs code (symbols, counts, datatype, group bracketing, stream order behind the layer events)
@@ -183,6 +185,33 @@ struct ConvF22Params {
 };
 bool conv_f22_eligible(const ConvF22Params& p);  // tuning().conv_f22, C a multiple of 32, alignment, 32-bit offsets
 hipError_t launch_conv_f22(const ConvF22Params& p, hipStream_t stream);
+// convtaps.hip: exact-fp32 stride-1 Conv1d on channel-last rows whose K walk is up to two tap runs (NPC's masked convolutions:
+// the masked taps in the middle are neither fetched nor multiplied), with a pre-activation residual and up to three destinations.
+// Utterance b's operand is P zero rows, T data rows, P zero rows; `src` points at the row that tap 0 of output row 0 reads.
+struct ConvTapsParams {
+    const float* src;    // utterance b at src + b * src_bs; output row t, tap j reads the C floats at src + b * src_bs + (t + j) * C
+    long src_bs;
+    int C;               // input channels, a multiple of 16
+    const float* W;      // (N, (taps0 + taps1) * C): the live taps only, tap-major (pack_conv_taps)
+    const float* bias;   // [N] or null
+    int T, N, B;
+    int taps0, gap, taps1;  // run 0 = taps [0, taps0); `gap` masked taps; run 1 = the taps1 taps behind them (0: one run)
+    int act;             // 0 none, 1 ReLU, 2 tanh — applied to acc + bias + res
+    const float* res;    // optional: row (b, t) at res + b * res_bs + t * ld_res, added BEFORE the activation
+    long res_bs, ld_res;
+    float* dst;          // optional: row (b, t) at dst + b * dst_bs + t * ld_dst (a bordered operand: point it at the first data row)
+    long dst_bs, ld_dst;
+    float* state;        // optional: a second copy, same addressing (a contiguous (B, T, N) state slot)
+    long state_bs, ld_state;
+    float* sum;          // optional: sum = sum_init ? v : sum + v
+    long sum_bs, ld_sum;
+    int sum_init;
+};
+// host: nn.Conv1d's (N, C, k) weight -> the kernel's (N, live * C) image; taps [(k - mask) / 2, (k + mask) / 2) are masked.
+// dense: all k taps, the masked ones stored as zeros (the form the skip form must equal)
+void pack_conv_taps(const float* w, int N, int C, int k, int mask, bool dense, std::vector<float>& out);
+const char* conv_taps_refusal(const ConvTapsParams& p);  // null, or why launch_conv_taps would refuse
+hipError_t launch_conv_taps(const ConvTapsParams& p, hipStream_t stream);
 
 // ---- frontend.hip ---------------------------------------------------------------------------------------
 // Waveform table: wav b is `ptrs[b]` with `lens[b]` valid samples; reads beyond are zeros (the padding).

@@ -26,7 +26,7 @@ int tuning_set(Tuning& t, const char* key, int value, const char** err) {
         {"ln_rows", &Tuning::ln_rows, 1, 2},                 {"ln1_fold", &Tuning::ln1_fold, 0, 1},
         {"ln_preload", &Tuning::ln_preload, 0, 1},           {"forward_chain", &Tuning::forward_chain, 0, 1},
         {"conv0_fast", &Tuning::conv0_fast, 0, 1},           {"conv_f22", &Tuning::conv_f22, 0, 1},
-        {"rnn_split", &Tuning::rnn_split, -1, 8},
+        {"rnn_split", &Tuning::rnn_split, -1, 8},           {"npc_skip_taps", &Tuning::npc_skip_taps, 0, 1},
     };
     static thread_local char msg[160];
     if (!key) {
@@ -434,6 +434,56 @@ int s3enc_op_lstm_bidir(const float* pre_fwd, const float* pre_bwd, const float*
     if (const char* why = rnnb_refusal(p)) return fail(std::string("s3enc_op_lstm_bidir: ") + why);
     HIP_TRY(launch_rnnb(p, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights, the lengths and the state are freed on return
+    return 0;
+}
+
+int s3enc_op_conv_taps(const float* x, const float* w_host, const float* bias, int32_t B, int32_t T, int32_t C, int32_t N, int32_t k,
+                       int32_t mask, int32_t act, const float* res, int64_t ld_res, float* dst, int32_t dst_pad, int64_t ldo,
+                       float* state, float* sum, int32_t sum_init, int32_t dense, void* stream) {
+    if (!x || !w_host) return fail("s3enc_op_conv_taps: null argument");
+    if (!dst && !state && !sum) return fail("s3enc_op_conv_taps: no destination (dst, state and sum are all null)");
+    if (B <= 0 || T <= 0 || C <= 0 || N <= 0) return fail("s3enc_op_conv_taps: bad shape");
+    if (k < 1 || !(k & 1) || k > 63) return fail("s3enc_op_conv_taps: k must be odd, at most 63");
+    if (mask < 0 || (mask && !(mask & 1))) return fail("s3enc_op_conv_taps: mask must be 0 or odd");
+    if (mask >= k) return fail("s3enc_op_conv_taps: the mask leaves no tap");
+    if (dst && (dst_pad < 0 || ldo < N)) return fail("s3enc_op_conv_taps: dst needs dst_pad >= 0 and ldo >= N");
+    if (res && ld_res < N) return fail("s3enc_op_conv_taps: ld_res < N");
+    const int P = (k - 1) / 2, head = (k - mask) / 2;
+    ConvTapsParams p{};
+    p.src = x;
+    p.src_bs = (long)(T + 2 * P) * C;
+    p.C = C;
+    p.bias = bias;
+    p.T = T;
+    p.N = N;
+    p.B = B;
+    p.taps0 = (dense || !mask) ? k : head;
+    p.gap = (dense || !mask) ? 0 : mask;
+    p.taps1 = (dense || !mask) ? 0 : k - head - mask;
+    p.act = act;
+    p.res = res;
+    p.res_bs = res ? (long)T * ld_res : 0;
+    p.ld_res = res ? ld_res : 0;
+    p.dst = dst ? dst + (long)dst_pad * ldo : nullptr;
+    p.dst_bs = dst ? (long)(T + 2 * dst_pad) * ldo : 0;
+    p.ld_dst = dst ? ldo : 0;
+    p.state = state;
+    p.state_bs = state ? (long)T * N : 0;
+    p.ld_state = state ? N : 0;
+    p.sum = sum;
+    p.sum_bs = sum ? (long)T * N : 0;
+    p.ld_sum = sum ? N : 0;
+    p.sum_init = sum_init;
+    alignas(16) static float stand_in[4];  // the checks that need no device memory first
+    p.W = stand_in;
+    if (const char* why = conv_taps_refusal(p)) return fail(std::string("s3enc_op_conv_taps: ") + why);
+    std::vector<float> packed;
+    pack_conv_taps(w_host, N, C, k, mask, dense != 0, packed);
+    DevBuf dw;
+    HIP_TRY(upload_f32(dw, packed));
+    p.W = (const float*)dw.p;
+    HIP_TRY(launch_conv_taps(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
     return 0;
 }
 

@@ -38,6 +38,8 @@ class HipEncoder:
             raise ValueError(f"Mockingjay / TERA / AudioALBERT are built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "decoar" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             raise ValueError(f"DeCoAR is built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "npc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"NPC is built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -78,6 +80,9 @@ class HipEncoder:
             elif cfg.family == "decoar":  # its front end and LSTM stacks travel beside the (unchanged) s3enc_config
                 dc = _lib.make_decoar_config(cfg)
                 rc = self._lib.s3enc_create_decoar(C.byref(ccfg), C.byref(dc), tensors, len(weights), self.device, C.byref(h))
+            elif cfg.family == "npc":  # its front end and convolution stack travel beside the (unchanged) s3enc_config
+                npc = _lib.make_npc_config(cfg)
+                rc = self._lib.s3enc_create_npc(C.byref(ccfg), C.byref(npc), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")
@@ -185,6 +190,9 @@ class HipEncoder:
         nm = max(lengths) if n_max is None else int(n_max)
         if self.cfg.family == "apc" and min(self.num_frames(n) for n in lengths) < 1:
             raise ValueError(f"an utterance of {min(lengths)} samples is shorter than one analysis window of the APC front end "
+                             f"({self.cfg.conv_layers[0][1]} samples)")
+        if self.cfg.family == "npc" and min(self.num_frames(n) for n in lengths) < 1:
+            raise ValueError(f"an utterance of {min(lengths)} samples is shorter than one analysis window of the NPC front end "
                              f"({self.cfg.conv_layers[0][1]} samples)")
         if self.cfg.family == "decoar":
             if B > 128:

@@ -30,6 +30,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _mockingjay_shapes(cfg)
     if cfg.family == "decoar":
         return _decoar_shapes(cfg)
+    if cfg.family == "npc":
+        return _npc_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -202,6 +204,27 @@ def _apc_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         s[f"rnn_layers.{l}.weight_hh_l0"] = (3 * H, H)
         s[f"rnn_layers.{l}.bias_ih_l0"] = (3 * H,)
         s[f"rnn_layers.{l}.bias_hh_l0"] = (3 * H,)
+    return s
+
+
+def _npc_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """NPC (upstream/npc/npc.py:131-171), reference state_dict names: the ConvBlocks (with their BatchNorm statistics) and the
+    masked convolutions.  ``postnet.*``, ``vq_layers.*``, the ``conv_mask`` buffers and ``num_batches_tracked`` are not hot-path
+    parameters."""
+    H, k = cfg.conv_dim, cfg.npc_kernel_size
+    s: Dict[str, tuple] = {}
+    for i in range(cfg.npc_blocks):
+        s[f"blocks.{i}.conv.weight"] = (H, cfg.apc_feat_dim if i == 0 else H, 3)
+        s[f"blocks.{i}.conv.bias"] = (H,)
+        s[f"blocks.{i}.linear.weight"] = (H, H, 1)
+        s[f"blocks.{i}.linear.bias"] = (H,)
+        if cfg.npc_batch_norm:
+            for bn in ("bn1", "bn2"):
+                for leaf in ("weight", "bias", "running_mean", "running_var"):
+                    s[f"blocks.{i}.{bn}.{leaf}"] = (H,)
+        if cfg.npc_has_mask(i):
+            s[f"masked_convs.{i}.conv.weight"] = (H, H, k)
+            s[f"masked_convs.{i}.conv.bias"] = (H,)
     return s
 
 
@@ -391,6 +414,23 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
             w = rng.standard_normal(shape) * (gain / np.sqrt(shape[1]))
         elif name.startswith(("forward_lstm.bias", "backward_lstm.bias")):
             w = 0.1 * rng.standard_normal(shape)
+        elif name.startswith("blocks.") and name.endswith((".conv.weight", ".linear.weight")):
+            # NPC's ConvBlocks at unit gain, 1 / sqrt(fan_in): the CMVN'd log-mel input has unit variance and BatchNorm's statistics
+            # below keep it there, so ReLU zeroes 30-55 % of a block's state and tanh is used on both sides of its bend, while the
+            # reference's own fp32 stays within 5e-7 of its float64 (at twice this gain the activations reach std 180, the masked
+            # states saturate at 98 % and the reference is 4e-6 from its double)
+            # (tanh blocks: gain 1.5, or the states shrink from block to block)
+            w = rng.standard_normal(shape) * ((1.5 if cfg.npc_activate == "tanh" else 1.0) / np.sqrt(shape[1] * shape[2]))
+        elif name.startswith("masked_convs.") and leaf == "weight":
+            # gain 1.6 over the LIVE taps (the masked ones never reach the output; a block's state has RMS 0.4-0.8): pre-activations
+            # of std 0.6-1.1 in front of tanh
+            live = shape[2] - cfg.npc_mask(int(name.split(".")[1]))
+            w = rng.standard_normal(shape) * (1.6 / np.sqrt(shape[1] * live))
+        elif name.startswith(("blocks.", "masked_convs.")) and name.endswith(("conv.bias", "linear.bias")):
+            w = 0.1 * rng.standard_normal(shape)
+        elif name.startswith("blocks.") and ".bn" in name:  # non-trivial eval statistics: the BatchNorm fold is exercised
+            w = {"weight": lambda: 1.0 + 0.1 * rng.standard_normal(shape), "bias": lambda: -0.1 + 0.05 * rng.standard_normal(shape),
+                 "running_mean": lambda: 0.2 * rng.standard_normal(shape), "running_var": lambda: rng.uniform(0.5, 2.0, size=shape)}[leaf]()
         elif name in ("vector_quantizer.embedding", "vector_quantizer.vars"):
             # codebooks at the scale of what they are compared with / replace (a trained k-means embedding lives where the
             # normalised projection does: unit variance; the reference's 0.01 * randn init leaves argmin decisions at rounding level)
@@ -582,6 +622,23 @@ def named_config(name: str) -> EncoderConfig:
         from .config import decoar_config
 
         return decoar_config(**decoar[name])
+    # NPC: APC's front end, ConvBlocks and masked convolutions; no length masking
+    tiny_npc = dict(hidden=64, n_blocks=4, kernel_size=15, mask_size=5, feat_dim=16)
+    npc = {
+        "tiny_npc": dict(tiny_npc, vq=dict(codebook_size=[8, 8], code_dim=[32, 32], gumbel_temperature=1.0)),
+        "tiny_npc_plain": dict(tiny_npc, batch_norm=False, activate="tanh", residual=False),
+        "tiny_npc_nocmvn": dict(tiny_npc, cmvn=False),  # a one-frame utterance has no std
+        "tiny_npc_last": dict(tiny_npc, disable_cross_layer=True),
+        "tiny_npc_k9": dict(hidden=64, n_blocks=3, kernel_size=9, mask_size=1, feat_dim=16),
+        "tiny_npc_h192": dict(tiny_npc, hidden=192, feat_dim=80),
+        # the released npc_360hr / npc_960hr shape (a checkpoint's own config decides at load time)
+        "npc_360hr": dict(hidden=512, n_blocks=4, kernel_size=15, mask_size=5, residual=True, batch_norm=True, activate="relu",
+                          vq=dict(codebook_size=[64, 64, 64, 64], code_dim=[128, 128, 128, 128], gumbel_temperature=1.0)),
+    }
+    if name in npc:
+        from .config import npc_config
+
+        return npc_config(**npc[name])
     # Mockingjay / TERA / AudioALBERT: a log-mel (or kaldi fbank) front end into post-LN BERT layers, long inputs in chunks
     tiny_mj = dict(hidden=128, layers=2, heads=2, intermediate=256, input_dim=16, sequence_length=0)
     mj = {
@@ -604,7 +661,7 @@ def named_config(name: str) -> EncoderConfig:
 
         return mockingjay_config(**mj[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(mj))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(mj))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
