@@ -550,12 +550,24 @@ int s3enc_debug_occupy_cus(int32_t workgroups, int32_t threads, double milliseco
  * to three device uint64 on `stream`.  Two samples around a region give its average shader clock: d(out[0]) / d(out[1]) x out[2]
  * (hipDeviceAttributeWallClockRate, 100 MHz) — bench.py's `clock_ghz`, so that a slow box reads as a slow box. */
 int s3enc_debug_clock_sample(uint64_t* out3_device, void* stream);
+/* Test hook (no reference counterpart, touches no device): the workgroups of one exact-fp32 tile-GEMM launch (gemmt.hip) in blockIdx
+ * order, through the kernel's own block -> tile map: M x N per batch, bulk tiles of 64 tm rows (tm 1..4), `tail` as the "gemm32_tail"
+ * key below, on a part of `cus` CUs.  Writes *n_items = the launch's grid, and — when items4_host holds max_items >= *n_items entries —
+ * four host int32 per workgroup: batch, first row, rows, first column. */
+int s3enc_debug_gemm_schedule(int32_t M, int32_t N, int32_t batches, int32_t tm, int32_t tail, int32_t cus, int32_t* items4_host,
+                              int64_t max_items, int64_t* n_items);
 
 /* Process-wide tuning knobs (kernel-variant selection for A/B measurements; results are unchanged, except "gelu32"):
  *   "gemm_variant": gemm.hip's 128x128 kernel: bit 0 = 64-byte K stages (else 128), bit 1 = LDS-DMA staging, bit 2 = no
  *                   XCD-aware tile order;
  *   "gemm32_big":   exact-fp32 tile kernel (gemmt.hip): 0 off (gemm.hip), 1 = tile height by shape (default), 2 / 3 / 4 / 5 =
  *                   force 256 / 192 / 128 / 64 rows;  "gemm_x3_tile": the same for S3ENC_F32X3 (1 = only small shapes);
+ *   "gemm32_tail":  exact-fp32 tile kernel: a launch of 256 / 192 / 128-row tiles may end with a tail region of 64-row tiles, the last
+ *                   workgroups dispatched, so that the last round of co-resident workgroups is not nearly empty (every height
+ *                   gives the same bits): 0 = never, 1 (default) = where the round model of gemmt.hip says it pays, 2 = every
+ *                   such launch, with the largest tail its M allows (one bulk tile when M exceeds the height, else none);
+ *   "gemm32_tail_units": lab probe under "gemm32_tail" = 1: 0 (default) = the model's tail, n = a tail of n 64-row units of every
+ *                   batch's M (clamped to M) on every such launch;
  *   "gemm16_big":   large-tile kernel of the 16-bit modes: 0 off, 1 = one workgroup per CU (256x256 or 192x256 tiles by CU
  *                   utilisation; 5 / 6 force either), 2 = 128x256, 4 = 128x256 with a 3-stage ring (two workgroups per
  *                   CU), 7 = mode 1's tiles walked by one persistent workgroup per CU, 8 = 7 with the epilogue's stores left

@@ -11,8 +11,8 @@
 // loss scales with the L2 -> LDS staging bytes per MFMA; round 2's 256x256 tile halved the bytes but ran ONE lock-step workgroup
 // per CU, so every stage boundary (wait, barrier, four M0-juggling DMA issues, fragment read latency) and every prologue /
 // 256 KiB epilogue drained the pipe.  Here:
-//   * 4 waves per workgroup, one per SIMD, each owning a (32 TM) x 64 accumulator block (TM = 4: 128 VGPRs, 193 in all;
-//     TM = 3: 152; TM = 2: 108): two / three / four independent workgroups share a CU, so a SIMD always has other waves whose
+//   * 4 waves per workgroup, one per SIMD, each owning a (32 TM) x 64 accumulator block (TM = 4: 128 VGPRs, 201 in all;
+//     TM = 3: 154; TM = 2: 122 — 193 / 152 / 108 before the epilogue requested its residual vectors ahead; the same waves per SIMD): two / three / four independent workgroups share a CU, so a SIMD always has other waves whose
 //     MFMAs fill one's barrier, prologue, GELU / store epilogue and DMA waits (vmcnt is per wave and in order: a wave's own
 //     epilogue stores never sit in front of its next DMA — it exits).
 //   * one 64-byte K step = 8 TM MFMAs per wave in two halves; the fragments of the second half / of the next step's first half
@@ -24,10 +24,19 @@
 //     as gemm_kernel<float>: results are BIT-IDENTICAL to the 128x128 kernel whatever tile is chosen (tests/test_ops_gpu.py),
 //     so a row's rounding does not depend on the batch it sits in (the shard == full-batch property of DESIGN §7).
 //   * the tile height is chosen per GEMM (tile_efficiency below; measured in profiles/r03_gemm32_lab.md): 128 rows unless
-//     another height divides the shape over the 256 CUs better (q|k|v of HuBERT-base 32 x 10 s: 192 rows = 5.9 tiles per CU)
-//     or K is long enough for the 256-row tile's lower staging traffic to pay (K >= 6144); 64 rows when there are fewer
-//     tiles than CUs.  Measured (same box, random operands): 128x128 kernel of round 2 -> this kernel, TFLOP/s: conv1 134.5
+//     another height divides the shape over the 256 CUs better (q|k|v of HuBERT-base 32 x 10 s runs 128-row tiles too: 2250
+//     of them, 2.2 rounds of the 1024 a chip holds) or K is long enough for the 256-row tile's lower staging traffic to pay
+//     (K >= 6144); 64 rows when there are fewer tiles than CUs.
+//   * since every height gives the same bits, an fp32 launch may MIX heights: a bulk region of 64 TM-row tiles and, dispatched
+//     last, a tail region of 64-row tiles run by the same kernel (tile_body<T, TM, 1>), so that the last round of co-resident
+//     workgroups is not one tall workgroup per CU with nothing to cover its barriers and epilogue.  The host decides per shape
+//     (gemm_tile_schedule: a round model, never the data); tuning key gemm32_tail.  Measured (profiles/gemm32_tail_lab_fp32.md):
+//     a tall workgroup alone on a CU still delivers 0.91 of the steady rate, so on the path's transformer shapes a tail is
+//     within the noise (q|k|v 134.0-135.8 against 135.2 TFLOP/s) and the model leaves it out; it takes conv1-like shapes
+//     (32 batches, 15.6 rounds: 140.4 -> 142.6).
+//     Measured (same box, random operands): 128x128 kernel of round 2 -> this kernel, TFLOP/s: conv1 134.5
 //     -> 145.6, q|k|v 128.7 -> 137.8, out_proj 121.7 -> 130.5, fc1 126.8 -> 135.5, fc2 130.5 -> 140.9, 8192^3 136.9 -> 151.1.
+#include <algorithm>
 #include <type_traits>
 
 #include "kernels.h"
@@ -57,15 +66,49 @@ template <> struct TileMma<bf16_tag> {
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
     }
 };
-template <typename T, int TM>
-__global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
+// Block -> work item.  XCD-aware tile order (as gemm.hip): workgroup wg runs on XCD wg & 7, and every XCD gets a contiguous
+// range of the (batch, m-tile, n-tile) sequence, n fastest.  A launch with a tail region has TWO such sequences, the bulk
+// tiles (m_bulk per batch, bm rows) and the tail tiles (m_tail per batch, 64 rows from row m_bulk * bm): every XCD walks its
+// range of the bulk sequence first and its range of the tail sequence after it, so the tail tiles are the highest loc = wg >> 3
+// of every XCD — the last workgroups dispatched — and not merely the highest tile numbers.  XCD x owns q8 + (x < r8) workgroups of
+// the grid and qb + (x < rb) of the bulk tiles (never more: nb <= nwg); the rest of its workgroups are tail tiles, numbered
+// from the count the XCDs before it took.  With m_tail = 0 this is the one-sequence map unchanged.
+struct TileItem {
+    int b, m0, n0;
+    bool tail;
+};
+__host__ __device__ inline TileItem tile_item(int wg, int nwg, int n_tiles, int batches, int bm, int m_bulk, int m_tail) {
+    const int nb = m_bulk * n_tiles * batches;
+    const int xcd = wg & 7, loc = wg >> 3;
+    const int q8 = nwg >> 3, r8 = nwg & 7, qb = nb >> 3, rb = nb & 7;
+    const int start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+    const int bstart = xcd < rb ? xcd * (qb + 1) : rb * (qb + 1) + (xcd - rb) * qb;
+    const int bcnt = qb + (xcd < rb ? 1 : 0);
+    TileItem it;
+    it.tail = loc >= bcnt;
+    const int tile = it.tail ? (start - bstart) + (loc - bcnt) : bstart + loc;
+    const int mt = it.tail ? m_tail : m_bulk;
+    const int tn = tile % n_tiles, tmb = tile / n_tiles;
+    it.b = tmb / mt;
+    it.m0 = it.tail ? m_bulk * bm + (tmb % mt) * 64 : (tmb % mt) * bm;
+    it.n0 = tn * BN;
+    return it;
+}
+
+// One output tile of 64 TE rows x 128 columns at (b, m0, n0), in the LDS image of the 64 TM-row tile: TE = TM is the kernel's
+// own tile, TE = 1 < TM the 64-row tile of a launch's tail region — the wave-to-row map of the TM = 1 instantiation (wave row wr
+// owns rows 32 wr), the A passes, fragment reads, MFMA groups and epilogue blocks of i < TE only; the W rows stay where the
+// TM-row plane has them.  TE is a template argument and not a run-time bound inside the loops: the height is uniform over the
+// workgroup, so the kernel branches ONCE, and the bulk tiles run the very instruction stream a launch without a tail runs.
+template <typename T, int TM, int TE>
+__device__ __forceinline__ void tile_body(const GemmParams& p, const int b, const int m0, const int n0) {
     typedef typename TileElem<T>::type store_t;
     constexpr int EB = sizeof(store_t);
     constexpr bool X3 = std::is_same<T, x3_tag>::value;
     constexpr int BM = 64 * TM;
     constexpr int PLANE = (BM + BN) * ROWB;  // one 64-byte K step of both operand tiles (24 / 20 / 16 KiB)
-    constexpr int NPASS = (BM + BN) / 64;    // 1 KiB DMA pieces per wave per step (6 / 5 / 4); passes < APASS fetch A rows
-    constexpr int APASS = BM / 64;
+    constexpr int NPASS = TE + BN / 64;      // 1 KiB DMA pieces per wave per step (6 / 5 / 4); passes < APASS fetch A rows
+    constexpr int APASS = TE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -73,20 +116,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
     const int wr = wave >> 1, wc = wave & 1;
     const int half = lane >> 5;
     const int l31 = lane & 31;
-
-    // XCD-aware tile order (as gemm.hip): every XCD gets a contiguous range of the (batch, m-tile, n-tile) sequence, n fastest
-    const int n_tiles = (p.N + BN - 1) / BN;
-    const int m_tiles = (p.M + BM - 1) / BM;
-    int tile;
-    {
-        const int nwg = gridDim.x, wg = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wg & 7, loc = wg >> 3;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-    }
-    const int tn = tile % n_tiles;
-    const int tmb = tile / n_tiles;
-    const int tm = tmb % m_tiles, b = tmb / m_tiles;
-    const int m0 = tm * BM, n0 = tn * BN;
     const int nk = (p.K * EB) >> 6;  // launcher: K is a multiple of the 64-byte step
 
     // ---- LDS-DMA sources.  A wave instruction lands 64 x 16 B = 16 rows of one operand at a wave-uniform LDS base; wave w
@@ -129,29 +158,29 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
         const unsigned kb = (unsigned)kt * ROWB;
         const unsigned d0 = lds0 + slot * PLANE;
 #pragma unroll
-        for (int i = 0; i < NPASS; ++i) dma(voff[i], i < APASS ? rsrc_a : rsrc_w, d0 + i * 4096, kb);
+        for (int i = 0; i < NPASS; ++i) dma(voff[i], i < APASS ? rsrc_a : rsrc_w, d0 + (i < APASS ? i : i - APASS + TM) * 4096, kb);
     };
 
     // ---- fragment addresses: row l31 of each 32-row block, 16-byte slot (half * 2 + q) ^ swizzle(row) ----
     const int swz = (l31 >> 2) & 3;
-    const char* fa_base = smem + (wr * (TM * 32) + l31) * ROWB;
+    const char* fa_base = smem + (wr * (TE * 32) + l31) * ROWB;
     const char* fb_base = smem + (BM + wc * 64 + l31) * ROWB;
     const int so0 = ((half * 2) ^ swz) << 4, so1 = ((half * 2 + 1) ^ swz) << 4;
 
-    f32x16 acc[TM][2];
+    f32x16 acc[TE][2];
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < TE; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     struct Frag {
-        uint4 a[TM], b[2];
+        uint4 a[TE], b[2];
     };
     auto read = [&](Frag& f, int slot, int so) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) f.a[i] = *(const uint4*)(fa_base + slot * PLANE + i * 32 * ROWB + so);
+        for (int i = 0; i < TE; ++i) f.a[i] = *(const uint4*)(fa_base + slot * PLANE + i * 32 * ROWB + so);
 #pragma unroll
         for (int j = 0; j < 2; ++j) f.b[j] = *(const uint4*)(fb_base + slot * PLANE + j * 32 * ROWB + so);
     };
@@ -164,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
         auto mma = [&](const Frag& f, int i, int j) { TileMma<T>::run(f.a[i], f.b[j], acc[i][j]); };
         auto mma_all = [&](const Frag& f) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+            for (int i = 0; i < TE; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) mma(f, i, j);
         };
@@ -188,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
             if (kt + 1 < nk) read(f0, slot ^ 1, so0);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+            for (int i = 0; i < TE; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     if (i | j) mma(f1, i, j);
@@ -232,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 1; i < TM; ++i) mma_row(c0, c1, i);
+            for (int i = 1; i < TE; ++i) mma_row(c0, c1, i);
         };
         int kt = 0;
         for (; kt + 1 < nk; kt += 2) {
@@ -243,9 +272,18 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
     }
     // the last step's barrier ordered every wave's fragment reads before this point: the planes are free for the epilogue
 
-    // ---- epilogue: acc[i][j][r] is (row = wr*32 TM + i*32 + (r&3) + 8*(r>>2) + 4*half, col = wc*64 + j*32 + l31); each
+    // ---- epilogue: acc[i][j][r] is (row = wr*32 TE + i*32 + (r&3) + 8*(r>>2) + 4*half, col = wc*64 + j*32 + l31); each
     //      32 x 64 block goes through a wave-private LDS transpose so that bias / GELU / residual run on row-contiguous
-    //      vectors and every global access is a 16-byte vector ----
+    //      vectors and every global access is a 16-byte vector.  fp32: the residual vectors of block i + 1 are requested
+    //      BEFORE block i's rows are read back and stored (block 0's before its transpose), as gemm_x3.hip does: loaded inside
+    //      the store loop, with out == residual (fc2 in place) no load can be moved above the previous stores and every row
+    //      group of a block pays its own memory round trip behind them (profiles/r04_gemm16_residual.md).  A lane reads
+    //      only the elements it later writes itself, and block i + 1's rows are not block i's: in place stays correct. ----
+    constexpr bool PRE = !X3;  // the split-precision instantiation keeps its schedule
+    // AHEAD: block 0's vectors before its transpose, block i + 1's before block i's rows are read back — two sets of eight
+    // vectors live beside the accumulators.  At 192 rows that takes the kernel to 169 VGPRs, one past three waves per SIMD:
+    // there block 0's are requested behind its transpose and block i + 1's behind block i's stores, one set live (154 VGPRs)
+    constexpr bool AHEAD = TE != 3;
     const int limit = p.row_limit ? p.row_limit[b] : p.M;
     const long ob = (long)b * p.o_bs;
     float* stg = (float*)(smem + wave * 8192);
@@ -256,18 +294,30 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
         const bool n_ok = n < p.N;
         float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (p.bias && n_ok) bias4 = *(const float4*)(p.bias + n);
+        float4 res[2][8];
+        auto load_res = [&](int i, float4 (&r)[8]) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
+            for (int t = 0; t < 8; ++t) {
+                const int m = m0 + wr * (TE * 32) + i * 32 + t * 4 + (lane >> 4);
+                r[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (m < p.M && n_ok) r[t] = *(const float4*)(p.residual + ob + (long)m * p.ldo + n);
+            }
+        };
+        if (PRE && AHEAD && p.residual) load_res(0, res[0]);
+#pragma unroll
+        for (int i = 0; i < TE; ++i) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * half) * 64 + j * 32 + l31] = acc[i][j][r];
+            if (PRE && !AHEAD && i == 0 && p.residual) load_res(0, res[0]);
+            if (PRE && AHEAD && i + 1 < TE && p.residual) load_res(i + 1, res[(i + 1) & 1]);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const int row = t * 4 + (lane >> 4);
                 float4 v = *(const float4*)(stg + row * 64 + c4);
-                const int m = m0 + wr * (TM * 32) + i * 32 + row;
+                const int m = m0 + wr * (TE * 32) + i * 32 + row;
                 if (m < p.M && n_ok) {
                     v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
                     if (p.act == 3) {
@@ -281,36 +331,53 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p) {
                     }
                     const long o = ob + (long)m * p.ldo + n;
                     if (p.residual) {
-                        const float4 rs = *(const float4*)(p.residual + o);
+                        const float4 rs = PRE ? res[i & 1][t] : *(const float4*)(p.residual + o);
                         v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w;
                     }
                     if (m >= limit) v = make_float4(0.f, 0.f, 0.f, 0.f);
                     *(float4*)(p.out32 + o) = v;
                 }
             }
+            if (PRE && !AHEAD && i + 1 < TE && p.residual) load_res(i + 1, res[(i + 1) & 1]);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
     }
 }
 
+// The kernel: block -> work item, then the tile at its height.  `m_bulk` tiles of 64 TM rows and `m_tail` tiles of 64 rows per
+// batch (GemmTileSched); only the fp32 instantiations of TM >= 2 are ever launched with a tail, the others keep one body.
 template <typename T, int TM>
-hipError_t go(const GemmParams& p, hipStream_t stream) {
+__global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmParams p, int m_bulk, int m_tail) {
+    constexpr bool MIX = TM > 1 && !std::is_same<T, x3_tag>::value;
+    const int n_tiles = (p.N + BN - 1) / BN;
+    const TileItem it = tile_item(blockIdx.x, gridDim.x, n_tiles, p.batches, 64 * TM, m_bulk, MIX ? m_tail : 0);
+    if constexpr (MIX) {
+        if (it.tail) {
+            tile_body<T, TM, 1>(p, it.b, it.m0, it.n0);
+            return;
+        }
+    }
+    tile_body<T, TM, TM>(p, it.b, it.m0, it.n0);
+}
+
+template <typename T, int TM>
+hipError_t go(const GemmParams& p, const GemmTileSched& s, hipStream_t stream) {
     constexpr int BM = 64 * TM;
     constexpr int plane2 = 2 * (BM + BN) * ROWB;
     constexpr int lds = plane2 > 4 * 8192 ? plane2 : 4 * 8192;  // 48 / 40 / 32 / 32 KiB: the workgroups per CU are VGPR-limited
     hipError_t e = ensure_dynamic_lds<gemm_tile_kernel<T, TM>>(lds);
     if (e != hipSuccess) return e;
-    dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.batches);
-    hipLaunchKernelGGL((gemm_tile_kernel<T, TM>), grid, dim3(256), lds, stream, p);
+    dim3 grid((s.m_bulk + s.m_tail) * ((p.N + BN - 1) / BN) * p.batches);
+    hipLaunchKernelGGL((gemm_tile_kernel<T, TM>), grid, dim3(256), lds, stream, p, s.m_bulk, s.m_tail);
     return hipGetLastError();
 }
 template <typename T>
-hipError_t go_tm(int tm, const GemmParams& p, hipStream_t stream) {
-    switch (tm) {
-        case 4: return go<T, 4>(p, stream);
-        case 3: return go<T, 3>(p, stream);
-        case 2: return go<T, 2>(p, stream);
-        case 1: return go<T, 1>(p, stream);
+hipError_t go_tm(const GemmParams& p, const GemmTileSched& s, hipStream_t stream) {
+    switch (s.tm) {
+        case 4: return go<T, 4>(p, s, stream);
+        case 3: return go<T, 3>(p, s, stream);
+        case 2: return go<T, 2>(p, s, stream);
+        case 1: return go<T, 1>(p, s, stream);
     }
     return hipErrorInvalidValue;
 }
@@ -334,7 +401,68 @@ double tile_efficiency(const GemmParams& p, int tm, int cus) {
     return cover * balance * steady;
 }
 
+// ---- the round model of a launch's end (the tail decision; profiles/gemm32_tail_lab_fp32.md is the data behind the constants).
+// The kernel is one-shot: a CU holds R = 4 / 3 / 2 workgroups of 128 / 192 / 256 rows (VGPR-limited), the R workgroups of a CU
+// start together and finish together, so a launch runs in rounds of cus x R workgroups and what is left after the whole
+// rounds runs at the occupancy it happens to have: k < R workgroups on a CU deliver occupancy(k) of the CU's steady rate — one
+// wave per SIMD has nothing to cover its barrier, its DMA wait and its epilogue.  Costs are in 64-row tile times of a full CU.
+constexpr int tile_resident(int tm) { return tm >= 4 ? 2 : tm == 3 ? 3 : 4; }
+// Constants from profiles/gemm32_tail_lab_fp32.md: a 499-row q|k|v (144 / 72 / 54 / 36 workgroups of 64 / 128 / 192 / 256 rows, one per CU)
+// against the steady rate of the 15968-row one gives what a workgroup alone on a CU delivers; a launch forced to 64-row tail
+// tiles against the same height without a tail gives the tail tiles' steady rate (q|k|v 0.976, conv1 0.97, fc1 0.946, L.qkv 0.941).
+constexpr double kAloneTall[5] = {0, 0.77, 0.91, 0.91, 0.92};  // one workgroup of tm x 64 rows alone on a CU, share of the steady rate
+constexpr double kAloneTail = 0.77;                            // one 64-row tail workgroup alone on a CU
+constexpr double kTailSteady = 0.95;                           // R co-resident 64-row tail workgroups against R tall ones
+constexpr double kTailMargin = 1.05;                           // a tail must win by this factor on the last round to be used
+double occupancy(int k, int r, double alone) { return k >= r ? 1.0 : 1.0 - (1.0 - alone) * (double)(r - k) / (double)(r - 1); }
+// k workgroups per CU of `units` 64-row units each, R at a time
+double rounds_cost(long k, int r, double units, double alone) {
+    const long whole = k / r, rest = k % r;
+    return (double)whole * r * units + (rest ? (double)rest * units / occupancy((int)rest, r, alone) : 0.0);
+}
+
 }  // namespace
+
+GemmTileSched gemm_tile_schedule(int M, int N, int batches, int tm, int tail_mode, int tail_units, int cus) {
+    const int bm = 64 * tm;
+    GemmTileSched s{tm, (M + bm - 1) / bm, 0};
+    if (!tail_mode || tm < 2) return s;
+    const long per_m = (long)((N + BN - 1) / BN) * batches;  // workgroups per m-tile index
+    int m_bulk;
+    if (tail_mode == 2) {
+        m_bulk = M > bm ? 1 : 0;  // forced: the largest tail that leaves the launch a bulk tile where M holds one
+    } else if (tail_units > 0) {
+        m_bulk = M > 64 * tail_units ? (M - 64 * tail_units) / bm : 0;  // probe: at least tail_units units in the tail
+    } else {
+        // the bulk fills the whole rounds the all-bulk launch would have; the remainder goes to the tail where that is cheaper
+        const int r = tile_resident(tm);
+        const long slots = (long)cus * r, tiles = s.m_bulk * per_m;
+        const long whole = tiles / slots, rest = tiles % slots;
+        if (!whole || !rest) return s;
+        m_bulk = (int)std::min<long>(whole * slots / per_m, M / bm);
+        const long m_tail = (M - m_bulk * bm + 63) / 64;
+        const long past = m_tail * per_m - (whole * slots - m_bulk * per_m);  // tail workgroups the whole rounds have no slot for
+        const double with_tail = past > 0 ? rounds_cost((past + cus - 1) / cus, r, 1.0 / kTailSteady, kAloneTail) : 0.0;
+        const double without = rounds_cost((rest + cus - 1) / cus, r, tm, kAloneTall[tm]);
+        if (with_tail * kTailMargin >= without) return s;
+    }
+    if (m_bulk * bm >= M) return s;  // nothing left for a tail
+    s.m_bulk = m_bulk;
+    s.m_tail = (M - m_bulk * bm + 63) / 64;
+    return s;
+}
+
+void gemm_tile_items(int M, int N, int batches, const GemmTileSched& s, std::vector<int>& items4) {
+    const int n_tiles = (N + BN - 1) / BN, bm = 64 * s.tm;
+    const int nwg = (s.m_bulk + s.m_tail) * n_tiles * batches;
+    items4.clear();
+    items4.reserve((size_t)nwg * 4);
+    for (int wg = 0; wg < nwg; ++wg) {
+        const TileItem it = tile_item(wg, nwg, n_tiles, batches, bm, s.m_bulk, s.m_tail);
+        const int rows = std::min(it.tail ? 64 : bm, M - it.m0);
+        items4.insert(items4.end(), {it.b, it.m0, rows, it.n0});
+    }
+}
 
 int device_cus() {
     static int cus = 0;
@@ -397,7 +525,8 @@ bool gemm_tile_eligible(int dtype, const GemmParams& p) {
 
 hipError_t launch_gemm_tile(int dtype, const GemmParams& p, hipStream_t stream) {
     const int tm = gemm_tile_pick(dtype == F32 ? tuning().gemm32_big : tuning().gemm_x3_tile, p);
-    return dtype == 3 ? go_tm<x3_tag>(tm, p, stream) : go_tm<float>(tm, p, stream);
+    if (dtype == 3) return go_tm<x3_tag>(p, gemm_tile_schedule(p.M, p.N, p.batches, tm, 0, 0, device_cus()), stream);
+    return go_tm<float>(p, gemm_tile_schedule(p.M, p.N, p.batches, tm, tuning().gemm32_tail, tuning().gemm32_tail_units, device_cus()), stream);
 }
 
 }  // namespace s3

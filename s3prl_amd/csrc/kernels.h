@@ -31,6 +31,9 @@ struct Tuning {
     int gemm_lds_pad = 0;  // gemm.hip occupancy probe: extra (unused) dynamic LDS per workgroup
     int gemm32_big = 1;    // gemmt.hip, fp32: 0 off, 1 = tile height by shape, 2..5 = force 256 / 192 / 128 / 64 rows
     int gemm_x3_tile = 1;  // gemmt.hip, S3ENC_F32X3: 0 off, 1 = only the shapes with few tiles, 2..5 = force a height
+    int gemm32_tail = 1;   // gemmt.hip, fp32: a launch of 128 / 192 / 256-row tiles may end with a tail region of 64-row tiles (the last
+                           // workgroups dispatched; same bits): 0 = never, 1 = where the round model says it pays, 2 = every launch, largest tail
+    int gemm32_tail_units = 0;  // lab probe under gemm32_tail = 1: 0 = the model's tail, n = a tail of n 64-row units of every batch's M
     int gemm16_big = 3;    // gemm16.hip: 0 off, 3 = choose by shape, 1 / 2 / 4 / 5 / 6 / 7 = force one configuration
     int gemm16_pp = 0;     // gemm16.hip, persistent loop: 0 = every wave issues its LDS-DMA pieces behind fragment steps 0 / 1;
                            // non-zero = waves 4-7 (the SIMD partners of waves 0-3) behind steps 1 / 2 instead (PP 3; measured
@@ -167,6 +170,15 @@ hipError_t launch_gemm16_big(int dtype, const GemmParams& p, hipStream_t stream)
 // gemm.hip's kernel.  tuning().gemm32_big (fp32) / .gemm_x3_tile (S3ENC_F32X3 = dtype code 3 below: fp32 operands, the
 // pair-packed p.W_x3)
 bool gemm_tile_eligible(int dtype, const GemmParams& p);
+// The schedule of one fp32 launch: per batch `m_bulk` tiles of 64 tm rows from row 0, then `m_tail` tiles of 64 rows (the last
+// one of a region may be ragged); both regions cover every 128-column tile and every batch.  Host arithmetic on (M, N, batches,
+// tm, the "gemm32_tail" setting, its probe units, CUs) only.  gemm_tile_items lists the (batch, m0, rows, n0) of every
+// workgroup in blockIdx order through the kernel's own block -> tile map (s3enc_debug_gemm_schedule).
+struct GemmTileSched {
+    int tm, m_bulk, m_tail;
+};
+GemmTileSched gemm_tile_schedule(int M, int N, int batches, int tm, int tail_mode, int tail_units, int cus);
+void gemm_tile_items(int M, int N, int batches, const GemmTileSched& s, std::vector<int>& items4);
 hipError_t launch_gemm_tile(int dtype, const GemmParams& p, hipStream_t stream);
 hipError_t launch_gemm(int dtype, const GemmParams& p, hipStream_t stream);
 // convf22.hip: exact-fp32 Conv1d(C, C, k = 3, stride = 2) on channel-last rows in the two-output form (5 block products per

@@ -27,6 +27,7 @@ int tuning_set(Tuning& t, const char* key, int value, const char** err) {
         {"ln_preload", &Tuning::ln_preload, 0, 1},           {"forward_chain", &Tuning::forward_chain, 0, 1},
         {"conv0_fast", &Tuning::conv0_fast, 0, 1},           {"conv_f22", &Tuning::conv_f22, 0, 1},
         {"rnn_split", &Tuning::rnn_split, -1, 8},           {"npc_skip_taps", &Tuning::npc_skip_taps, 0, 1},
+        {"gemm32_tail", &Tuning::gemm32_tail, 0, 2},         {"gemm32_tail_units", &Tuning::gemm32_tail_units, 0, 1 << 20},
     };
     static thread_local char msg[160];
     if (!key) {
@@ -194,6 +195,19 @@ int s3enc_debug_clock_sample(uint64_t* out3_device, void* stream) {
     hipLaunchKernelGGL(clock_sample_kernel, dim3(64), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)out3_device,
                        (unsigned long long)khz);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int s3enc_debug_gemm_schedule(int32_t M, int32_t N, int32_t batches, int32_t tm, int32_t tail, int32_t cus, int32_t* items4_host,
+                              int64_t max_items, int64_t* n_items) {
+    if (!n_items) return fail("s3enc_debug_gemm_schedule: null argument");
+    if (M < 1 || N < 1 || batches < 1 || tm < 1 || tm > 4 || tail < 0 || tail > 2 || cus < 1)
+        return fail("s3enc_debug_gemm_schedule: M, N, batches, cus >= 1, tm 1..4, tail 0..2");
+    const GemmTileSched s = gemm_tile_schedule(M, N, batches, tm, tail, 0, cus);
+    std::vector<int> items;
+    gemm_tile_items(M, N, batches, s, items);
+    *n_items = (int64_t)(items.size() / 4);
+    if (items4_host && max_items >= *n_items) memcpy(items4_host, items.data(), items.size() * sizeof(int));
     return 0;
 }
 

@@ -2,6 +2,9 @@
 // large models' layer shapes), through the C ABI (s3enc_op_gemm + the "gemm32_big" / "gemm16_tile" tuning keys):
 //   fp32 (default):  mode 0 = gemm_kernel<float> (128x128 tile), 2 / 3 / 4 / 5 = the 256 / 192 / 128 / 64 x 128 tile of gemmt.hip,
 //                    1 = the library's own choice.  Every mode's output is compared BIT FOR BIT with mode 0.
+//                    Each height is also measured with "gemm32_tail" = 2 (the launch ends with the largest tail of 64-row tiles),
+//                    the library's choice with "gemm32_tail" = 0 (no tail: the launches before the key existed) and = 1 (by
+//                    shape); a second table sweeps the probe key "gemm32_tail_units" under the chosen height.
 //   bf16 (argv[3] = bf16): mode 0 = gemm16.hip's 256x256 lock-step tile, the others gemmt.hip; outputs are compared with
 //                    mode 0 by count of values that differ (different k order: rounding-level differences are expected), and
 //                    the gemmt.hip heights with each other bit for bit.
@@ -107,8 +110,27 @@ int main(int argc, char** argv) {
         {"sq8k 8192^3", 1, 8192, 8192, 8192, 8192, 0, 0, 0, 0},
         {"small 1x499 qkv 499x2304x768", 1, 499, 2304, 768, 768, 0, 0, 0, 0},
     };
-    const int modes[] = {0, 2, 3, 4, 5, 1};
-    const int NM = 6;
+    struct Config {
+        int big, tail, units;
+        const char* name;
+    };
+    std::vector<Config> cfg;
+    if (x3) {
+        cfg = {{0, 0, 0, "gemm_x3.hip 256x256 (mode 0)"}, {2, 0, 0, "256x128"}, {3, 0, 0, "192x128"}, {4, 0, 0, "128x128"}, {5, 0, 0, "64x128"}, {1, 0, 0, "auto"}};
+    } else {
+        cfg = {{0, 0, 0, "gemm.hip 128x128 (mode 0)"}, {1, 0, 0, "auto, no tail"}, {2, 0, 0, "256"}, {3, 0, 0, "192"}, {4, 0, 0, "128"}, {5, 0, 0, "64"},
+               {2, 2, 0, "256+tail"}, {3, 2, 0, "192+tail"}, {4, 2, 0, "128+tail"}, {1, 1, 0, "auto"},
+               {1, 1, 8, "u8"}, {1, 1, 16, "u16"}, {1, 1, 32, "u32"}, {1, 1, 64, "u64"}, {1, 1, 128, "u128"}};
+    }
+    const int NM = (int)cfg.size();
+    const int AUTO0 = 1, AUTO1 = x3 ? 5 : 9, NMAIN = x3 ? NM : 10;
+    auto set = [&](const Config& c) {
+        s3enc_set_tuning(key, c.big);
+        if (!x3) {
+            s3enc_set_tuning("gemm32_tail", c.tail);
+            s3enc_set_tuning("gemm32_tail_units", c.units);
+        }
+    };
     hipStream_t st;
     CK(hipStreamCreate(&st));
     hipEvent_t e0, e1;
@@ -116,8 +138,12 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e1));
     unsigned long long* d_cnt;
     CK(hipMalloc(&d_cnt, 8));
-    printf("%s GEMMs, TFLOP/s\n\n| shape | act/res | %s (mode 0) | 256x128 | 192x128 | 128x128 | 64x128 | auto | vs mode 0 |\n|---|---|---:|---:|---:|---:|---:|---:|---|\n",
-           h16 ? "bf16" : (x3 ? "fp32x3" : "fp32"), h16 ? "gemm16.hip 256x256" : (x3 ? "gemm_x3.hip 256x256" : "gemm.hip 128x128"));
+    printf("%s GEMMs, TFLOP/s (best of %d interleaved rounds; spread = slowest round of a column against its best)\n\n| shape | act/res |", x3 ? "fp32x3" : "fp32", rounds);
+    for (int m = 0; m < NMAIN; ++m) printf(" %s |", cfg[m].name);
+    printf(" spread auto, no tail | spread auto | vs mode 0 |\n|---|---|");
+    for (int m = 0; m < NMAIN; ++m) printf("---:|");
+    printf("---:|---:|---|\n");
+    std::string sweep;  // the second table
     for (const Shape& s : shapes) {
         if (only) {  // comma-separated substrings
             bool hit = false;
@@ -169,19 +195,18 @@ int main(int argc, char** argv) {
                 exit(1);
             }
         };
-        double best[NM];
+        std::vector<double> best(NM, 1e30), worst(NM, 0.0);
         std::string bit;
         const double flops = 2.0 * s.batches * s.M * (double)s.N * s.K;
-        for (int m = 0; m < NM; ++m) best[m] = 1e30;
         // correctness first: every mode against mode 0, whole output, bit for bit
-        s3enc_set_tuning(key, 0);
+        set(cfg[0]);
         CK(hipMemsetAsync(ref, 0xff, o_elems * 4, st));
         run(ref);
         const bool o16 = h16 && !s.residual && !s.limit;
         float* first = nullptr;  // 16-bit: the first gemmt.hip height, the others must equal it bit for bit
         if (h16) CK(hipMalloc(&first, o_elems * 4));
         for (int m = 1; m < NM; ++m) {
-            s3enc_set_tuning(key, modes[m]);
+            set(cfg[m]);
             CK(hipMemsetAsync(out, 0xff, o_elems * 4, st));
             run(out);
             auto count = [&](const float* x, const float* y, int how) {
@@ -197,14 +222,14 @@ int main(int argc, char** argv) {
             };
             if (!h16) {
                 const unsigned long long c = count(out, ref, 0);
-                bit += c ? ("mode" + std::to_string(modes[m]) + ":" + std::to_string(c) + "DIFF ") : "";
+                bit += c ? (std::string(cfg[m].name) + ":" + std::to_string(c) + "DIFF ") : "";
             } else {
                 const unsigned long long far = count(out, ref, 1);
-                if (far) bit += "mode" + std::to_string(modes[m]) + ":" + std::to_string(far) + "FAR ";
+                if (far) bit += std::string(cfg[m].name) + ":" + std::to_string(far) + "FAR ";
                 if (m == 1) CK(hipMemcpyAsync(first, out, o_elems * 4, hipMemcpyDeviceToDevice, st));
                 else {
                     const unsigned long long c = count(out, first, 0);
-                    if (c) bit += "mode" + std::to_string(modes[m]) + ":" + std::to_string(c) + "!=mode2 ";
+                    if (c) bit += std::string(cfg[m].name) + ":" + std::to_string(c) + "!=mode2 ";
                 }
             }
         }
@@ -213,7 +238,7 @@ int main(int argc, char** argv) {
         const int iters = std::max(2, (int)((h16 ? 2e13 : (x3 ? 8e12 : 3e12)) / flops));  // ~20 ms per measurement
         for (int r = 0; r < rounds; ++r)
             for (int m = 0; m < NM; ++m) {
-                s3enc_set_tuning(key, modes[m]);
+                set(cfg[m]);
                 run(out);  // warm
                 CK(hipEventRecord(e0, st));
                 for (int i = 0; i < iters; ++i) run(out);
@@ -222,15 +247,33 @@ int main(int argc, char** argv) {
                 float ms;
                 CK(hipEventElapsedTime(&ms, e0, e1));
                 best[m] = std::min(best[m], (double)ms / iters);
+                worst[m] = std::max(worst[m], (double)ms / iters);
             }
         printf("| %s | %d/%d |", s.name, s.act, s.residual);
-        for (int m = 0; m < NM; ++m) printf(" %.1f |", flops / best[m] * 1e-9);
-        printf(" %s |\n", bit.c_str());
+        for (int m = 0; m < NMAIN; ++m) printf(" %.1f |", flops / best[m] * 1e-9);
+        printf(" %.1f %% | %.1f %% | %s |\n", (worst[AUTO0] / best[AUTO0] - 1) * 100, (worst[AUTO1] / best[AUTO1] - 1) * 100, bit.c_str());
+        if (NM > NMAIN) {
+            char line[512];
+            int n = snprintf(line, sizeof(line), "| %s | %.1f | %.1f |", s.name, flops / best[AUTO0] * 1e-9, flops / best[AUTO1] * 1e-9);
+            for (int m = NMAIN; m < NM; ++m) n += snprintf(line + n, sizeof(line) - n, " %.1f |", flops / best[m] * 1e-9);
+            sweep += line;
+            sweep += "\n";
+        }
         fflush(stdout);
         CK(hipFree(A)); CK(hipFree(W)); CK(hipFree(bias)); CK(hipFree(res)); CK(hipFree(out)); CK(hipFree(ref));
         if (lim) CK(hipFree(lim));
     }
+    if (!sweep.empty()) {
+        printf("\nTail size under the chosen height: \"gemm32_tail_units\" = n puts at least n 64-row units of every batch's M into the tail\n\n"
+               "| shape | auto, no tail | auto |");
+        for (int m = NMAIN; m < NM; ++m) printf(" %s |", cfg[m].name);
+        printf("\n|---|---:|---:|");
+        for (int m = NMAIN; m < NM; ++m) printf("---:|");
+        printf("\n%s", sweep.c_str());
+    }
     s3enc_set_tuning("gemm32_big", 1);
     s3enc_set_tuning("gemm_x3_tile", 1);
+    s3enc_set_tuning("gemm32_tail", 1);
+    s3enc_set_tuning("gemm32_tail_units", 0);
     return 0;
 }
