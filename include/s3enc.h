@@ -72,7 +72,13 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * Conv1d (kernel_size taps with a hole of mask_size + 2 (i + 1) in the middle) -> tanh, summed over the blocks.  No length
         * masking anywhere: 2 n_blocks + 1 states of (B, T, hidden) (n_blocks + 2 with disable_cross_layer) whose rows behind an
         * utterance's own frames are the reference's values, not zeros.  compute_dtype S3ENC_F32 only; built by s3enc_create_npc. */
-       S3ENC_NPC = 10 };
+       S3ENC_NPC = 10,
+       /* VGGish (upstream/vggish/{audio,vggish,expert}.py): a log-mel front end without padding (periodic Hann window, |rfft|, HTK
+        * mel, log(. + offset)) cut into examples of example_frames frames, a stack of 3 x 3 Conv2d + ReLU (+ 2 x 2 max-pool) layers
+        * over every example, three Linear + ReLU layers and — with postprocess — the PCA / clamp / 8-bit quantiser.  One state of
+        * (B, E_max, fc[2]): an utterance's examples, exact zeros behind them (pad_sequence).  compute_dtype S3ENC_F32 only; built by
+        * s3enc_create_vggish. */
+       S3ENC_VGGISH = 11 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -321,6 +327,42 @@ typedef struct s3enc_npc_config {
     int32_t dim_bottleneck;                         /* 0: none; the auto-encoder bottleneck gives the last state another width (refused) */
 } s3enc_npc_config;
 
+/* S3ENC_VGGISH only (vggish/audio.py:30-84,256-294, vggish/vggish.py:18-133, vggish/expert.py:16-40): the second configuration
+ * block of s3enc_create_vggish.  s3enc_config carries the frame geometry as APC does: n_conv = 1, conv_kernel[0] / conv_stride[0]
+ * = window / shift in samples (400 / 160; both multiples of 4), conv_dim = embed_dim = fc[2], encoder_layers = 0 (one state).
+ * Front end, 16 kHz input: frames of `window` samples every `shift` samples with NO padding, F = 1 + (n - window) / shift; each
+ * times the periodic Hann window; |rfft(., n_fft)|; the (n_fft / 2 + 1) x num_mel_bins HTK mel matrix (edges linear in mel = 1127
+ * ln(1 + f / 700) between mel_min_hz and mel_max_hz, DC row zero); log(. + log_offset); examples of example_frames frames every
+ * example_hop frames, incomplete tails dropped: E = 1 + (F - example_frames) / example_hop for F >= example_frames, else 0.
+ * Model: n_layers times Conv2d(3 x 3, padding 1) + ReLU, layer i followed by MaxPool2d(2, 2) when pool_after[i]; the last map is
+ * flattened in (frames, bands, channels) order; Linear + ReLU three times (widths fc[0..2]); with `postprocess`
+ * q = rint((clamp(P (y - m), quant_min, quant_max) - quant_min) * (255 / (quant_max - quant_min))), rint half to even.
+ * Checkpoint tensors, reference state_dict names: features.K.{weight,bias} with K the layer's index in the reference's
+ * nn.Sequential (a conv + its ReLU count two, a pool one: 0, 3, 6, 8, 11, 13 at the released shape), embeddings.{0,2,4}.
+ * {weight,bias}, and with postprocess pca_eigen_vectors (D, D) and pca_means (D) or (D, 1), D = fc[2].  s3enc_create_vggish
+ * refuses by name: every compute dtype but fp32, n_layers outside 1..8, channels that are not a multiple of 16, example_frames or
+ * num_mel_bins not divisible by 2^pools, example_hop other than example_frames, window / shift that are not multiples of 4
+ * samples, an n_fft that is not the power of two at or above window, Linear widths that are not multiples of 4. */
+#define S3ENC_VGGISH_MAX_LAYERS 8
+typedef struct s3enc_vggish_config {
+    int32_t num_mel_bins;                           /* 64 */
+    int32_t window;                                 /* samples: 400 */
+    int32_t shift;                                  /* samples: 160 */
+    int32_t n_fft;                                  /* 512 */
+    float mel_min_hz;                               /* 125 */
+    float mel_max_hz;                               /* 7500 */
+    float log_offset;                               /* 0.01 */
+    int32_t example_frames;                         /* 96 */
+    int32_t example_hop;                            /* 96: must equal example_frames */
+    int32_t n_layers;                               /* 6 */
+    int32_t channels[S3ENC_VGGISH_MAX_LAYERS];      /* 64, 128, 256, 256, 512, 512 */
+    int32_t pool_after[S3ENC_VGGISH_MAX_LAYERS];    /* 1, 1, 0, 1, 0, 1 */
+    int32_t fc[3];                                  /* 4096, 4096, 128 */
+    int32_t postprocess;                            /* 1 */
+    float quant_min;                                /* -2 */
+    float quant_max;                                /* +2 */
+} s3enc_vggish_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -387,6 +429,14 @@ int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* deco
  * reference's value for this T; an utterance's rows depend on T and on nothing else of the batch. */
 int s3enc_create_npc(const s3enc_config* cfg, const s3enc_npc_config* npc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out);
+/* The S3ENC_VGGISH family: s3enc_config beside its own block (the other create entries refuse the family by name).  Replaces
+ * UpstreamExpert.__init__ of upstream/vggish/expert.py.  On the handle: s3enc_num_frames(n) is the number of examples E (0 below
+ * window + (example_frames - 1) * shift samples = 15600, and the forward refuses such an utterance by index and length);
+ * s3enc_valid_frames is the utterance's own E, the rows behind it are exact zeros (also in the quantised form);
+ * s3enc_downsample_rate is 16000 (expert.py:21-22, although the examples are 15360 samples apart); s3enc_num_states is 1 for
+ * S3ENC_SEL_HIDDEN (the other selections are refused), out_dtype must be S3ENC_F32. */
+int s3enc_create_vggish(const s3enc_config* cfg, const s3enc_vggish_config* vggish, const s3enc_tensor* tensors, int32_t n_tensors,
+                        int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -751,6 +801,21 @@ int s3enc_op_rnn_len(int32_t cell, const float* pre, const float* w_hh_host, con
 int s3enc_op_conv_taps(const float* x, const float* w_host, const float* bias, int32_t B, int32_t T, int32_t C, int32_t N, int32_t k,
                        int32_t mask, int32_t act, const float* res, int64_t ld_res, float* dst, int32_t dst_pad, int64_t ldo,
                        float* state, float* sum, int32_t sum_init, int32_t dense, void* stream);
+
+/* Stride-1 nn.Conv2d(C, N, 3, padding = 1) on channel-last images, exact fp32, with bias -> act -> optional nn.MaxPool2d(2, 2) in
+ * one pass (conv2d.hip; VGGish's features stack):
+ *   v[b][y][x][:] = act(sum_{ky, kx} W[:, :, ky, kx] img[b][y + ky][x + kx] + bias),  act 0 none / 1 ReLU;
+ *   pool = 1: out[b][y'][x'] = max of v over the 2 x 2 window (a NaN stays a NaN), H and W even; pool = 0: out = v.
+ * x: device fp32, the BORDERED operand (B, H + 2, W + 2, C): every example's outermost pixels are zeros (the caller zeroes them).
+ * w_host: HOST fp32 (N, C, 3, 3), nn.Conv2d's layout; packed tap-major (N, 9 C) and uploaded inside.  bias: device fp32 [N] or null.
+ * dst: a bordered (B, Ho + 2 dst_pad, Wo + 2 dst_pad, ldo) buffer, Ho x Wo = H x W or H / 2 x W / 2 under pool, of which only the
+ * interior pixels and columns [0, N) are written; dst_pad = 0 is a plain (B, Ho, Wo, ldo) tensor.  The un-pooled activation is
+ * never written.  C = 1 runs the first-layer VALU kernel, otherwise C % 16 == 0 and the product runs on the fp32 MFMA as an
+ * implicit GEMM over the pixels of all examples; N % 4 == 0, ldo % 4 == 0, ldo >= N, 16-byte aligned pointers (C = 1: x 4-byte).
+ * An example's bits depend neither on B, nor on its place in the batch, nor on the tiling; the pooled output is bit for bit the
+ * max over the un-pooled output.  Synchronises. */
+int s3enc_op_conv2d3x3(const float* x, const float* w_host, const float* bias, int32_t B, int32_t H, int32_t W, int32_t C, int32_t N,
+                       int32_t act, int32_t pool, float* dst, int32_t dst_pad, int64_t ldo, void* stream);
 
 /* A forward and a backward unidirectional nn.LSTM on packed sequences, side by side, on the batch-shared kernel: one launch per
  * time step for both directions, W_hh read once per step for the whole batch (fp32 MFMA).  pre_fwd / pre_bwd: device fp32, row

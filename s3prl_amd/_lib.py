@@ -19,7 +19,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -106,6 +106,19 @@ class S3NpcConfig(C.Structure):
     ]
 
 
+S3ENC_VGGISH_MAX_LAYERS = 8
+
+
+class S3VggishConfig(C.Structure):
+    """s3enc_vggish_config: the front-end / layer block of a VGGish handle (s3enc_create_vggish)."""
+    _fields_ = [
+        ("num_mel_bins", C.c_int32), ("window", C.c_int32), ("shift", C.c_int32), ("n_fft", C.c_int32), ("mel_min_hz", C.c_float),
+        ("mel_max_hz", C.c_float), ("log_offset", C.c_float), ("example_frames", C.c_int32), ("example_hop", C.c_int32),
+        ("n_layers", C.c_int32), ("channels", C.c_int32 * S3ENC_VGGISH_MAX_LAYERS), ("pool_after", C.c_int32 * S3ENC_VGGISH_MAX_LAYERS),
+        ("fc", C.c_int32 * 3), ("postprocess", C.c_int32), ("quant_min", C.c_float), ("quant_max", C.c_float),
+    ]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -139,6 +152,7 @@ _PROTOS = {
                                           C.POINTER(_VP)]),
     "s3enc_create_decoar": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3DecoarConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_npc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3NpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    "s3enc_create_vggish": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3VggishConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -189,6 +203,7 @@ _PROTOS = {
     "s3enc_pack_lstm_bidir_whh": (C.c_int, [_VP, _I32, _VP]),
     "s3enc_op_conv_taps": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _I64, _VP, _VP,
                                      _I32, _I32, _VP]),
+    "s3enc_op_conv2d3x3": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
@@ -398,4 +413,25 @@ def make_npc_config(cfg) -> S3NpcConfig:
     c.activate = NPC_ACTIVATE.get(cfg.npc_activate, -1)
     c.disable_cross_layer = int(cfg.npc_disable_cross_layer)
     c.dim_bottleneck = int(cfg.npc_dim_bottleneck or 0)
+    return c
+
+
+def make_vggish_config(cfg) -> S3VggishConfig:
+    """The second configuration block of a ``family="vggish"`` EncoderConfig (``s3enc_create_vggish``)."""
+    if cfg.family != "vggish":
+        raise S3EncError("make_vggish_config needs a vggish configuration")
+    if len(cfg.vg_layers) > S3ENC_VGGISH_MAX_LAYERS:
+        raise S3EncError("too many vggish conv layers")
+    c = S3VggishConfig()
+    c.num_mel_bins, c.n_fft = int(cfg.vg_num_mel_bins), int(cfg.vg_n_fft)
+    c.window, c.shift = int(cfg.conv_layers[0][1]), int(cfg.conv_layers[0][2])
+    c.mel_min_hz, c.mel_max_hz, c.log_offset = float(cfg.vg_mel_min_hz), float(cfg.vg_mel_max_hz), float(cfg.vg_log_offset)
+    c.example_frames, c.example_hop = int(cfg.vg_example_frames), int(cfg.vg_example_hop)
+    c.n_layers = len(cfg.vg_layers)
+    for i, (ch, pool) in enumerate(cfg.vg_layers):
+        c.channels[i], c.pool_after[i] = int(ch), int(bool(pool))
+    for i, f in enumerate(cfg.vg_fc):
+        c.fc[i] = int(f)
+    c.postprocess = int(cfg.vg_postprocess)
+    c.quant_min, c.quant_max = float(cfg.vg_quant_min), float(cfg.vg_quant_max)
     return c

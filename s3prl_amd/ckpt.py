@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, decoar_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -101,6 +101,64 @@ def load_npc_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]
             raise ValueError(f"{ckpt}: {name} is not the mask of kernel_size {k} / mask_size {cfg.npc_mask_size} (block {i}: taps "
                              f"[{head}, {head + cfg.npc_mask(i)}) zeroed)")
     return cfg, weights
+
+
+def vggish_geometry(cfg: EncoderConfig) -> Dict:
+    """What a VGGish state dict does not show: the front end and the quantiser's range (``vggish_params.py`` in the reference)."""
+    return dict(example_frames=cfg.vg_example_frames, num_mel_bins=cfg.vg_num_mel_bins, window=cfg.conv_layers[0][1],
+                shift=cfg.conv_layers[0][2], mel_min_hz=cfg.vg_mel_min_hz, mel_max_hz=cfg.vg_mel_max_hz,
+                log_offset=cfg.vg_log_offset, quant_min=cfg.vg_quant_min, quant_max=cfg.vg_quant_max)
+
+
+def load_vggish_checkpoint(ckpt, postprocess: bool = True) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"vggish": state_dict, "pca": {"pca_eigen_vectors", "pca_means"}}`` (upstream/vggish/hubconf.py:22-31, vggish.py:136-156) —
+    a dict, as the reference's expert takes it, or the path of a file holding one.  The files carry no configuration: the layer
+    list is read off the tensors themselves (``features.K.weight`` in ``nn.Sequential`` order, a gap of 3 between two conv indices
+    is a pool; a pool behind the last conv is taken when the flattened width of ``embeddings.0.weight`` asks for it), the front
+    end is ``vggish_params.py``'s unless the dict carries this package's ``config`` entry (``vggish_geometry``).  ``pca_means`` may be ``(D,)`` or ``(D, 1)``; without ``postprocess`` the ``pca`` entry is not
+    read."""
+    if not isinstance(ckpt, dict):
+        import torch
+
+        ckpt = torch.load(ckpt, map_location="cpu", weights_only=False)
+    if "vggish" not in ckpt:
+        raise ValueError("a VGGish checkpoint is a dict with the key 'vggish' (and 'pca' with postprocess): 'vggish' is missing")
+    sd = ckpt["vggish"]
+    idx = sorted(int(k.split(".")[1]) for k in sd if k.startswith("features.") and k.endswith(".weight"))
+    if not idx or idx[0] != 0:
+        raise ValueError("VGGish checkpoint: no features.0.weight")
+    layers = []
+    for j, k in enumerate(idx):
+        gap = (idx[j + 1] - k) if j + 1 < len(idx) else 2
+        if gap not in (2, 3):
+            raise ValueError(f"VGGish checkpoint: features.{k} is followed by features.{k + gap}: not a conv + ReLU (+ pool) stack")
+        layers.append((int(sd[f"features.{k}.weight"].shape[0]), gap == 3))
+    for name in ("embeddings.0.weight", "embeddings.2.weight", "embeddings.4.weight"):
+        if name not in sd:
+            raise ValueError(f"VGGish checkpoint: missing parameter {name}")
+    fc = tuple(int(sd[f"embeddings.{i}.weight"].shape[0]) for i in (0, 2, 4))
+    flat, (ch, _) = int(sd["embeddings.0.weight"].shape[1]), layers[-1]
+    geometry = dict(ckpt.get("config") or {})
+    frames, bands = int(geometry.get("example_frames", 96)), int(geometry.get("num_mel_bins", 64))
+    pools = sum(p for _, p in layers)
+    if flat * (4 ** (pools + 1)) == frames * bands * ch:
+        layers[-1] = (ch, True)
+    cfg = vggish_config(layers=layers, fc=fc, postprocess=postprocess, **geometry)
+    what = "the VGGish checkpoint"
+    merged = dict(sd)
+    if postprocess:
+        if "pca" not in ckpt:
+            raise ValueError("a VGGish checkpoint needs the key 'pca' with postprocess=True")
+        for name in ("pca_eigen_vectors", "pca_means"):
+            if name not in ckpt["pca"]:
+                raise ValueError(f"{what}: missing parameter pca.{name}")
+            merged[name] = ckpt["pca"][name]
+        m = merged["pca_means"]
+        m = m.detach().cpu().float().numpy() if hasattr(m, "detach") else np.asarray(m, dtype=np.float32)
+        if m.shape not in ((fc[2],), (fc[2], 1)):
+            raise ValueError(f"{what}: parameter pca_means has shape {tuple(m.shape)}, expected ({fc[2]},) or ({fc[2]}, 1)")
+        merged["pca_means"] = m.reshape(fc[2])
+    return cfg, _hot_path_weights(what, cfg, merged)
 
 
 def load_decoar_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
@@ -215,6 +273,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_decoar_checkpoint(ckpt)
     if family == "npc":
         return load_npc_checkpoint(ckpt)
+    if family == "vggish":
+        return load_vggish_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -268,6 +328,11 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
         return
     if cfg.family == "decoar":  # upstream/decoar/expert.py:30-36
         torch.save({"model": sd}, path)
+        return
+    if cfg.family == "vggish":  # upstream/vggish/hubconf.py:22-31: the two state dicts in one file
+        # "config" is this package's addition (the reference reads "vggish" and "pca" only): a shape other than the released one
+        pca = {k: sd.pop(k) for k in ("pca_eigen_vectors", "pca_means") if k in sd}
+        torch.save({"vggish": sd, "pca": pca, "config": vggish_geometry(cfg)}, path)
         return
     if cfg.family == "npc":  # upstream/npc/expert.py:22-26
         audio = dict(feat_type=cfg.apc_feat_type, feat_dim=cfg.apc_feat_dim, frame_length=cfg.apc_frame_length,

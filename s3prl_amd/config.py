@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -189,6 +189,23 @@ class EncoderConfig:
     npc_vq: Dict | None = None        # paras.vq: feeds only the discarded prediction; kept for the checkpoint round trip
     npc_dim_bottleneck: int | None = None  # paras.dim_bottleneck: the last state would have another width (refused)
 
+    # VGGish (family "vggish", upstream/vggish/{audio,vggish,vggish_params}.py): an un-padded log-mel front end cut into examples,
+    # a 3 x 3 Conv2d + ReLU (+ 2 x 2 max-pool) stack, three Linear + ReLU layers and the PCA / 8-bit quantiser.
+    # ``conv_layers`` = [(embedding width, window, shift)] in samples; ``encoder_layers`` = 0: one state
+    vg_num_mel_bins: int = 64         # NUM_MEL_BINS
+    vg_n_fft: int = 512               # the power of two at or above the window
+    vg_mel_min_hz: float = 125.0      # MEL_MIN_HZ
+    vg_mel_max_hz: float = 7500.0     # MEL_MAX_HZ
+    vg_log_offset: float = 0.01       # LOG_OFFSET
+    vg_example_frames: int = 96       # EXAMPLE_WINDOW_SECONDS in frames
+    vg_example_hop: int = 96          # EXAMPLE_HOP_SECONDS in frames (only = vg_example_frames is built)
+    vg_layers: List[Tuple[int, bool]] = field(default_factory=lambda: [(64, True), (128, True), (256, False), (256, True),
+                                                                      (512, False), (512, True)])  # (channels, pool behind it)
+    vg_fc: Tuple[int, int, int] = (4096, 4096, 128)  # the three Linear widths; the last one is the embedding
+    vg_postprocess: bool = True       # the PCA + clamp + 8-bit quantiser (vggish.py:44-120)
+    vg_quant_min: float = -2.0        # QUANTIZE_MIN_VAL
+    vg_quant_max: float = 2.0         # QUANTIZE_MAX_VAL
+
     # ---- derived -------------------------------------------------------------------------
     @property
     def conv_dim(self) -> int:
@@ -212,6 +229,8 @@ class EncoderConfig:
 
     @property
     def downsample_rate(self) -> int:
+        if self.family == "vggish":  # vggish/expert.py:21-22 (the examples are 15360 samples apart; the reference says 16000)
+            return 16000
         r = 1
         for _, _, s in self.conv_layers:
             r *= s
@@ -231,6 +250,9 @@ class EncoderConfig:
             return 1 + n // 160 if n > 200 else 0
         if self.family == "decoar":  # ceil(fbank frames / subsample)
             return -(-self.conv_lengths(n)[-1] // self.decoar_subsample)
+        if self.family == "vggish":  # examples: complete groups of vg_example_frames un-padded frames (audio.py:90-111)
+            F = self.conv_lengths(n)[-1]
+            return 1 + (F - self.vg_example_frames) // self.vg_example_hop if F >= self.vg_example_frames else 0
         return self.conv_lengths(n)[-1]
 
     def valid_frames(self, length: int, n_max: int) -> int:
@@ -249,7 +271,7 @@ class EncoderConfig:
             return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
         if self.family == "mockingjay":
             return min(T, max(self.num_frames(length), 0))
-        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "npc"):  # distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
+        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "npc", "vggish"):  # vggish: the utterance's own examples, exact zeros behind them; distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -358,6 +380,8 @@ class EncoderConfig:
             return self._validate_decoar()
         if self.family == "npc":
             return self._validate_npc()
+        if self.family == "vggish":
+            return self._validate_vggish()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -505,6 +529,56 @@ class EncoderConfig:
         states = self.npc_blocks + 2 if self.npc_disable_cross_layer else 2 * self.npc_blocks + 1
         if self.encoder_layers != states - 1 or self.encoder_embed_dim != H:
             raise ValueError("npc: encoder_layers / encoder_embed_dim must be the number of states - 1 / hidden_size (npc_config sets them)")
+
+    @property
+    def vg_pools(self) -> int:
+        return sum(1 for _, pool in self.vg_layers if pool)
+
+    def vg_seq_index(self, i: int) -> int:
+        """Index of conv layer ``i`` in the reference's ``nn.Sequential`` (vggish.py:123-133): a conv and its ReLU count two, a
+        pool one — 0, 3, 6, 8, 11, 13 at the released shape."""
+        return sum(2 + int(pool) for _, pool in self.vg_layers[:i])
+
+    @property
+    def vg_min_samples(self) -> int:
+        """The shortest utterance that yields one example (15600 at the released shape)."""
+        return self.conv_layers[0][1] + (self.vg_example_frames - 1) * self.conv_layers[0][2]
+
+    def _validate_vggish(self) -> None:
+        """What the HIP path builds of VGGish; everything else is refused by name (s3enc_create_vggish repeats it)."""
+        if not 1 <= len(self.vg_layers) <= 8:
+            raise ValueError(f"vggish needs 1..8 conv layers, got {len(self.vg_layers)}")
+        for i, (ch, _) in enumerate(self.vg_layers):
+            if ch % 16 or not 16 <= ch <= 4096:
+                raise ValueError(f"vggish channels of layer {i} must be a multiple of 16, at most 4096 (a tap is a whole number of "
+                                 f"64-byte K steps), got {ch}")
+        div = 1 << self.vg_pools
+        if self.vg_example_frames < 1 or self.vg_example_frames % div:
+            raise ValueError(f"vggish example_frames {self.vg_example_frames} is not divisible by 2^pools = {div}")
+        if self.vg_num_mel_bins < 1 or self.vg_num_mel_bins % div:
+            raise ValueError(f"vggish num_mel_bins {self.vg_num_mel_bins} is not divisible by 2^pools = {div}")
+        if self.vg_example_hop != self.vg_example_frames:
+            raise ValueError(f"vggish example_hop {self.vg_example_hop} is not built: only example_hop = example_frames "
+                             f"({self.vg_example_frames}), examples that do not overlap")
+        if len(self.conv_layers) != 1:
+            raise ValueError("vggish: conv_layers carries the frame geometry as one (embedding, window, shift) entry (vggish_config sets it)")
+        D, size, shift = self.conv_layers[0]
+        if size < 4 or shift < 4 or size % 4 or shift % 4 or size > 4096:
+            raise ValueError(f"vggish window / shift of {size} / {shift} samples are not built: both must be a multiple of 4 samples "
+                             "(the front end's GEMM reads 16-byte vectors)")
+        if self.vg_n_fft != 1 << max(size - 1, 1).bit_length():
+            raise ValueError(f"vggish n_fft must be the power of two at or above the window, got {self.vg_n_fft}")
+        if not 0.0 <= self.vg_mel_min_hz < self.vg_mel_max_hz <= 8000.0:
+            raise ValueError("vggish mel edges must satisfy 0 <= mel_min_hz < mel_max_hz <= 8000")
+        if not self.vg_log_offset > 0:
+            raise ValueError("vggish log_offset must be positive")
+        if len(self.vg_fc) != 3 or any(int(f) % 4 or not 4 <= int(f) <= 16384 for f in self.vg_fc):
+            raise ValueError(f"vggish needs three Linear widths that are multiples of 4, at most 16384, got {tuple(self.vg_fc)}")
+        if self.vg_postprocess and not self.vg_quant_min < self.vg_quant_max:
+            raise ValueError("vggish quantiser range must satisfy quant_min < quant_max")
+        if D != self.vg_fc[2] or self.encoder_embed_dim != self.vg_fc[2] or self.encoder_layers != 0:
+            raise ValueError("vggish: conv_dim / encoder_embed_dim must be the last Linear's width and encoder_layers 0 (vggish_config "
+                             "sets them)")
 
     def _validate_decoar(self) -> None:
         """What the HIP path builds of DeCoAR; everything else is refused by name (s3enc_create_decoar repeats it)."""
@@ -739,6 +813,37 @@ def config_from_npc(config: Dict) -> EncoderConfig:
                       paras.get("batch_norm", True), paras.get("activate", "relu"), paras.get("disable_cross_layer", False),
                       feat_dim, frame_length, frame_shift, cmvn, paras.get("vq"), paras.get("dim_bottleneck"),
                       apc_feat_type=str(feat_type))
+
+
+def vggish_config(layers=None, fc=(4096, 4096, 128), example_frames: int = 96, num_mel_bins: int = 64, postprocess: bool = True,
+                  window: int = 400, shift: int = 160, mel_min_hz: float = 125.0, mel_max_hz: float = 7500.0,
+                  log_offset: float = 0.01, example_hop: int | None = None, quant_min: float = -2.0, quant_max: float = 2.0,
+                  **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "vggish" (vggish/vggish.py:18-41,123-133, vggish_params.py).  ``layers``: (channels,
+    pool behind it) per conv layer, or the reference's ``make_layers`` list with ``"M"`` entries; default: the released shape."""
+    if layers is None:
+        layers = [64, "M", 128, "M", 256, 256, "M", 512, 512, "M"]
+    if all(v == "M" or isinstance(v, int) for v in layers):
+        if layers[0] == "M" or any(a == "M" and b == "M" for a, b in zip(layers, layers[1:])):
+            raise ValueError("vggish layers: every 'M' must follow a conv layer")
+        pairs = []
+        for v in layers:
+            if v == "M":
+                pairs[-1] = (pairs[-1][0], True)
+            else:
+                pairs.append((int(v), False))
+    else:
+        pairs = [(int(c), bool(p)) for c, p in layers]
+    fc = tuple(int(f) for f in fc)
+    size, sh = int(window), int(shift)
+    cfg = EncoderConfig(family="vggish", conv_layers=[(fc[-1], size, sh)], encoder_layers=0, encoder_embed_dim=fc[-1],
+                        vg_num_mel_bins=int(num_mel_bins), vg_n_fft=1 << max(size - 1, 1).bit_length(),
+                        vg_mel_min_hz=float(mel_min_hz), vg_mel_max_hz=float(mel_max_hz), vg_log_offset=float(log_offset),
+                        vg_example_frames=int(example_frames),
+                        vg_example_hop=int(example_frames if example_hop is None else example_hop), vg_layers=pairs, vg_fc=fc,
+                        vg_postprocess=bool(postprocess), vg_quant_min=float(quant_min), vg_quant_max=float(quant_max), **flags)
+    cfg.validate()
+    return cfg
 
 
 def decoar_config(hidden: int = 1024, num_layers: int = 4, per_layer: bool = False, feat_dim: int = 80, subsample: int = 1,

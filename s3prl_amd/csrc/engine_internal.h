@@ -9,6 +9,7 @@
 //   apc.hip / mockingjay.hip  the log-mel families (APC / VQ-APC on GRU layers; Mockingjay / TERA / AudioALBERT on BERT layers)
 //   decoar.hip  DeCoAR: the log-mel front end, a projection and two LSTM stacks on rnnb.hip's batch-shared step
 //   npc.hip     NPC: the log-mel front end, ConvBlocks and masked convolutions on convtaps.hip's two-run implicit GEMM
+//   vggish.hip  VGGish: the un-padded log-mel examples, the 3 x 3 conv + pool stack on conv2d.hip, three Linears, the quantiser
 //   (a family file holds its configuration check, its weights and its forward schedule: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
 #pragma once
@@ -428,6 +429,15 @@ struct NpcW {
     std::vector<int> has_mask;
 };
 
+// VGGish (vggish.hip): per conv layer conv2d.hip's packed image and the bias, the three Linears, the post-processor's PCA matrix and
+// means (postprocess only), and the front end's constants: the windowed DFT (2 nbin, window) and the mel matrix (nbin, bands)
+struct VggishW {
+    std::vector<DevBuf> cw, cb;
+    DevBuf fw[3], fb[3];
+    DevBuf pca, pca_mean;
+    DevBuf dft, melT;
+};
+
 // Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table, and per layer (ONE layer with
 // share_layer) q|k|v stacked as one (3 D, D) operand with q pre-scaled by head_dim^-0.5, the other projections and LayerNorm affines
 struct MjLayerW {
@@ -505,6 +515,8 @@ struct s3enc_encoder {
     s3enc_decoar_config decoar_cfg = {};  // ... and its second configuration block (s3enc_create_decoar)
     std::unique_ptr<NpcW> npc;          // S3ENC_NPC
     s3enc_npc_config npc_cfg = {};      // ... and its second configuration block (s3enc_create_npc)
+    std::unique_ptr<VggishW> vggish;    // S3ENC_VGGISH
+    s3enc_vggish_config vggish_cfg = {};  // ... and its second configuration block (s3enc_create_vggish)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -805,6 +817,12 @@ int npc_check_config(const s3enc_config& c, const s3enc_npc_config& x);
 int npc_create(s3enc_encoder* e, const Ckpt& ck);
 int npc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+// vggish.hip: the S3ENC_VGGISH family (un-padded log-mel examples + 3 x 3 conv / pool stack + Linears + quantiser; zero pad rows)
+int vggish_check_config(const s3enc_config& c, const s3enc_vggish_config& x);
+int vggish_create(s3enc_encoder* e, const Ckpt& ck);
+long vggish_num_examples(const s3enc_vggish_config& x, long n_samples);  // E of an n-sample utterance, 0 when it holds no example
+int vggish_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 // mockingjay.hip: the S3ENC_MOCKINGJAY family (spectrogram front end + input representation + post-LN BERT layers, chunked)
 int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x);
 int mj_create(s3enc_encoder* e, const Ckpt& ck);

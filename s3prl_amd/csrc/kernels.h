@@ -224,6 +224,27 @@ struct ConvTapsParams {
 void pack_conv_taps(const float* w, int N, int C, int k, int mask, bool dense, std::vector<float>& out);
 const char* conv_taps_refusal(const ConvTapsParams& p);  // null, or why launch_conv_taps would refuse
 hipError_t launch_conv_taps(const ConvTapsParams& p, hipStream_t stream);
+// conv2d.hip: exact-fp32 stride-1 3 x 3 Conv2d(C, N, padding = 1) on channel-last images + bias + ReLU + optional 2 x 2 / stride-2
+// max-pool in one pass (VGGish's features stack).  Example b's operand is an (H + 2) x (W + 2) x C image with a zero border; the
+// result goes to the interior of a (Ho + 2 dst_pad) x (Wo + 2 dst_pad) image of pixel pitch ld_dst (Ho, Wo = H, W, halved under
+// pool), whose border is never touched.  C = 1 runs the VALU first-layer kernel, any other C (a multiple of 16) the MFMA kernel.
+struct Conv2dParams {
+    const float* src;    // example b at src + b * src_bs; bordered pixel (r, c) at + (r * (W + 2) + c) * C
+    long src_bs;
+    int C;               // input channels: 1, or a multiple of 16
+    const float* Wt;     // pack_conv2d3x3: (N, 9 C) with k = (ky * 3 + kx) * C + c; C = 1: (9, N)
+    const float* bias;   // [N] or null
+    int H, W, N, B;
+    int act;             // 0 none, 1 ReLU
+    int pool;            // 1: 2 x 2 / stride-2 max-pool behind the activation (H, W even)
+    float* dst;          // example b at dst + b * dst_bs; output pixel (y, x) at + ((y + dst_pad) * (Wo + 2 dst_pad) + x + dst_pad) * ld_dst
+    long dst_bs;
+    int dst_pad;
+    long ld_dst;
+};
+void pack_conv2d3x3(const float* w, int N, int C, std::vector<float>& out);  // host: nn.Conv2d's (N, C, 3, 3) -> the kernel's image
+const char* conv2d3x3_refusal(const Conv2dParams& p);  // null, or why launch_conv2d3x3 would refuse
+hipError_t launch_conv2d3x3(const Conv2dParams& p, hipStream_t stream);
 
 // ---- frontend.hip ---------------------------------------------------------------------------------------
 // Waveform table: wav b is `ptrs[b]` with `lens[b]` valid samples; reads beyond are zeros (the padding).

@@ -501,6 +501,42 @@ int s3enc_op_conv_taps(const float* x, const float* w_host, const float* bias, i
     return 0;
 }
 
+int s3enc_op_conv2d3x3(const float* x, const float* w_host, const float* bias, int32_t B, int32_t H, int32_t W, int32_t C, int32_t N,
+                       int32_t act, int32_t pool, float* dst, int32_t dst_pad, int64_t ldo, void* stream) {
+    if (!x || !w_host || !dst) return fail("s3enc_op_conv2d3x3: null argument");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0) return fail("s3enc_op_conv2d3x3: bad shape");
+    if (H > 32768 || W > 32768 || B > (1 << 24)) return fail("s3enc_op_conv2d3x3: bad shape");
+    Conv2dParams p{};
+    p.src = x;
+    p.src_bs = (long)(H + 2) * (W + 2) * C;
+    p.C = C;
+    p.bias = bias;
+    p.H = H;
+    p.W = W;
+    p.N = N;
+    p.B = B;
+    p.act = act;
+    p.pool = pool;
+    p.dst = dst;
+    p.dst_pad = dst_pad;
+    p.ld_dst = ldo;
+    {
+        const long Ho = pool == 1 ? H / 2 : H, Wo = pool == 1 ? W / 2 : W;
+        p.dst_bs = (Ho + 2 * (long)dst_pad) * (Wo + 2 * (long)dst_pad) * ldo;
+    }
+    alignas(16) static float stand_in[4];  // the checks that need no device memory first
+    p.Wt = stand_in;
+    if (const char* why = conv2d3x3_refusal(p)) return fail(std::string("s3enc_op_conv2d3x3: ") + why);
+    std::vector<float> packed;
+    pack_conv2d3x3(w_host, N, C, packed);
+    DevBuf dw;
+    HIP_TRY(upload_f32(dw, packed));
+    p.Wt = (const float*)dw.p;
+    HIP_TRY(launch_conv2d3x3(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
+    return 0;
+}
+
 int s3enc_op_argmax_gather(const float* scores, const float* table, int32_t shared, int64_t rows, int32_t G, int32_t V, int32_t Dv,
                            int64_t* ids, float* out, void* stream) {
     if (!scores || (!ids && !out) || (out && !table)) return fail("s3enc_op_argmax_gather: null argument");

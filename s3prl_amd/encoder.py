@@ -40,6 +40,8 @@ class HipEncoder:
             raise ValueError(f"DeCoAR is built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "npc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             raise ValueError(f"NPC is built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "vggish" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"VGGish is built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -83,6 +85,9 @@ class HipEncoder:
             elif cfg.family == "npc":  # its front end and convolution stack travel beside the (unchanged) s3enc_config
                 npc = _lib.make_npc_config(cfg)
                 rc = self._lib.s3enc_create_npc(C.byref(ccfg), C.byref(npc), tensors, len(weights), self.device, C.byref(h))
+            elif cfg.family == "vggish":  # its front end and layer list travel beside the (unchanged) s3enc_config
+                vg = _lib.make_vggish_config(cfg)
+                rc = self._lib.s3enc_create_vggish(C.byref(ccfg), C.byref(vg), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")
@@ -194,6 +199,11 @@ class HipEncoder:
         if self.cfg.family == "npc" and min(self.num_frames(n) for n in lengths) < 1:
             raise ValueError(f"an utterance of {min(lengths)} samples is shorter than one analysis window of the NPC front end "
                              f"({self.cfg.conv_layers[0][1]} samples)")
+        if self.cfg.family == "vggish":
+            for i, n in enumerate(lengths):
+                if self.num_frames(n) < 1:
+                    raise ValueError(f"utterance {i} has {n} samples, fewer than one VGGish example of {self.cfg.vg_min_samples} "
+                                     f"samples ({self.cfg.vg_example_frames} frames; the reference raises on it)")
         if self.cfg.family == "decoar":
             if B > 128:
                 raise ValueError(f"a DeCoAR batch holds at most 128 utterances (the batch-shared recurrent kernel's limit), got {B}")

@@ -32,6 +32,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _decoar_shapes(cfg)
     if cfg.family == "npc":
         return _npc_shapes(cfg)
+    if cfg.family == "vggish":
+        return _vggish_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -228,6 +230,29 @@ def _npc_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     return s
 
 
+def _vggish_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """VGGish (upstream/vggish/vggish.py:18-41,123-133), the names of the reference's two state dicts: ``features.K`` with K the
+    conv's index in its ``nn.Sequential``, ``embeddings.{0,2,4}``, and — with the post-processor — ``pca_eigen_vectors`` and
+    ``pca_means`` (held here as ``(D,)``; the reference reshapes whatever it is given to ``(D, 1)``)."""
+    s: Dict[str, tuple] = {}
+    cin, H, W = 1, cfg.vg_example_frames, cfg.vg_num_mel_bins
+    for i, (ch, pool) in enumerate(cfg.vg_layers):
+        s[f"features.{cfg.vg_seq_index(i)}.weight"] = (ch, cin, 3, 3)
+        s[f"features.{cfg.vg_seq_index(i)}.bias"] = (ch,)
+        cin = ch
+        if pool:
+            H, W = H // 2, W // 2
+    k = H * W * cin
+    for i, f in zip((0, 2, 4), cfg.vg_fc):
+        s[f"embeddings.{i}.weight"] = (f, k)
+        s[f"embeddings.{i}.bias"] = (f,)
+        k = f
+    if cfg.vg_postprocess:
+        s["pca_eigen_vectors"] = (k, k)
+        s["pca_means"] = (k,)
+    return s
+
+
 def _decoar_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     """Decoar (upstream/decoar/decoar.py:21-39), the checkpoint's names: the projection and the two multi-layer nn.LSTM modules
     (decoar_layers/expert.py:35-47 renames them to its per-layer modules; both experts read this one file)."""
@@ -379,6 +404,10 @@ def scale_outlier_writers(cfg: EncoderConfig, weights: Dict[str, np.ndarray], se
     return out
 
 
+VGGISH_PCA_SCALE = 0.25  # x (embedding - mean): see _synthetic
+VGGISH_EMB_MEAN = 1.0
+
+
 def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
     rng = np.random.default_rng(seed)
     out: Dict[str, np.ndarray] = {}
@@ -431,6 +460,19 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
         elif name.startswith("blocks.") and ".bn" in name:  # non-trivial eval statistics: the BatchNorm fold is exercised
             w = {"weight": lambda: 1.0 + 0.1 * rng.standard_normal(shape), "bias": lambda: -0.1 + 0.05 * rng.standard_normal(shape),
                  "running_mean": lambda: 0.2 * rng.standard_normal(shape), "running_var": lambda: rng.uniform(0.5, 2.0, size=shape)}[leaf]()
+        elif cfg.family == "vggish" and leaf == "weight":
+            # He scaling, sqrt(2 / fan_in), through every conv and Linear: ReLU then keeps the second moment of the log-mel input
+            # (RMS 3-4 for unit-variance PCM) up to the embedding, about half of whose elements are exact zeros
+            w = rng.standard_normal(shape) * np.sqrt(2.0 / int(np.prod(shape[1:])))
+        elif name == "pca_eigen_vectors":
+            # an orthogonal matrix times a fixed scale: every output mixes all embedding dimensions with unit-norm rows, and the
+            # scale puts the output's spread (VGGISH_PCA_SCALE x the embedding's) at about a third of the quantiser's half range
+            q, r = np.linalg.qr(rng.standard_normal(shape))
+            w = VGGISH_PCA_SCALE * q * np.sign(np.diag(r))
+        elif name == "pca_means":
+            # near the embedding's mean (about VGGISH_EMB_MEAN per element under the rule above), so that the quantiser's input is
+            # centred in its range
+            w = VGGISH_EMB_MEAN * (1.0 + 0.1 * rng.standard_normal(shape))
         elif name in ("vector_quantizer.embedding", "vector_quantizer.vars"):
             # codebooks at the scale of what they are compared with / replace (a trained k-means embedding lives where the
             # normalised projection does: unit variance; the reference's 0.01 * randn init leaves argmin decisions at rounding level)
@@ -639,6 +681,22 @@ def named_config(name: str) -> EncoderConfig:
         from .config import npc_config
 
         return npc_config(**npc[name])
+    # VGGish: un-padded log-mel examples, a 3 x 3 conv + pool stack, three Linears, the PCA / 8-bit quantiser
+    vggish = {
+        "vggish": dict(),  # the released shape: 96 x 64 examples, [64, M, 128, M, 256, 256, M, 512, 512, M], 4096 / 4096 / 128
+        "vggish_raw": dict(postprocess=False),
+        "tiny_vggish": dict(layers=[16, "M", 32, "M", 32, 32, "M", 64, 64, "M"], fc=(128, 128, 32), example_frames=16, num_mel_bins=16),
+        "tiny_vggish_raw": dict(layers=[16, "M", 32, "M", 32, 32, "M", 64, 64, "M"], fc=(128, 128, 32), example_frames=16,
+                                num_mel_bins=16, postprocess=False),
+        # channel counts that are no multiple of 64, a 3 x 1 last map
+        "tiny_vggish_odd": dict(layers=[16, "M", 48, "M", 48, "M"], fc=(128, 128, 32), example_frames=24, num_mel_bins=8),
+        "tiny_vggish_odd_raw": dict(layers=[16, "M", 48, "M", 48, "M"], fc=(128, 128, 32), example_frames=24, num_mel_bins=8,
+                                    postprocess=False),
+    }
+    if name in vggish:
+        from .config import vggish_config
+
+        return vggish_config(**vggish[name])
     # Mockingjay / TERA / AudioALBERT: a log-mel (or kaldi fbank) front end into post-LN BERT layers, long inputs in chunks
     tiny_mj = dict(hidden=128, layers=2, heads=2, intermediate=256, input_dim=16, sequence_length=0)
     mj = {
@@ -661,7 +719,7 @@ def named_config(name: str) -> EncoderConfig:
 
         return mockingjay_config(**mj[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(mj))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(mj))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
