@@ -78,7 +78,15 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * over every example, three Linear + ReLU layers and — with postprocess — the PCA / clamp / 8-bit quantiser.  One state of
         * (B, E_max, fc[2]): an utterance's examples, exact zeros behind them (pad_sequence).  compute_dtype S3ENC_F32 only; built by
         * s3enc_create_vggish. */
-       S3ENC_VGGISH = 11 };
+       S3ENC_VGGISH = 11,
+       /* BYOL-A (upstream/byol_a/{expert,byol_a}.py): every utterance zero-padded and cut into segments of `window` samples every
+        * `stride` samples; per segment a centred 1024-point hann STFT (the segment reflect-padded about its own ends), |X|^2, 64 HTK
+        * mel triangles, (log(. + FLT_EPSILON) - mean) / std; three Conv2d(3 x 3) + BatchNorm2d (eval) + ReLU + MaxPool2d(2, 2) (floor)
+        * layers, Linear + ReLU + Linear + ReLU per pooled time step, max + mean over time.  One state of (B, S, feature_d), S =
+        * ceil(n_max / stride).  NOTHING is masked: the rows behind an utterance's own segments are the network's response to the
+        * zero padding, the reference's values and not zeros (NPC's convention).  compute_dtype S3ENC_F32 only; built by
+        * s3enc_create_byol_a. */
+       S3ENC_BYOL_A = 12 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -363,6 +371,27 @@ typedef struct s3enc_vggish_config {
     float quant_max;                                /* +2 */
 } s3enc_vggish_config;
 
+/* S3ENC_BYOL_A only (byol_a/expert.py:27-125, byol_a.py:36-137, config.yaml): the second configuration block of
+ * s3enc_create_byol_a.  s3enc_config carries the segment geometry: n_conv = 1, conv_kernel[0] / conv_stride[0] = window / stride in
+ * samples, conv_dim = embed_dim = feature_d, encoder_layers = 0 (one state).  The caller computes window = int(window_secs * 16000)
+ * and stride = int(stride_secs * 16000) exactly as the reference does.  Segments: starts = range(0, n_max, stride); every utterance
+ * zero-padded to starts[-1] + window; segment (b, s) = padded[b][starts[s] : starts[s] + window].  Front end per segment, fixed:
+ * n_fft = win_length = 1024, hop 160, center = True with reflect padding about the segment's own ends, periodic hann, power 2,
+ * 1 + window / 160 frames; 64 HTK mel triangles between 60 and 7800 Hz over linspace(0, 8000, 513), norm = None; (log(mel +
+ * FLT_EPSILON) - norm_mean) / norm_std.  Checkpoint tensors, reference state_dict names after the prefix rule of byol_a.py:66-74:
+ * features.{0,4,8}.{weight,bias} (Conv2d(., 64, 3)), features.{1,5,9}.{weight,bias,running_mean,running_var} (BatchNorm2d),
+ * fc.0.{weight,bias} (feature_d, 512), fc.3.{weight,bias} (feature_d, feature_d).  s3enc_create_byol_a refuses by name: every
+ * compute dtype but fp32, a window of at most 512 samples (the reflection is undefined), a window below 1120 samples (fewer than 8
+ * frames: nothing survives three pools), a feature_d that is not a multiple of 4. */
+typedef struct s3enc_byol_a_config {
+    int32_t feature_d;                              /* 512 / 1024 / 2048 */
+    int32_t window;                                 /* samples per segment: 16000 */
+    int32_t stride;                                 /* samples between two segment starts: 16000 */
+    float norm_mean;                                /* -5.4919195 */
+    float norm_std;                                 /* 5.0389895 */
+    float bn_eps;                                   /* 1e-5 */
+} s3enc_byol_a_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -436,6 +465,13 @@ int s3enc_create_npc(const s3enc_config* cfg, const s3enc_npc_config* npc, const
  * s3enc_downsample_rate is 16000 (expert.py:21-22, although the examples are 15360 samples apart); s3enc_num_states is 1 for
  * S3ENC_SEL_HIDDEN (the other selections are refused), out_dtype must be S3ENC_F32. */
 int s3enc_create_vggish(const s3enc_config* cfg, const s3enc_vggish_config* vggish, const s3enc_tensor* tensors, int32_t n_tensors,
+                        int32_t device, s3enc_handle* out);
+/* The S3ENC_BYOL_A family: s3enc_config beside its own block (the other create entries refuse the family by name).  Replaces
+ * UpstreamExpert.__init__ of upstream/byol_a/expert.py.  On the handle: s3enc_num_frames(n) is the number of segments S =
+ * ceil(n / stride); s3enc_valid_frames is the utterance's own S — the rows behind it are NOT zeros but the reference's values for
+ * the zero-padded segments; s3enc_downsample_rate is stride; s3enc_num_states is 1 for S3ENC_SEL_HIDDEN (the other selections are
+ * refused), out_dtype must be S3ENC_F32.  A row (b, s) depends on segment (b, s)'s own `window` samples and on nothing else. */
+int s3enc_create_byol_a(const s3enc_config* cfg, const s3enc_byol_a_config* byol_a, const s3enc_tensor* tensors, int32_t n_tensors,
                         int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
@@ -670,6 +706,13 @@ int s3enc_debug_gemm_schedule(int32_t M, int32_t N, int32_t batches, int32_t tm,
  *                   masked taps are neither fetched nor multiplied), 0 = the same kernel over all kernel_size taps on weights whose
  *                   masked taps are stored as zeros — equal values; measured 6.13 against 10.55 ms per 32 x 10 s npc_360hr forward
  *                   (profiles/npc_360hr_fp32.md);
+ *   "melspec_fft":  S3ENC_BYOL_A handles and s3enc_op_melspec1024: 1 (default) = the 1024-point STFT as a real FFT in LDS, one
+ *                   workgroup per frame (melspec.hip), 0 = the overlapping-row GEMM against the folded hann x DFT matrix — the
+ *                   yardstick and the fallback; results differ in the last bits; measured 1.04 against 1.75 ms per 32 x 10 s
+ *                   byol_a_2048 forward (profiles/byol_a_fp32.md);
+ *   "conv2d_n64":   S3ENC_BYOL_A handles and s3enc_op_conv2d3x3_affine: 1 (default) = Cout <= 64 runs on the 64-wide n-tile of
+ *                   conv2d.hip, 0 = on the 128-wide one, half of whose MFMA columns are then padding — the same bits; measured 1.04
+ *                   against 1.28 ms per forward (profiles/byol_a_fp32.md);
  *   "conv_f22":     S3ENC_F32: 1 (default) = conv layers 1.. with kernel 3 and stride 2 (conv1-4 of every extractor) run in the
  *                   two-output form (convf22.hip: 5 block products per pair of outputs instead of 6, fp32 operands and accumulation,
  *                   a different association — results differ in the last bits), 0 = the implicit GEMM;
@@ -816,6 +859,25 @@ int s3enc_op_conv_taps(const float* x, const float* w_host, const float* bias, i
  * max over the un-pooled output.  Synchronises. */
 int s3enc_op_conv2d3x3(const float* x, const float* w_host, const float* bias, int32_t B, int32_t H, int32_t W, int32_t C, int32_t N,
                        int32_t act, int32_t pool, float* dst, int32_t dst_pad, int64_t ldo, void* stream);
+
+/* s3enc_op_conv2d3x3 with BYOL-A's additions (conv2d.hip); what the two entries share is described above.
+ *   scale / shift: device fp32 [N] or both null.  With them v = act(acc * scale[n] + shift[n]) — an eval-mode BatchNorm behind the
+ *   conv, scale = gamma / sqrt(var + eps), shift = (conv_bias - mean) * scale + beta — and `bias` must be null.  Null scale is the
+ *   acc + bias path, bit for bit s3enc_op_conv2d3x3's.
+ *   pool_floor = 1 (needs pool = 1): odd H / W are allowed, Ho = H / 2 and Wo = W / 2 rounded down as nn.MaxPool2d(2, 2) does; the
+ *   dropped last row / column is never computed.  H, W >= 2.
+ *   Cout <= 64 runs on a 64-wide n-tile (tuning key conv2d_n64 = 0: on the 128-wide one); an output's bits do not depend on it. */
+int s3enc_op_conv2d3x3_affine(const float* x, const float* w_host, const float* bias, const float* scale, const float* shift, int32_t B,
+                              int32_t H, int32_t W, int32_t C, int32_t N, int32_t act, int32_t pool, int32_t pool_floor, float* dst,
+                              int32_t dst_pad, int64_t ldo, void* stream);
+
+/* BYOL-A's front end on a table of segments (melspec.hip): segments: device fp32 (nseg, L) contiguous.  Every segment is
+ * reflect-padded by 512 about its own ends; 1 + L / 160 frames of a 1024-point periodic-hann STFT; |X|^2 over 513 bins; 64 HTK mel
+ * triangles 60..7800 Hz; out (nseg, frames, 64) = (log(mel + FLT_EPSILON) - (-5.4919195)) / 5.0389895.  power: null, or device fp32
+ * (nseg, frames, 513) that receives |X|^2.  Tuning key melspec_fft: 1 = a real FFT in LDS, one workgroup per frame (a frame's bits
+ * depend on its 1024 samples only), 0 = the overlapping-row GEMM against the folded hann x DFT matrix.  Refused by message: L <= 512
+ * (the reflection is undefined), L < 1120 (fewer than 8 frames).  Synchronises. */
+int s3enc_op_melspec1024(const float* segments, int32_t nseg, int32_t L, float* out, float* power, void* stream);
 
 /* A forward and a backward unidirectional nn.LSTM on packed sequences, side by side, on the batch-shared kernel: one launch per
  * time step for both directions, W_hh read once per step for the whole batch (fp32 MFMA).  pre_fwd / pre_bwd: device fp32, row

@@ -19,7 +19,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -119,6 +119,12 @@ class S3VggishConfig(C.Structure):
     ]
 
 
+class S3ByolAConfig(C.Structure):
+    """s3enc_byol_a_config: the segment block of a BYOL-A handle (s3enc_create_byol_a)."""
+    _fields_ = [("feature_d", C.c_int32), ("window", C.c_int32), ("stride", C.c_int32), ("norm_mean", C.c_float),
+                ("norm_std", C.c_float), ("bn_eps", C.c_float)]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -153,6 +159,7 @@ _PROTOS = {
     "s3enc_create_decoar": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3DecoarConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_npc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3NpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_vggish": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3VggishConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    "s3enc_create_byol_a": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3ByolAConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -204,6 +211,8 @@ _PROTOS = {
     "s3enc_op_conv_taps": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _I64, _VP, _VP,
                                      _I32, _I32, _VP]),
     "s3enc_op_conv2d3x3": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
+    "s3enc_op_conv2d3x3_affine": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
+    "s3enc_op_melspec1024": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
@@ -434,4 +443,14 @@ def make_vggish_config(cfg) -> S3VggishConfig:
         c.fc[i] = int(f)
     c.postprocess = int(cfg.vg_postprocess)
     c.quant_min, c.quant_max = float(cfg.vg_quant_min), float(cfg.vg_quant_max)
+    return c
+
+
+def make_byol_a_config(cfg) -> S3ByolAConfig:
+    """The second configuration block of a ``family="byol_a"`` EncoderConfig (``s3enc_create_byol_a``)."""
+    if cfg.family != "byol_a":
+        raise S3EncError("make_byol_a_config needs a byol_a configuration")
+    c = S3ByolAConfig()
+    c.feature_d, c.window, c.stride = (int(v) for v in cfg.conv_layers[0])
+    c.norm_mean, c.norm_std, c.bn_eps = float(cfg.ba_norm_mean), float(cfg.ba_norm_std), float(cfg.ba_bn_eps)
     return c

@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, byol_a_config, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -161,6 +161,45 @@ def load_vggish_checkpoint(ckpt, postprocess: bool = True) -> Tuple[EncoderConfi
     return cfg, _hot_path_weights(what, cfg, merged)
 
 
+def byol_a_state_dict(state) -> Dict:
+    """``NetworkCommonMixIn.load_weight`` (upstream/byol_a/byol_a.py:58-80): a plain state dict, or one under ``"state_dict"``;
+    every key is cut at its first ``fc.`` / ``features.`` component (whatever prefix a training wrapper put in front of it), keys
+    without one are dropped."""
+    import re
+
+    if "state_dict" in state:
+        state = state["state_dict"]
+    out = {}
+    for k in state:
+        m = re.search(r"(^fc\.|\.fc\.|^features\.|\.features\.)", k)
+        if m is None:
+            continue
+        new_k = k[m.start():]
+        out[new_k[1:] if new_k[0] == "." else new_k] = state[k]
+    return out
+
+
+def load_byol_a_checkpoint(ckpt, feature_d: int = None, window_secs: float = 1.0, stride_secs: float = 1.0
+                           ) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """An ``AudioNTT2020`` weight file (upstream/byol_a/hubconf.py:18-42) or the dict it holds.  The file carries no configuration:
+    ``feature_d`` is read off ``fc.0.weight`` and, when the caller names one (the hub entries do), checked against it.  The
+    BatchNorm2d layers bring ``running_mean`` / ``running_var`` (eps 1e-5, the module's default); ``num_batches_tracked`` is
+    training state and is ignored.  The reference loads strictly: every tensor is required."""
+    what = ckpt if isinstance(ckpt, str) else "the BYOL-A checkpoint"
+    if not isinstance(ckpt, dict):
+        import torch
+
+        ckpt = torch.load(ckpt, map_location="cpu", weights_only=False)
+    sd = byol_a_state_dict(ckpt)
+    if "fc.0.weight" not in sd:
+        raise ValueError(f"{what}: missing parameter fc.0.weight")
+    d = int(sd["fc.0.weight"].shape[0])
+    if feature_d is not None and int(feature_d) != d:
+        raise ValueError(f"{what}: feature_d {int(feature_d)} was asked for, but fc.0.weight has {d} rows")
+    cfg = byol_a_config(feature_d=d, window_secs=window_secs, stride_secs=stride_secs)
+    return cfg, _hot_path_weights(what, cfg, sd)
+
+
 def load_decoar_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
     """``{"model": state_dict}`` (upstream/decoar/expert.py:30-36; decoar_layers/expert.py:30-47 reads the same file and renames
     ``{forward,backward}_lstm.X_lN`` to its per-layer modules).  The file carries no configuration — the reference's ``Decoar()``
@@ -275,6 +314,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_npc_checkpoint(ckpt)
     if family == "vggish":
         return load_vggish_checkpoint(ckpt)
+    if family == "byol_a":
+        return load_byol_a_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -328,6 +369,9 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
         return
     if cfg.family == "decoar":  # upstream/decoar/expert.py:30-36
         torch.save({"model": sd}, path)
+        return
+    if cfg.family == "byol_a":  # upstream/byol_a/byol_a.py:58-80: a plain state dict
+        torch.save(sd, path)
         return
     if cfg.family == "vggish":  # upstream/vggish/hubconf.py:22-31: the two state dicts in one file
         # "config" is this package's addition (the reference reads "vggish" and "pca" only): a shape other than the released one

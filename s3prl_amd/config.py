@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -206,6 +206,15 @@ class EncoderConfig:
     vg_quant_min: float = -2.0        # QUANTIZE_MIN_VAL
     vg_quant_max: float = 2.0         # QUANTIZE_MAX_VAL
 
+    # BYOL-A (family "byol_a", upstream/byol_a/{expert,byol_a}.py, config.yaml): segments of ``window`` samples every ``stride``
+    # samples, each through a 1024-point log-mel front end, three conv + BatchNorm + ReLU + floor-pool layers, two Linears and
+    # max + mean over time.  ``conv_layers`` = [(feature_d, window, stride)] in samples; ``encoder_layers`` = 0: one state
+    ba_window_secs: float = 1.0       # the expert's constructor arguments as given; the samples are int(secs * 16000)
+    ba_stride_secs: float = 1.0
+    ba_norm_mean: float = -5.4919195  # expert.py:56-60: PrecomputedNorm's statistics
+    ba_norm_std: float = 5.0389895
+    ba_bn_eps: float = 1e-5           # nn.BatchNorm2d's default
+
     # ---- derived -------------------------------------------------------------------------
     @property
     def conv_dim(self) -> int:
@@ -250,6 +259,8 @@ class EncoderConfig:
             return 1 + n // 160 if n > 200 else 0
         if self.family == "decoar":  # ceil(fbank frames / subsample)
             return -(-self.conv_lengths(n)[-1] // self.decoar_subsample)
+        if self.family == "byol_a":  # segments: len(range(0, n, stride)) (byol_a/expert.py:85)
+            return -(-n // self.conv_layers[0][2]) if n > 0 else 0
         if self.family == "vggish":  # examples: complete groups of vg_example_frames un-padded frames (audio.py:90-111)
             F = self.conv_lengths(n)[-1]
             return 1 + (F - self.vg_example_frames) // self.vg_example_hop if F >= self.vg_example_frames else 0
@@ -271,7 +282,7 @@ class EncoderConfig:
             return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
         if self.family == "mockingjay":
             return min(T, max(self.num_frames(length), 0))
-        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "npc", "vggish"):  # vggish: the utterance's own examples, exact zeros behind them; distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
+        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "npc", "vggish", "byol_a"):  # byol_a: the utterance's own segments (the rows behind them are the reference's values, not zeros); vggish: the utterance's own examples, exact zeros behind them; distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -382,6 +393,8 @@ class EncoderConfig:
             return self._validate_npc()
         if self.family == "vggish":
             return self._validate_vggish()
+        if self.family == "byol_a":
+            return self._validate_byol_a()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -579,6 +592,28 @@ class EncoderConfig:
         if D != self.vg_fc[2] or self.encoder_embed_dim != self.vg_fc[2] or self.encoder_layers != 0:
             raise ValueError("vggish: conv_dim / encoder_embed_dim must be the last Linear's width and encoder_layers 0 (vggish_config "
                              "sets them)")
+
+    def _validate_byol_a(self) -> None:
+        """What the HIP path builds of BYOL-A; everything else is refused by name (s3enc_create_byol_a repeats it)."""
+        if len(self.conv_layers) != 1:
+            raise ValueError("byol_a: conv_layers carries the segment geometry as one (feature_d, window, stride) entry (byol_a_config sets it)")
+        d, window, stride = self.conv_layers[0]
+        if d % 4 or not 4 <= d <= 16384:
+            raise ValueError(f"byol_a feature_d must be a multiple of 4, at most 16384, got {d}")
+        if window <= 512:
+            raise ValueError(f"byol_a window of {window} samples is too short: a segment of at most 512 samples cannot be reflect-padded "
+                             "by 512 (n_fft / 2)")
+        if window < 1120:
+            raise ValueError(f"byol_a window of {window} samples is too short: fewer than 8 frames (1120 samples), nothing survives "
+                             "three 2 x 2 pools")
+        if stride < 1:
+            raise ValueError(f"byol_a stride must be at least one sample, got {stride}")
+        if (window, stride) != (int(self.ba_window_secs * 16000), int(self.ba_stride_secs * 16000)):
+            raise ValueError("byol_a: conv_layers does not match window_secs / stride_secs (byol_a_config sets it)")
+        if not self.ba_norm_std > 0 or not self.ba_bn_eps > 0:
+            raise ValueError("byol_a norm_std and bn_eps must be positive")
+        if self.encoder_embed_dim != d or self.encoder_layers != 0:
+            raise ValueError("byol_a: encoder_embed_dim must be feature_d and encoder_layers 0 (byol_a_config sets them)")
 
     def _validate_decoar(self) -> None:
         """What the HIP path builds of DeCoAR; everything else is refused by name (s3enc_create_decoar repeats it)."""
@@ -842,6 +877,16 @@ def vggish_config(layers=None, fc=(4096, 4096, 128), example_frames: int = 96, n
                         vg_example_frames=int(example_frames),
                         vg_example_hop=int(example_frames if example_hop is None else example_hop), vg_layers=pairs, vg_fc=fc,
                         vg_postprocess=bool(postprocess), vg_quant_min=float(quant_min), vg_quant_max=float(quant_max), **flags)
+    cfg.validate()
+    return cfg
+
+
+def byol_a_config(feature_d: int = 2048, window_secs: float = 1.0, stride_secs: float = 1.0, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "byol_a" (byol_a/expert.py:27-65).  The two ``int(secs * 16000)`` are the reference's own
+    expressions: the samples, not the seconds, travel through the ABI."""
+    window, stride = int(window_secs * 16000), int(stride_secs * 16000)
+    cfg = EncoderConfig(family="byol_a", conv_layers=[(int(feature_d), window, stride)], encoder_layers=0,
+                        encoder_embed_dim=int(feature_d), ba_window_secs=float(window_secs), ba_stride_secs=float(stride_secs), **flags)
     cfg.validate()
     return cfg
 

@@ -24,6 +24,12 @@
 // Epilogue, one pass, plain vector stores into the INTERIOR of the next layer's bordered buffer (border width dst_pad, pixel pitch
 // ld_dst; dst_pad = 0 gives a plain contiguous (B, H', W', N) tensor — VGGish's flatten order, the first Linear's A operand).
 //
+// BYOL-A's additions (upstream/byol_a/byol_a.py:95-107), as template parameters of separate instantiations — the ones above are
+// VGGish's as they were.  EXT: the epilogue is act(acc * scale[n] + shift[n]), an eval-mode BatchNorm2d behind the conv (the host
+// folds the conv bias into the shift; (1, bias) is bit for bit acc + bias), and under pool_floor an example's M extent is 4 (H / 2)
+// (W / 2): odd maps pool as nn.MaxPool2d(2, 2) does and the dropped last row / column is never enumerated, while the operand's row
+// pitch and the kernel-row jump keep the true W.  WN = 1: a 64-wide n-tile for Cout <= 64 with all four waves along M.
+//
 // conv2d3x3_first_kernel is the C = 1 layer (K = 9 is not matrix work): a VALU kernel, one thread per (pixel or window, 4 output
 // channels), an fmaf chain over the nine taps in the same order, the same epilogue.
 #include "kernels.h"
@@ -32,7 +38,7 @@ namespace s3 {
 
 namespace {
 
-constexpr int BN = 128, ROWB = 64;
+constexpr int ROWB = 64;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void mma4(const uint4& a, const uint4& b, f32x16& c) {  // k order x, y, z, w (gemm_kernel<float>'s)
@@ -50,6 +56,30 @@ __device__ __forceinline__ float pmax(float a, float b) { return (a > b || a != 
 __device__ __forceinline__ float4 act4(float4 v, const float4& b, int act) {
     v.x = act1(v.x + b.x, act); v.y = act1(v.y + b.y, act); v.z = act1(v.z + b.z, act); v.w = act1(v.w + b.w, act);
     return v;
+}
+// the affine epilogue: act(acc * s + t), one fma per element; s = 1, t = bias is bit for bit act4's acc + bias
+__device__ __forceinline__ float4 aff4(float4 v, const float4& s, const float4& t, int act) {
+    v.x = act1(fmaf(v.x, s.x, t.x), act); v.y = act1(fmaf(v.y, s.y, t.y), act); v.z = act1(fmaf(v.z, s.z, t.z), act);
+    v.w = act1(fmaf(v.w, s.w, t.w), act);
+    return v;
+}
+template <bool EXT>
+__device__ __forceinline__ float4 ep4(const float4& v, const float4& s, const float4& t, int act) {
+    if constexpr (EXT) return aff4(v, s, t, act);
+    else return act4(v, t, act);
+}
+// the per-channel pair of the epilogue: (scale, shift), or (1, bias) / (1, 0) without an affine
+template <bool EXT>
+__device__ __forceinline__ void load_ep(const Conv2dParams& p, int n, bool ok, float4& s4, float4& t4) {
+    s4 = make_float4(1.f, 1.f, 1.f, 1.f);
+    t4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!ok) return;
+    if (EXT && p.scale) {
+        s4 = *(const float4*)(p.scale + n);
+        t4 = *(const float4*)(p.shift + n);
+    } else if (p.bias) {
+        t4 = *(const float4*)(p.bias + n);
+    }
 }
 __device__ __forceinline__ float4 pmax4(const float4& a, const float4& b) {
     return make_float4(pmax(a.x, b.x), pmax(a.y, b.y), pmax(a.z, b.z), pmax(a.w, b.w));
@@ -70,9 +100,12 @@ __device__ __forceinline__ void pixel_of(int m, int HW, int W, int pool, int& b,
     }
 }
 
-template <int TM>
+// WN = waves along N: 2 is the (64 TM) x 128 tile, 1 the (128 TM) x 64 tile for Cout <= 64 (all four waves along M; a wave's block,
+// fragments and K order are the same, so the bits are too).  EXT = the affine epilogue and floor pooling (an example's M extent is
+// 4 (H / 2) (W / 2): the dropped last row / column is never enumerated); EXT = false is VGGish's kernel as it was.
+template <int TM, int WN, bool EXT>
 __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
-    constexpr int BM = 64 * TM;
+    constexpr int BM = (4 / WN) * 32 * TM, BN = 64 * WN;
     constexpr int PLANE = (BM + BN) * ROWB;
     constexpr int NPASS = (BM + BN) / 64;
     constexpr int APASS = BM / 64;
@@ -80,11 +113,11 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
+    const int wr = WN == 2 ? wave >> 1 : wave, wc = WN == 2 ? wave & 1 : 0;
     const int half = lane >> 5;
     const int l31 = lane & 31;
 
-    const int HW = p.H * p.W;
+    const int HW = EXT && p.pool ? 4 * (p.H >> 1) * (p.W >> 1) : p.H * p.W;
     const int M = p.B * HW;
     const int n_tiles = (p.N + BN - 1) / BN;
     int tile;
@@ -208,8 +241,8 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
     const int c4 = (lane & 15) * 4;
     const int n = n0 + wc * 64 + c4;
     const bool n_ok = n < p.N;
-    float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.bias && n_ok) bias4 = *(const float4*)(p.bias + n);
+    float4 scale4, bias4;
+    load_ep<EXT>(p, n, n_ok, scale4, bias4);
     const int pad = p.dst_pad;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -226,9 +259,9 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
                 const int row = (t * 4 + (lane >> 4)) * 4;  // the window's first row; its partners are the next three
                 const int m = mb + row;
                 if (m < M && n_ok) {
-                    float4 v = act4(*(const float4*)(stg + row * 64 + c4), bias4, p.act);
+                    float4 v = ep4<EXT>(*(const float4*)(stg + row * 64 + c4), scale4, bias4, p.act);
 #pragma unroll
-                    for (int s = 1; s < 4; ++s) v = pmax4(v, act4(*(const float4*)(stg + (row + s) * 64 + c4), bias4, p.act));
+                    for (int s = 1; s < 4; ++s) v = pmax4(v, ep4<EXT>(*(const float4*)(stg + (row + s) * 64 + c4), scale4, bias4, p.act));
                     int b, y, x;
                     pixel_of(m, HW, p.W, 1, b, y, x);
                     *(float4*)(p.dst + (long)b * p.dst_bs + ((long)((y >> 1) + pad) * (Wo + 2 * pad) + (x >> 1) + pad) * p.ld_dst + n) = v;
@@ -240,7 +273,7 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
                 const int row = t * 4 + (lane >> 4);
                 const int m = mb + row;
                 if (m < M && n_ok) {
-                    const float4 v = act4(*(const float4*)(stg + row * 64 + c4), bias4, p.act);
+                    const float4 v = ep4<EXT>(*(const float4*)(stg + row * 64 + c4), scale4, bias4, p.act);
                     int b, y, x;
                     pixel_of(m, HW, p.W, 0, b, y, x);
                     *(float4*)(p.dst + (long)b * p.dst_bs + ((long)(y + pad) * (p.W + 2 * pad) + x + pad) * p.ld_dst + n) = v;
@@ -251,21 +284,24 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
     }
 }
 
-template <int TM>
+// GEMM rows of the launch: every un-pooled pixel, or under pool the four pixels of every whole window
+long m_rows(const Conv2dParams& p) { return (long)p.B * (p.pool ? 4L * (p.H / 2) * (p.W / 2) : (long)p.H * p.W); }
+
+template <int TM, int WN, bool EXT>
 hipError_t go(const Conv2dParams& p, hipStream_t stream) {
-    constexpr int BM = 64 * TM;
+    constexpr int BM = (4 / WN) * 32 * TM, BN = 64 * WN;
     constexpr int plane2 = 2 * (BM + BN) * ROWB;
     constexpr int lds = plane2 > 4 * 8192 ? plane2 : 4 * 8192;
-    hipError_t e = ensure_dynamic_lds<conv2d3x3_kernel<TM>>(lds);
+    hipError_t e = ensure_dynamic_lds<conv2d3x3_kernel<TM, WN, EXT>>(lds);
     if (e != hipSuccess) return e;
-    const long M = (long)p.B * p.H * p.W;
+    const long M = m_rows(p);
     dim3 grid((unsigned)(((M + BM - 1) / BM) * ((p.N + BN - 1) / BN)));
-    hipLaunchKernelGGL((conv2d3x3_kernel<TM>), grid, dim3(256), lds, stream, p);
+    hipLaunchKernelGGL((conv2d3x3_kernel<TM, WN, EXT>), grid, dim3(256), lds, stream, p);
     return hipGetLastError();
 }
 
 // ---- the C = 1 layer: thread = (pixel or window, 4 output channels) ----
-template <int POOL>
+template <int POOL, bool EXT>
 __global__ __launch_bounds__(256) void conv2d3x3_first_kernel(Conv2dParams p) {
     const int n4 = p.N >> 2;
     const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
@@ -289,8 +325,8 @@ __global__ __launch_bounds__(256) void conv2d3x3_first_kernel(Conv2dParams p) {
     float4 w[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) w[t] = *(const float4*)(p.Wt + t * p.N + n);
-    float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.bias) bias4 = *(const float4*)(p.bias + n);
+    float4 scale4, bias4;
+    load_ep<EXT>(p, n, true, scale4, bias4);
     float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int dy = 0; dy < S; ++dy)
@@ -302,7 +338,7 @@ __global__ __launch_bounds__(256) void conv2d3x3_first_kernel(Conv2dParams p) {
                 const float v = in[dy + t / 3][dx + t % 3];
                 a.x = fmaf(v, w[t].x, a.x); a.y = fmaf(v, w[t].y, a.y); a.z = fmaf(v, w[t].z, a.z); a.w = fmaf(v, w[t].w, a.w);
             }
-            a = act4(a, bias4, p.act);
+            a = ep4<EXT>(a, scale4, bias4, p.act);
             out = (dy | dx) ? pmax4(out, a) : a;
         }
     const int pad = p.dst_pad;
@@ -330,7 +366,12 @@ const char* conv2d3x3_refusal(const Conv2dParams& p) {
     if (p.N & 3) return "Cout must be a multiple of 4 (vector stores)";
     if (p.act < 0 || p.act > 1) return "act must be 0 (none) or 1 (ReLU)";
     if (p.pool < 0 || p.pool > 1) return "pool must be 0 or 1";
-    if (p.pool && ((p.H | p.W) & 1)) return "H and W must be even under pool (2 x 2 windows, stride 2)";
+    if (p.pool_floor < 0 || p.pool_floor > 1) return "pool_floor must be 0 or 1";
+    if (p.pool_floor && !p.pool) return "pool_floor needs pool";
+    if (p.pool && !p.pool_floor && ((p.H | p.W) & 1)) return "H and W must be even under pool (2 x 2 windows, stride 2)";
+    if (p.pool_floor && (p.H < 2 || p.W < 2)) return "the map is smaller than one 2 x 2 pool window";
+    if ((p.scale != nullptr) != (p.shift != nullptr)) return "the affine needs both scale and shift";
+    if (p.scale && p.bias) return "bias and an affine together: the shift carries the bias";
     if (p.dst_pad < 0) return "dst border width must not be negative";
     if (p.ld_dst < p.N) return "the dst pixel pitch is smaller than Cout";
     if ((p.ld_dst | p.dst_bs) & 3) return "dst pixel pitch and example stride must be multiples of 4 floats (vector stores)";
@@ -341,33 +382,46 @@ const char* conv2d3x3_refusal(const Conv2dParams& p) {
         if (p.B > 1 && p.dst_bs < (Ho + 2 * p.dst_pad) * (Wo + 2 * p.dst_pad) * p.ld_dst)
             return "dst example stride is smaller than one bordered image";
     }
-    if (((uintptr_t)p.Wt | (uintptr_t)p.bias | (uintptr_t)p.dst | (p.C == 1 ? 0 : (uintptr_t)p.src)) & 15)
+    if (((uintptr_t)p.Wt | (uintptr_t)p.bias | (uintptr_t)p.scale | (uintptr_t)p.shift | (uintptr_t)p.dst | (p.C == 1 ? 0 : (uintptr_t)p.src)) & 15)
         return "operands must be 16-byte aligned";
     if ((uintptr_t)p.src & 3) return "operands must be 4-byte aligned";
     const unsigned long a_span = (unsigned long)p.B * (unsigned long)p.src_bs * 4ul;
     const unsigned long w_span = (unsigned long)p.N * 9ul * (unsigned long)p.C * 4ul;
     if (a_span >= (1ul << 32) - 64 || w_span >= (1ul << 32) - 64) return "an operand is not addressable with 32-bit offsets";
-    const long M = (long)p.B * p.H * p.W;
+    const long M = m_rows(p);
     if (M > 0x7fffffffL - 256) return "too many pixels";
-    if (((M + 63) / 64) * ((p.N + BN - 1) / BN) > 0x7fffffffL || M * (p.N / 4) / 256 > 0x7fffffffL) return "too many tiles";
+    if (((M + 63) / 64) * ((p.N + 63) / 64) > 0x7fffffffL || M * (p.N / 4) / 256 > 0x7fffffffL) return "too many tiles";
     return nullptr;
 }
 
 hipError_t launch_conv2d3x3(const Conv2dParams& p, hipStream_t stream) {
     if (conv2d3x3_refusal(p)) return hipErrorInvalidValue;
+    // the instantiations with the affine epilogue / floor pooling / the 64-wide tile serve only the launches that ask for them
+    const bool ext = p.scale || p.pool_floor || p.n64;
     if (p.C == 1) {
         const long items = (long)p.B * (p.pool ? (p.H / 2) * (p.W / 2) : p.H * p.W) * (p.N / 4);
         dim3 grid((unsigned)((items + 255) / 256));
-        if (p.pool)
-            hipLaunchKernelGGL((conv2d3x3_first_kernel<1>), grid, dim3(256), 0, stream, p);
+        if (ext) {
+            if (p.pool)
+                hipLaunchKernelGGL((conv2d3x3_first_kernel<1, true>), grid, dim3(256), 0, stream, p);
+            else
+                hipLaunchKernelGGL((conv2d3x3_first_kernel<0, true>), grid, dim3(256), 0, stream, p);
+        } else if (p.pool)
+            hipLaunchKernelGGL((conv2d3x3_first_kernel<1, false>), grid, dim3(256), 0, stream, p);
         else
-            hipLaunchKernelGGL((conv2d3x3_first_kernel<0>), grid, dim3(256), 0, stream, p);
+            hipLaunchKernelGGL((conv2d3x3_first_kernel<0, false>), grid, dim3(256), 0, stream, p);
         return hipGetLastError();
     }
+    const long M = m_rows(p);
+    if (ext && p.n64 && p.N <= 64 && tuning().conv2d_n64) {
+        // Cout <= 64: a 128-wide tile would multiply 64 columns of padding; 256-row tiles once they fill the chip (the bits are the same)
+        return (M > 128 && (M + 255) / 256 >= device_cus()) ? go<2, 1, true>(p, stream) : go<1, 1, true>(p, stream);
+    }
     // 128-row tiles once they fill the chip, 64-row tiles for few pixels (the bits are the same)
-    const long M = (long)p.B * p.H * p.W;
-    const long t128 = ((M + 127) / 128) * ((p.N + BN - 1) / BN);
-    return (M > 64 && t128 >= device_cus()) ? go<2>(p, stream) : go<1>(p, stream);
+    const long t128 = ((M + 127) / 128) * ((p.N + 127) / 128);
+    const bool big = M > 64 && t128 >= device_cus();
+    if (ext) return big ? go<2, 2, true>(p, stream) : go<1, 2, true>(p, stream);
+    return big ? go<2, 2, false>(p, stream) : go<1, 2, false>(p, stream);
 }
 
 }  // namespace s3

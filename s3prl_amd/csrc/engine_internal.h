@@ -10,6 +10,7 @@
 //   decoar.hip  DeCoAR: the log-mel front end, a projection and two LSTM stacks on rnnb.hip's batch-shared step
 //   npc.hip     NPC: the log-mel front end, ConvBlocks and masked convolutions on convtaps.hip's two-run implicit GEMM
 //   vggish.hip  VGGish: the un-padded log-mel examples, the 3 x 3 conv + pool stack on conv2d.hip, three Linears, the quantiser
+//   byol_a.hip  BYOL-A: per-segment FFT log-mel (melspec.hip), conv + BatchNorm + floor-pool on conv2d.hip, two Linears, max + mean
 //   (a family file holds its configuration check, its weights and its forward schedule: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
 #pragma once
@@ -438,6 +439,13 @@ struct VggishW {
     DevBuf dft, melT;
 };
 
+// BYOL-A (byol_a.hip): per conv layer conv2d.hip's packed image (taps transposed: the image is time x mel) and the BatchNorm as the
+// epilogue's per-channel scale / shift (the conv bias inside the shift), and the two Linears
+struct ByolAW {
+    DevBuf cw[3], scale[3], shift[3];
+    DevBuf fw[2], fb[2];
+};
+
 // Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table, and per layer (ONE layer with
 // share_layer) q|k|v stacked as one (3 D, D) operand with q pre-scaled by head_dim^-0.5, the other projections and LayerNorm affines
 struct MjLayerW {
@@ -517,6 +525,8 @@ struct s3enc_encoder {
     s3enc_npc_config npc_cfg = {};      // ... and its second configuration block (s3enc_create_npc)
     std::unique_ptr<VggishW> vggish;    // S3ENC_VGGISH
     s3enc_vggish_config vggish_cfg = {};  // ... and its second configuration block (s3enc_create_vggish)
+    std::unique_ptr<ByolAW> byol_a;     // S3ENC_BYOL_A
+    s3enc_byol_a_config byol_a_cfg = {};  // ... and its second configuration block (s3enc_create_byol_a)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -822,6 +832,13 @@ int vggish_check_config(const s3enc_config& c, const s3enc_vggish_config& x);
 int vggish_create(s3enc_encoder* e, const Ckpt& ck);
 long vggish_num_examples(const s3enc_vggish_config& x, long n_samples);  // E of an n-sample utterance, 0 when it holds no example
 int vggish_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+// byol_a.hip: the S3ENC_BYOL_A family (segments -> FFT log-mel -> conv / BatchNorm / floor-pool stack -> Linears -> max + mean; the
+// rows behind an utterance's own segments are the reference's values, not zeros)
+int byol_a_check_config(const s3enc_config& c, const s3enc_byol_a_config& x);
+int byol_a_create(s3enc_encoder* e, const Ckpt& ck);
+long byol_a_num_segments(const s3enc_byol_a_config& x, long n_samples);  // len(range(0, n, stride))
+int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 // mockingjay.hip: the S3ENC_MOCKINGJAY family (spectrogram front end + input representation + post-LN BERT layers, chunked)
 int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x);

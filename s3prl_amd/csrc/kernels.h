@@ -93,6 +93,10 @@ struct Tuning {
                            // 8 B <= 256: 27.0 against 88.8 ms per apc_360hr forward, profiles/apc_360hr_fp32.md), else one launch
     int npc_skip_taps = 1; // npc.hip: 1 = the masked convolutions walk their two runs of live taps only (convtaps.hip), 0 = the same kernel over
                            // all k taps on weights whose masked taps are stored as zeros (equal values; the A/B of profiles/npc_360hr_fp32.md)
+    int conv2d_n64 = 1;    // conv2d.hip: 1 = launches that allow it (Conv2dParams::n64) run Cout <= 64 on the (256 | 128) x 64 tile, 0 = on the
+                           // 128-wide tile, half of whose MFMA columns are then padding (bit-identical; the A/B of profiles/byol_a_fp32.md)
+    int melspec_fft = 1;   // melspec.hip: 1 = the 1024-point STFT as a real FFT in LDS, one workgroup per frame; 0 = the overlapping-row GEMM
+                           // against the folded hann x DFT matrix (fbank.hip's form at K = 1024: the yardstick and the fallback)
     int comm_self_p2p = 0; // comm.hip, S3ENC_EXCHANGE_DIRECT: 1 = a rank's OWN block also travels as an ncclSend-to-self / ncclRecv-from-self
                            // pair inside the state's group instead of a device copy — on a one-GPU box this is the only way the
                            // all-pairs code (symbols, counts, datatype, group bracketing, stream order behind the layer events)
@@ -241,6 +245,12 @@ struct Conv2dParams {
     long dst_bs;
     int dst_pad;
     long ld_dst;
+    // BYOL-A's additions; all zero is the launch as it was (VGGish's)
+    const float* scale;  // [N] or null: v = act(acc * scale[n] + shift[n]) — an eval-mode BatchNorm behind the conv; `bias` must be null
+    const float* shift;  // [N], with scale
+    int pool_floor;      // under pool: odd H / W allowed, Ho = H / 2 and Wo = W / 2 rounded down (nn.MaxPool2d's floor mode); the
+                         // dropped last row / column is never computed
+    int n64;             // 1: Cout <= 64 may run on the 64-wide n-tile (tuning().conv2d_n64); same bits as the 128-wide one
 };
 void pack_conv2d3x3(const float* w, int N, int C, std::vector<float>& out);  // host: nn.Conv2d's (N, C, 3, 3) -> the kernel's image
 const char* conv2d3x3_refusal(const Conv2dParams& p);  // null, or why launch_conv2d3x3 would refuse
@@ -604,6 +614,27 @@ struct LogmelParams {
     long o_bs;
 };
 hipError_t launch_logmel(const LogmelParams& p, hipStream_t st);
+
+// ---- melspec.hip (BYOL-A: per-segment centred 1024-point hann STFT, |X|^2, 64 HTK triangles 60..7800 Hz, log, (x - mean) / std) ----
+long melspec_num_frames(long L);                 // 1 + L / 160
+size_t melspec_sig_elems(long nseg, long L);     // floats of MelspecParams::sig
+size_t melspec_spec_elems(long nseg, long L);    // floats of MelspecParams::spec
+void melspec_bank(std::vector<int>& bands, std::vector<float>& wts);  // host: [3][64] first bin / bins / offset, and the weights
+struct MelspecParams {
+    const float* const* ptrs;  // device [nseg]: the segment's first sample (not read where valid <= 0)
+    const int* valid;          // device [nseg]: samples readable behind ptrs[i]; the segment's samples at or past it are zeros
+    int nseg;
+    int L;                     // samples per segment, >= 1120; every segment is reflect-padded by 512 about its own ends
+    float mean, std_;          // out = (log(mel + FLT_EPSILON) - mean) / std_
+    float* out;                // value (i, t, m) at out + i * o_bs + t * o_row + m
+    long o_bs, o_row;
+    float* power;              // null, or (nseg, frames, 513): |X|^2 before the mel sum
+    int fft;                   // 1 the FFT kernel, 0 the GEMM form (needs sig and spec)
+    float* sig;                // GEMM form: melspec_sig_elems floats, 16-byte aligned
+    float* spec;               // GEMM form: melspec_spec_elems floats
+};
+const char* melspec_refusal(const MelspecParams& p);  // null, or why launch_melspec would refuse
+hipError_t launch_melspec(const MelspecParams& p, hipStream_t st);
 
 // ---- mockingjay.hip (TF-style LayerNorm with a run-time eps; the input representation's row pass) -----------------
 // y = (x (+ pos[row % Tc]) - mean) / sqrt(var + eps) * gamma + beta per row of C (biased variance), one wave per row.

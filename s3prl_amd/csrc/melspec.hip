@@ -1,0 +1,258 @@
+// melspec.hip — BYOL-A's front end (upstream/byol_a/expert.py:45-60,83-107, torchaudio.transforms.MelSpectrogram's defaults), exact
+// fp32, over a table of SEGMENTS of L samples each:
+//   reflect-pad every segment by 512 about ITS OWN ends (center = True on the sub-wav; samples at or past the segment's `valid`
+//   count are zeros: the utterance's zero padding)  ->  1 + L / 160 frames of 1024 samples every 160  ->  periodic hann(1024)
+//   ->  |X|^2 over 513 one-sided bins, no normalisation  ->  64 HTK triangles in Hz between mel-spaced points (f_min 60, f_max 7800,
+//   norm = None, over linspace(0, 8000, 513))  ->  (log(mel + FLT_EPSILON) - mean) / std, written as (segment, frame, mel).
+//
+// Two forms of the spectrum (tuning key melspec_fft):
+//   1  melspec_fft_kernel, one workgroup of 256 threads per frame: the windowed frame packed as 512 complex numbers z[n] = x[2n] +
+//      i x[2n + 1], a 512-point radix-2 Stockham FFT in two LDS buffers (nine stages, one butterfly per thread and stage, a fixed
+//      order: a frame's bits depend on its 1024 samples only), the split X[k] = (Z[k] + Z*[512 - k]) / 2 + e^(-2 pi i k / 1024)
+//      (Z[k] - Z*[512 - k]) / 2i, the power, the sparse mel sum (band m walks its own bins in ascending order), log and the affine.
+//      Twiddles come from one float64-built table e^(-2 pi i m / 1024), m = 0..512.  About 50 kFLOP per frame; 10 KiB LDS, no scratch.
+//   0  fbank.hip's / logmel.hip's form at K = 1024: melspec_pad_kernel materialises every reflect-padded segment, the spectrum is an
+//      overlapping-row GEMM (lda = 160) against hann x DFT folded in float64 into a (2 x 513) x 1024 matrix (2.1 MFLOP per frame), and
+//      melspec_mel_kernel is the same power -> mel -> log -> affine epilogue.  The yardstick and the fallback.
+#include <cfloat>
+#include <cmath>
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "kernels.h"
+
+namespace s3 {
+
+namespace {
+
+constexpr int NFFT = 1024, NBIN = 513, HOP = 160, NMEL = 64, HALF = 512;
+
+// sample i of frame t of a segment: padded position n = 160 t + i - 512 reflected about 0 and about L - 1 (L > 512: one reflection)
+__device__ __forceinline__ float seg_sample(const float* src, int nv, int L, int n) {
+    if (n < 0) n = -n;
+    if (n >= L) n = 2 * (L - 1) - n;
+    return n < nv ? src[n] : 0.f;
+}
+
+// band m's sum over its own bins, ascending, then log and the affine: shared by both forms
+__device__ __forceinline__ float mel_value(const float* pw, const int* bands, const float* wts, int m, float mean, float std_) {
+    const int lo = bands[m], n = bands[NMEL + m];
+    const float* w = wts + bands[2 * NMEL + m];
+    float acc = 0.f;
+    for (int i = 0; i < n; ++i) acc = fmaf(pw[lo + i], w[i], acc);
+    return (logf(acc + FLT_EPSILON) - mean) / std_;
+}
+
+__global__ __launch_bounds__(256) void melspec_fft_kernel(const float* const* ptrs, const int* valid, int L, int T, const float2* tw,
+                                                          const float* win, const int* bands, const float* wts, float mean, float std_,
+                                                          float* out, long o_bs, long o_row, float* power) {
+    __shared__ float2 za[HALF], zb[HALF];
+    __shared__ float pw[NBIN + 3];
+    const int tid = threadIdx.x;
+    const long r = blockIdx.x;
+    const int seg = (int)(r / T), t = (int)(r - (long)seg * T);
+    const float* src = ptrs[seg];
+    int nv = valid[seg];
+    nv = nv < 0 ? 0 : (nv > L ? L : nv);
+    const int base = t * HOP - HALF;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int n = tid + 256 * h;
+        za[n] = make_float2(seg_sample(src, nv, L, base + 2 * n) * win[2 * n], seg_sample(src, nv, L, base + 2 * n + 1) * win[2 * n + 1]);
+    }
+    __syncthreads();
+    float2 *in = za, *ot = zb;
+#pragma unroll 1
+    for (int ns = 1; ns < HALF; ns <<= 1) {  // Stockham radix 2: natural order in, natural order out
+        const int k = tid & (ns - 1);
+        const float2 w = tw[k * (HALF / ns)];  // e^(-2 pi i k / (2 ns))
+        const float2 a = in[tid], b = in[tid + 256];
+        const float2 c = make_float2(b.x * w.x - b.y * w.y, b.x * w.y + b.y * w.x);
+        const int j = ((tid - k) << 1) + k;
+        ot[j] = make_float2(a.x + c.x, a.y + c.y);
+        ot[j + ns] = make_float2(a.x - c.x, a.y - c.y);
+        __syncthreads();
+        float2* s = in;
+        in = ot;
+        ot = s;
+    }
+    // `in` holds Z; bins tid, tid + 256 and (thread 0) 512
+    float* prow = power ? power + r * NBIN : nullptr;
+    for (int k = tid; k < NBIN; k += 256) {
+        const float2 zk = in[k & (HALF - 1)], zm = in[(HALF - k) & (HALF - 1)];
+        const float er = 0.5f * (zk.x + zm.x), ei = 0.5f * (zk.y - zm.y);   // (Z[k] + conj Z[512 - k]) / 2
+        const float orr = 0.5f * (zk.y + zm.y), oi = -0.5f * (zk.x - zm.x);  // (Z[k] - conj Z[512 - k]) / 2i
+        const float2 w = tw[k];
+        const float xr = er + (orr * w.x - oi * w.y), xi = ei + (orr * w.y + oi * w.x);
+        const float v = xr * xr + xi * xi;
+        pw[k] = v;
+        if (prow) prow[k] = v;
+    }
+    __syncthreads();
+    if (tid < NMEL) out[seg * o_bs + t * o_row + tid] = mel_value(pw, bands, wts, tid, mean, std_);
+}
+
+__global__ __launch_bounds__(256) void melspec_pad_kernel(const float* const* ptrs, const int* valid, int L, long Lp, float* sig) {
+    const int seg = blockIdx.y;
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= Lp) return;
+    int nv = valid[seg];
+    nv = nv < 0 ? 0 : (nv > L ? L : nv);
+    sig[(long)seg * Lp + j] = j < L + NFFT ? seg_sample(ptrs[seg], nv, L, (int)j - HALF) : 0.f;
+}
+
+// one workgroup per frame of the GEMM form: row r of `spec` is (re[513] | im[513])
+__global__ __launch_bounds__(256) void melspec_mel_kernel(const float* spec, int T, const int* bands, const float* wts, float mean,
+                                                          float std_, float* out, long o_bs, long o_row, float* power) {
+    __shared__ float pw[NBIN + 3];
+    const long r = blockIdx.x;
+    const int seg = (int)(r / T), t = (int)(r - (long)seg * T);
+    const float* s = spec + r * (2L * NBIN);
+    for (int k = threadIdx.x; k < NBIN; k += 256) {
+        const float re = s[k], im = s[NBIN + k];
+        const float v = re * re + im * im;
+        pw[k] = v;
+        if (power) power[r * NBIN + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NMEL) out[seg * o_bs + t * o_row + threadIdx.x] = mel_value(pw, bands, wts, threadIdx.x, mean, std_);
+}
+
+struct MelspecPlan {
+    float2* tw = nullptr;   // e^(-2 pi i m / 1024), m = 0..512
+    float* win = nullptr;   // periodic hann(1024)
+    int* bands = nullptr;   // [3][64]: first bin, bins, offset into wts
+    float* wts = nullptr;   // the non-zero triangle weights, band by band
+    float* dft = nullptr;   // the GEMM form's (2 * 513, 1024) matrix, built on first use
+};
+std::mutex g_mu;
+std::map<int, MelspecPlan> g_plans;
+
+template <class T>
+hipError_t to_device(T** dst, const std::vector<T>& v) {
+    hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T) + 16);
+    if (e != hipSuccess) return e;
+    return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+hipError_t build_plan(MelspecPlan& pl) {
+    std::vector<float2> tw(HALF + 1);
+    for (int m = 0; m <= HALF; ++m) {
+        const double a = 2.0 * M_PI * m / NFFT;
+        tw[m] = make_float2((float)std::cos(a), (float)-std::sin(a));
+    }
+    std::vector<float> win(NFFT);
+    for (int i = 0; i < NFFT; ++i) win[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / NFFT));
+    std::vector<int> bands;
+    std::vector<float> wts;
+    melspec_bank(bands, wts);
+    hipError_t e = to_device(&pl.tw, tw);
+    if (e == hipSuccess) e = to_device(&pl.win, win);
+    if (e == hipSuccess) e = to_device(&pl.bands, bands);
+    if (e == hipSuccess) e = to_device(&pl.wts, wts);
+    return e;
+}
+
+hipError_t build_dft(MelspecPlan& pl) {
+    std::vector<float> M((size_t)2 * NBIN * NFFT);
+    for (int r = 0; r < NBIN; ++r)
+        for (int i = 0; i < NFFT; ++i) {
+            const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * i / NFFT);
+            const double a = 2.0 * M_PI * (double)((long)r * i % NFFT) / NFFT;
+            M[(size_t)r * NFFT + i] = (float)(w * std::cos(a));
+            M[(size_t)(NBIN + r) * NFFT + i] = (float)(-w * std::sin(a));
+        }
+    return to_device(&pl.dft, M);
+}
+
+}  // namespace
+
+// torchaudio.functional.melscale_fbanks(513, 60, 7800, 64, 16000, norm = None, "htk") in float64, stored band by band: only the
+// non-zero weights (a bin feeds at most two bands)
+void melspec_bank(std::vector<int>& bands, std::vector<float>& wts) {
+    auto hz2mel = [](double f) { return 2595.0 * std::log10(1.0 + f / 700.0); };
+    auto mel2hz = [](double m) { return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0); };
+    const double m_lo = hz2mel(60.0), m_hi = hz2mel(7800.0);
+    std::vector<double> fpt(NMEL + 2);
+    for (int i = 0; i < NMEL + 2; ++i) fpt[i] = mel2hz(m_lo + (m_hi - m_lo) * i / (NMEL + 1));
+    bands.assign(3 * NMEL, 0);
+    wts.clear();
+    for (int m = 0; m < NMEL; ++m) {
+        int lo = -1, hi = -1;
+        std::vector<float> w(NBIN);
+        for (int k = 0; k < NBIN; ++k) {
+            const double f = 8000.0 * k / (NBIN - 1);
+            const double down = (f - fpt[m]) / (fpt[m + 1] - fpt[m]), up = (fpt[m + 2] - f) / (fpt[m + 2] - fpt[m + 1]);
+            w[k] = (float)std::fmax(0.0, std::fmin(down, up));
+            if (w[k] != 0.f) {
+                if (lo < 0) lo = k;
+                hi = k;
+            }
+        }
+        bands[m] = lo < 0 ? 0 : lo;
+        bands[NMEL + m] = lo < 0 ? 0 : hi - lo + 1;
+        bands[2 * NMEL + m] = (int)wts.size();
+        for (int k = bands[m]; k < bands[m] + bands[NMEL + m]; ++k) wts.push_back(w[k]);
+    }
+}
+
+long melspec_num_frames(long L) { return 1 + L / HOP; }
+size_t melspec_sig_elems(long nseg, long L) { return (size_t)nseg * (size_t)((L + NFFT + 3) & ~3L); }
+size_t melspec_spec_elems(long nseg, long L) { return (size_t)nseg * (size_t)melspec_num_frames(L) * 2 * NBIN; }
+
+const char* melspec_refusal(const MelspecParams& p) {
+    if (!p.ptrs || !p.valid || !p.out) return "null operand";
+    if (p.nseg < 1) return "no segments";
+    if (p.L <= 512) return "a segment of at most 512 samples cannot be reflect-padded by 512 (n_fft / 2)";
+    if (p.L < 1120) return "a segment below 1120 samples has fewer than 8 frames: nothing survives three 2 x 2 pools";
+    if (p.L > (1 << 24)) return "segment too long";
+    const long T = melspec_num_frames(p.L);
+    if ((long)p.nseg * T > 0x7fffffffL / (2 * NBIN) || p.nseg > 65535 * 16) return "too many frames";
+    if (p.o_row < NMEL || p.o_bs < (T - 1) * p.o_row + NMEL) return "the output pitches are smaller than one segment";
+    if (!p.fft && (!p.sig || !p.spec)) return "the GEMM form needs its scratch buffers";
+    if (!p.fft && p.nseg > 65535) return "too many segments for the GEMM form";
+    return nullptr;
+}
+
+hipError_t launch_melspec(const MelspecParams& p, hipStream_t st) {
+    if (melspec_refusal(p)) return hipErrorInvalidValue;
+    const long T = melspec_num_frames(p.L);
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    MelspecPlan* pl;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        pl = &g_plans[dev];
+        if (!pl->tw && (e = build_plan(*pl)) != hipSuccess) return e;
+        if (!p.fft && !pl->dft && (e = build_dft(*pl)) != hipSuccess) return e;
+    }
+    const unsigned frames = (unsigned)(p.nseg * T);
+    if (p.fft) {
+        hipLaunchKernelGGL(melspec_fft_kernel, dim3(frames), dim3(256), 0, st, p.ptrs, p.valid, p.L, (int)T, pl->tw, pl->win, pl->bands,
+                           pl->wts, p.mean, p.std_, p.out, p.o_bs, p.o_row, p.power);
+        return hipGetLastError();
+    }
+    const long Lp = (p.L + NFFT + 3) & ~3L;
+    hipLaunchKernelGGL(melspec_pad_kernel, dim3((unsigned)((Lp + 255) / 256), p.nseg), dim3(256), 0, st, p.ptrs, p.valid, p.L, Lp, p.sig);
+    GemmParams g{};
+    g.A = p.sig;
+    g.lda = HOP;  // overlapping rows: frame t starts at padded sample 160 t
+    g.a_bs = Lp;
+    g.W = pl->dft;
+    g.M = (int)T;
+    g.N = 2 * NBIN;
+    g.K = NFFT;
+    g.batches = p.nseg;
+    g.out32 = p.spec;
+    g.ldo = 2 * NBIN;
+    g.o_bs = T * 2 * NBIN;
+    e = launch_gemm(F32, g, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(melspec_mel_kernel, dim3(frames), dim3(256), 0, st, p.spec, (int)T, pl->bands, pl->wts, p.mean, p.std_, p.out, p.o_bs,
+                       p.o_row, p.power);
+    return hipGetLastError();
+}
+
+}  // namespace s3

@@ -27,6 +27,7 @@ int tuning_set(Tuning& t, const char* key, int value, const char** err) {
         {"ln_preload", &Tuning::ln_preload, 0, 1},           {"forward_chain", &Tuning::forward_chain, 0, 1},
         {"conv0_fast", &Tuning::conv0_fast, 0, 1},           {"conv_f22", &Tuning::conv_f22, 0, 1},
         {"rnn_split", &Tuning::rnn_split, -1, 8},           {"npc_skip_taps", &Tuning::npc_skip_taps, 0, 1},
+        {"conv2d_n64", &Tuning::conv2d_n64, 0, 1},           {"melspec_fft", &Tuning::melspec_fft, 0, 1},
         {"gemm32_tail", &Tuning::gemm32_tail, 0, 2},         {"gemm32_tail_units", &Tuning::gemm32_tail_units, 0, 1 << 20},
     };
     static thread_local char msg[160];
@@ -534,6 +535,88 @@ int s3enc_op_conv2d3x3(const float* x, const float* w_host, const float* bias, i
     p.Wt = (const float*)dw.p;
     HIP_TRY(launch_conv2d3x3(p, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
+    return 0;
+}
+
+int s3enc_op_conv2d3x3_affine(const float* x, const float* w_host, const float* bias, const float* scale, const float* shift, int32_t B,
+                              int32_t H, int32_t W, int32_t C, int32_t N, int32_t act, int32_t pool, int32_t pool_floor, float* dst,
+                              int32_t dst_pad, int64_t ldo, void* stream) {
+    if (!x || !w_host || !dst) return fail("s3enc_op_conv2d3x3_affine: null argument");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0) return fail("s3enc_op_conv2d3x3_affine: bad shape");
+    if (H > 32768 || W > 32768 || B > (1 << 24)) return fail("s3enc_op_conv2d3x3_affine: bad shape");
+    Conv2dParams p{};
+    p.src = x;
+    p.src_bs = (long)(H + 2) * (W + 2) * C;
+    p.C = C;
+    p.bias = bias;
+    p.scale = scale;
+    p.shift = shift;
+    p.H = H;
+    p.W = W;
+    p.N = N;
+    p.B = B;
+    p.act = act;
+    p.pool = pool;
+    p.pool_floor = pool_floor;
+    p.n64 = 1;
+    p.dst = dst;
+    p.dst_pad = dst_pad;
+    p.ld_dst = ldo;
+    {
+        const long Ho = pool == 1 ? H / 2 : H, Wo = pool == 1 ? W / 2 : W;
+        p.dst_bs = (Ho + 2 * (long)dst_pad) * (Wo + 2 * (long)dst_pad) * ldo;
+    }
+    alignas(16) static float stand_in[4];  // the checks that need no device memory first
+    p.Wt = stand_in;
+    if (const char* why = conv2d3x3_refusal(p)) return fail(std::string("s3enc_op_conv2d3x3_affine: ") + why);
+    std::vector<float> packed;
+    pack_conv2d3x3(w_host, N, C, packed);
+    DevBuf dw;
+    HIP_TRY(upload_f32(dw, packed));
+    p.Wt = (const float*)dw.p;
+    HIP_TRY(launch_conv2d3x3(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
+    return 0;
+}
+
+int s3enc_op_melspec1024(const float* segments, int32_t nseg, int32_t L, float* out, float* power, void* stream) {
+    if (!segments || !out) return fail("s3enc_op_melspec1024: null argument");
+    if (nseg <= 0 || nseg > 65535) return fail("s3enc_op_melspec1024: nseg must be 1..65535");
+    MelspecParams p{};
+    p.nseg = nseg;
+    p.L = L;
+    p.mean = -5.4919195f;
+    p.std_ = 5.0389895f;
+    p.out = out;
+    p.o_row = 64;
+    p.o_bs = melspec_num_frames(L > 0 ? L : 0) * 64;
+    p.power = power;
+    p.fft = tuning().melspec_fft;
+    static const float* const stand_in_ptr = nullptr;
+    static const int stand_in_val = 0;
+    p.ptrs = &stand_in_ptr;  // the checks that need no device memory first
+    p.valid = &stand_in_val;
+    p.sig = p.spec = out;
+    if (const char* why = melspec_refusal(p)) return fail(std::string("s3enc_op_melspec1024: ") + why);
+    std::vector<const float*> hp(nseg);
+    std::vector<int> hv(nseg, L);
+    for (int i = 0; i < nseg; ++i) hp[i] = segments + (size_t)i * L;
+    DevBuf dp, dv, dsig, dspec;
+    HIP_TRY(dp.ensure(hp.size() * sizeof(const float*)));
+    HIP_TRY(dv.ensure(hv.size() * sizeof(int)));
+    HIP_TRY(hipMemcpy(dp.p, hp.data(), hp.size() * sizeof(const float*), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dv.p, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice));
+    p.ptrs = (const float* const*)dp.p;
+    p.valid = (const int*)dv.p;
+    p.sig = p.spec = nullptr;
+    if (!p.fft) {
+        HIP_TRY(dsig.ensure(melspec_sig_elems(nseg, L) * 4 + 64));
+        HIP_TRY(dspec.ensure(melspec_spec_elems(nseg, L) * 4 + 64));
+        p.sig = (float*)dsig.p;
+        p.spec = (float*)dspec.p;
+    }
+    HIP_TRY(launch_melspec(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the tables and the scratch are freed on return
     return 0;
 }
 

@@ -42,6 +42,8 @@ class HipEncoder:
             raise ValueError(f"NPC is built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "vggish" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             raise ValueError(f"VGGish is built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "byol_a" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"BYOL-A is built for compute dtype fp32 only; {dtype} is not built")
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -88,6 +90,9 @@ class HipEncoder:
             elif cfg.family == "vggish":  # its front end and layer list travel beside the (unchanged) s3enc_config
                 vg = _lib.make_vggish_config(cfg)
                 rc = self._lib.s3enc_create_vggish(C.byref(ccfg), C.byref(vg), tensors, len(weights), self.device, C.byref(h))
+            elif cfg.family == "byol_a":  # its segment geometry travels beside the (unchanged) s3enc_config
+                ba = _lib.make_byol_a_config(cfg)
+                rc = self._lib.s3enc_create_byol_a(C.byref(ccfg), C.byref(ba), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")

@@ -34,6 +34,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _npc_shapes(cfg)
     if cfg.family == "vggish":
         return _vggish_shapes(cfg)
+    if cfg.family == "byol_a":
+        return _byol_a_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -253,6 +255,23 @@ def _vggish_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     return s
 
 
+def _byol_a_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """AudioNTT2020 (upstream/byol_a/byol_a.py:91-137), the reference's state_dict names after its prefix rule: three Conv2d(., 64,
+    3) at ``features.{0,4,8}`` each followed by a BatchNorm2d, ``fc.0`` (d, 64 * 8) and ``fc.3`` (d, d).  ``num_batches_tracked`` is
+    training state and is not listed."""
+    s: Dict[str, tuple] = {}
+    cin, d = 1, cfg.conv_layers[0][0]
+    for k in (0, 4, 8):
+        s[f"features.{k}.weight"] = (64, cin, 3, 3)
+        s[f"features.{k}.bias"] = (64,)
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            s[f"features.{k + 1}.{leaf}"] = (64,)
+        cin = 64
+    s["fc.0.weight"], s["fc.0.bias"] = (d, 512), (d,)
+    s["fc.3.weight"], s["fc.3.bias"] = (d, d), (d,)
+    return s
+
+
 def _decoar_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     """Decoar (upstream/decoar/decoar.py:21-39), the checkpoint's names: the projection and the two multi-layer nn.LSTM modules
     (decoar_layers/expert.py:35-47 renames them to its per-layer modules; both experts read this one file)."""
@@ -460,6 +479,13 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
         elif name.startswith("blocks.") and ".bn" in name:  # non-trivial eval statistics: the BatchNorm fold is exercised
             w = {"weight": lambda: 1.0 + 0.1 * rng.standard_normal(shape), "bias": lambda: -0.1 + 0.05 * rng.standard_normal(shape),
                  "running_mean": lambda: 0.2 * rng.standard_normal(shape), "running_var": lambda: rng.uniform(0.5, 2.0, size=shape)}[leaf]()
+        elif cfg.family == "byol_a" and name.split(".")[1] in ("1", "5", "9") and name.startswith("features."):
+            # eval-mode BatchNorm statistics that do something: running variances well away from zero, means and shifts that move
+            # a good part of the channels across the ReLU's edge
+            w = {"weight": lambda: 1.0 + 0.2 * rng.standard_normal(shape), "bias": lambda: 0.2 * rng.standard_normal(shape),
+                 "running_mean": lambda: 0.3 * rng.standard_normal(shape), "running_var": lambda: rng.uniform(0.5, 2.0, size=shape)}[leaf]()
+        elif cfg.family == "byol_a" and leaf == "weight":
+            w = rng.standard_normal(shape) * np.sqrt(2.0 / int(np.prod(shape[1:])))  # He scaling, as for VGGish
         elif cfg.family == "vggish" and leaf == "weight":
             # He scaling, sqrt(2 / fan_in), through every conv and Linear: ReLU then keeps the second moment of the log-mel input
             # (RMS 3-4 for unit-variance PCM) up to the embedding, about half of whose elements are exact zeros
@@ -697,6 +723,17 @@ def named_config(name: str) -> EncoderConfig:
         from .config import vggish_config
 
         return vggish_config(**vggish[name])
+    # BYOL-A: FFT log-mel segments, three conv + BatchNorm + floor-pool layers, two Linears, max + mean over time
+    byol_a = {
+        "byol_a_2048": dict(feature_d=2048), "byol_a_1024": dict(feature_d=1024), "byol_a_512": dict(feature_d=512),
+        "tiny_byol_a": dict(feature_d=64),
+        "tiny_byol_a_overlap": dict(feature_d=64, window_secs=1.0, stride_secs=0.5),
+        "tiny_byol_a_win025": dict(feature_d=64, window_secs=0.25, stride_secs=0.1),  # 26 frames -> 13 -> 6 -> 3: odd at two levels
+    }
+    if name in byol_a:
+        from .config import byol_a_config
+
+        return byol_a_config(**byol_a[name])
     # Mockingjay / TERA / AudioALBERT: a log-mel (or kaldi fbank) front end into post-LN BERT layers, long inputs in chunks
     tiny_mj = dict(hidden=128, layers=2, heads=2, intermediate=256, input_dim=16, sequence_length=0)
     mj = {
@@ -719,7 +756,7 @@ def named_config(name: str) -> EncoderConfig:
 
         return mockingjay_config(**mj[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(mj))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(byol_a) + list(mj))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
