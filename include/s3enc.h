@@ -86,7 +86,17 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * ceil(n_max / stride).  NOTHING is masked: the rows behind an utterance's own segments are the network's response to the
         * zero padding, the reference's values and not zeros (NPC's convention).  compute_dtype S3ENC_F32 only; built by
         * s3enc_create_byol_a. */
-       S3ENC_BYOL_A = 12 };
+       S3ENC_BYOL_A = 12,
+       /* MAE-AST (upstream/mae_ast/{expert,mae_ast}.py; mae_ast_frame, mae_ast_patch): per utterance a kaldi log-mel front end at 128
+        * bins (25 ms / 10 ms povey frames, pre-emphasis 0.97, snip_edges; F = 1 + (n - 400) / 160 frames), zero-padded to the batch's
+        * F_max; BatchNorm2d(1, affine = False) on its running statistics times 0.5; nn.Unfold into kt x kc patches (token t * V + v, V =
+        * 128 / kc, time the slow axis); Linear(kt * kc, D); the checkpoint's own sinusoidal position rows on the live tokens;
+        * encoder_layers Transformer layers (encoder.layer_norm in front of post-LN layers; pre-LN layers when layer_norm_first) with
+        * the padded tokens masked as keys.  encoder_layers states of (B, F_max / kt, V * D): the layer outputs, V tokens per row.  The
+        * rows at or behind an utterance's valid count are the reference's values, not zeros: zero log-mel rows through the folded
+        * Linear, no position row, queries over the utterance's live keys.  compute_dtype S3ENC_F32 only; built by
+        * s3enc_create_mae_ast. */
+       S3ENC_MAE_AST = 13 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -392,6 +402,29 @@ typedef struct s3enc_byol_a_config {
     float bn_eps;                                   /* 1e-5 */
 } s3enc_byol_a_config;
 
+/* S3ENC_MAE_AST only (mae_ast/expert.py:24-100, mae_ast.py:202-281,305-325,400-481,613-821): the second configuration block of
+ * s3enc_create_mae_ast.  s3enc_config carries embed_dim = D, heads, ffn_dim, encoder_layers and layer_norm_first; its conv fields
+ * are not read.  Patches: kernel = stride = (kt, kc) on both axes; Tt = F_max / kt time steps, V = 128 / kc tokens per step, Ttok =
+ * Tt * V tokens; frames Tt * kt .. F_max are never read.  Key padding (forward_padding_mask): utterance b keeps kv_b =
+ * min(ceil(F_b / kt) * V, Ttok) leading tokens as keys — a patch that is only partly real counts as real.  The eval BatchNorm is
+ * folded into the Linear once, on the host, in float64: s = 0.5 / sqrt(bn_var + bn_eps), W' = s W, b' = b - s bn_mean rowsum(W); the
+ * image stays raw log-mel and the rows behind an utterance's frames stay zeros.  Checkpoint tensors, reference state_dict names:
+ * post_extract_proj.{weight,bias} (D, kt * kc); enc_sine_pos_embed.pe: the LEADING pos_rows rows of the file's table, (pos_rows, D) —
+ * the table in the file is the reference's operand, it is not recomputed; encoder.layer_norm.{weight,bias} (read only without
+ * layer_norm_first: with it the final LayerNorm reaches no returned state and is not computed); encoder.layers.N.self_attn.{q,k,v,
+ * out}_proj.{weight,bias}, .self_attn_layer_norm, .fc1, .fc2, .final_layer_norm.  A batch with more than pos_rows tokens is refused
+ * by message, with the count.  s3enc_create_mae_ast refuses by name: every compute dtype but fp32, feature_dim != 128 (the
+ * reference's mask rule hard-codes 128), kc outside {16, 32, 64, 128}, kt outside 1..32, embed_dim / heads != 64. */
+typedef struct s3enc_mae_ast_config {
+    int32_t kt;                                     /* ast_kernel_size_time = ast_kernel_stride_time: 16 (patch), 2 (frame) */
+    int32_t kc;                                     /* ast_kernel_size_chan = ast_kernel_stride_chan: 16 (patch), 128 (frame) */
+    int32_t feature_dim;                            /* task.feature_dim: 128 */
+    float bn_mean;                                  /* batch_norm.running_mean[0] */
+    float bn_var;                                   /* batch_norm.running_var[0] */
+    float bn_eps;                                   /* 1e-5 */
+    int32_t pos_rows;                               /* rows of enc_sine_pos_embed.pe handed over: min(max_token_length, 8192) */
+} s3enc_mae_ast_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -473,6 +506,17 @@ int s3enc_create_vggish(const s3enc_config* cfg, const s3enc_vggish_config* vggi
  * refused), out_dtype must be S3ENC_F32.  A row (b, s) depends on segment (b, s)'s own `window` samples and on nothing else. */
 int s3enc_create_byol_a(const s3enc_config* cfg, const s3enc_byol_a_config* byol_a, const s3enc_tensor* tensors, int32_t n_tensors,
                         int32_t device, s3enc_handle* out);
+/* The S3ENC_MAE_AST family: s3enc_config beside its own block (the other create entries refuse the family by name).  Replaces
+ * UpstreamExpert.__init__ of upstream/mae_ast/expert.py.  On the handle: s3enc_num_frames(n) is F(n) / kt time steps, F(n) = 1 +
+ * (n - 400) / 160; s3enc_valid_frames(length, n_max) is min(ceil(F(length) / kt), F(n_max) / kt); s3enc_downsample_rate is kt * 160;
+ * s3enc_num_states is encoder_layers for S3ENC_SEL_HIDDEN (the layer outputs, not the embedding; the other selections are refused);
+ * a state row is V * D wide (layer_stride counts B * F_max / kt * V * D elements); out_dtype must be S3ENC_F32; featurize is
+ * elementwise over the same slab (feat_normalize is refused when V > 1: the reference would normalise rows of V * D).  Rows at or
+ * behind an utterance's valid count are the reference's values (see S3ENC_MAE_AST): the attention kernel computes padded query
+ * rows over the live keys, as for the Mockingjay family.  s3enc_forward refuses by message: an utterance under 400 samples (by index
+ * and length), a batch with F_max < kt, a batch with more tokens than pos_rows (with the count).  Tuning key patch_embed_fused. */
+int s3enc_create_mae_ast(const s3enc_config* cfg, const s3enc_mae_ast_config* mae_ast, const s3enc_tensor* tensors, int32_t n_tensors,
+                         int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -713,6 +757,10 @@ int s3enc_debug_gemm_schedule(int32_t M, int32_t N, int32_t batches, int32_t tm,
  *   "conv2d_n64":   S3ENC_BYOL_A handles and s3enc_op_conv2d3x3_affine: 1 (default) = Cout <= 64 runs on the 64-wide n-tile of
  *                   conv2d.hip, 0 = on the 128-wide one, half of whose MFMA columns are then padding — the same bits; measured 1.04
  *                   against 1.28 ms per forward (profiles/byol_a_fp32.md);
+ *   "patch_embed_fused": S3ENC_MAE_AST handles and s3enc_op_patch_embed: 1 (default) = the patch embedding as one implicit GEMM that reads
+ *                   the image in place (patchembed.hip), 0 = a gather kernel that writes the (B * tokens, kt * kc) rows, the tile GEMM
+ *                   and a position add — the yardstick and a second implementation, held to the fixture bound; measured 0.0625
+ *                   against 0.0798 ms per 32 x 10 s mae_ast_patch embedding, the forwards indistinguishable (profiles/mae_ast_fp32.md);
  *   "conv_f22":     S3ENC_F32: 1 (default) = conv layers 1.. with kernel 3 and stride 2 (conv1-4 of every extractor) run in the
  *                   two-output form (convf22.hip: 5 block products per pair of outputs instead of 6, fp32 operands and accumulation,
  *                   a different association — results differ in the last bits), 0 = the implicit GEMM;
@@ -878,6 +926,18 @@ int s3enc_op_conv2d3x3_affine(const float* x, const float* w_host, const float* 
  * depend on its 1024 samples only), 0 = the overlapping-row GEMM against the folded hann x DFT matrix.  Refused by message: L <= 512
  * (the reflection is undefined), L < 1120 (fewer than 8 frames).  Synchronises. */
 int s3enc_op_melspec1024(const float* segments, int32_t nseg, int32_t L, float* out, float* power, void* stream);
+
+/* The patch embedding of (frames, 128) fp32 images as an implicit GEMM over the tokens of all utterances (patchembed.hip): nn.Unfold
+ * with kernel = stride = (kt, kc), Linear(kt * kc, N) and a position row in one pass.
+ *   out[b][t*V+v][n] = sum_{r<kt} sum_{c<kc} img[b][t*kt + r][v*kc + c] * w[n][r*kc + c] + bias[n] + (t*V+v < kv[b] ? pos[t*V+v][n] : 0)
+ *   img: device fp32, utterance b at img + b * img_bs, rows of 128 floats; only rows [0, Tt * kt) are read.  w_host: HOST fp32 (N, kt *
+ *   kc), the Linear's weight as stored.  bias: device [N] or null.  pos: device (>= Tt * V, N) with kv: device int32 [B], or both
+ *   null.  out: device (B, Tt * V, N), V = 128 / kc.  fp32 MFMA on 64-byte K steps in a fixed order (patch rows ascending, then the
+ *   step's order): a token row's bits depend neither on B, nor on its place in the batch, nor on Tt, nor on the tile height.
+ * Refused by message: kc outside {16, 32, 64, 128}, kt outside 1..32, N % 4 != 0, img_bs < Tt * kt * 128 or not a multiple of 4,
+ * operands that are not 16-byte aligned.  Tuning key patch_embed_fused = 0: gather + tile GEMM + position add.  Synchronises. */
+int s3enc_op_patch_embed(const float* img, int64_t img_bs, const float* w_host, const float* bias, const float* pos, const int32_t* kv,
+                         int32_t B, int32_t Tt, int32_t kt, int32_t kc, int32_t N, float* out, void* stream);
 
 /* A forward and a backward unidirectional nn.LSTM on packed sequences, side by side, on the batch-shared kernel: one launch per
  * time step for both directions, W_hh read once per step for the whole batch (fp32 MFMA).  pre_fwd / pre_bwd: device fp32, row

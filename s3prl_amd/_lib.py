@@ -19,7 +19,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -125,6 +125,12 @@ class S3ByolAConfig(C.Structure):
                 ("norm_std", C.c_float), ("bn_eps", C.c_float)]
 
 
+class S3MaeAstConfig(C.Structure):
+    """s3enc_mae_ast_config: the patch / BatchNorm block of an MAE-AST handle (s3enc_create_mae_ast)."""
+    _fields_ = [("kt", C.c_int32), ("kc", C.c_int32), ("feature_dim", C.c_int32), ("bn_mean", C.c_float), ("bn_var", C.c_float),
+                ("bn_eps", C.c_float), ("pos_rows", C.c_int32)]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -160,6 +166,7 @@ _PROTOS = {
     "s3enc_create_npc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3NpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_vggish": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3VggishConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_create_byol_a": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3ByolAConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    "s3enc_create_mae_ast": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3MaeAstConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -213,6 +220,7 @@ _PROTOS = {
     "s3enc_op_conv2d3x3": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
     "s3enc_op_conv2d3x3_affine": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
     "s3enc_op_melspec1024": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
+    "s3enc_op_patch_embed": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
@@ -453,4 +461,20 @@ def make_byol_a_config(cfg) -> S3ByolAConfig:
     c = S3ByolAConfig()
     c.feature_d, c.window, c.stride = (int(v) for v in cfg.conv_layers[0])
     c.norm_mean, c.norm_std, c.bn_eps = float(cfg.ba_norm_mean), float(cfg.ba_norm_std), float(cfg.ba_bn_eps)
+    return c
+
+
+def make_mae_ast_config(cfg, weights) -> S3MaeAstConfig:
+    """The second configuration block of a ``family="mae_ast"`` EncoderConfig (``s3enc_create_mae_ast``).  The BatchNorm's running
+    statistics are checkpoint tensors: they are read off ``weights`` and travel in the block."""
+    if cfg.family != "mae_ast":
+        raise S3EncError("make_mae_ast_config needs a mae_ast configuration")
+    for name in ("batch_norm.running_mean", "batch_norm.running_var"):
+        if name not in weights:
+            raise S3EncError(f"make_mae_ast_config: missing parameter {name}")
+    as_float = lambda w: float(w.detach().cpu().reshape(-1)[0]) if hasattr(w, "detach") else float(w.reshape(-1)[0])
+    c = S3MaeAstConfig()
+    c.kt, c.kc, c.feature_dim = int(cfg.ma_kt), int(cfg.ma_kc), int(cfg.ma_feature_dim)
+    c.bn_mean, c.bn_var = as_float(weights["batch_norm.running_mean"]), as_float(weights["batch_norm.running_var"])
+    c.bn_eps, c.pos_rows = float(cfg.ma_bn_eps), int(cfg.ma_pos_rows)
     return c

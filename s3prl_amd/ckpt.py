@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, byol_a_config, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, byol_a_config, config_from_mae_ast, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -200,6 +200,71 @@ def load_byol_a_checkpoint(ckpt, feature_d: int = None, window_secs: float = 1.0
     return cfg, _hot_path_weights(what, cfg, sd)
 
 
+# what an MAE-AST state dict holds and the forward never reads (mae_ast.py:202-281): the decoder, the reconstruction / classification
+# heads, the mask embeddings, the LayerNorm(feature_dim) and the decoder's position table; num_batches_tracked is training state
+MAE_AST_UNUSED = ("decoder.", "final_proj_", "encoder_mask_emb", "decoder_mask_emb", "layer_norm.", "dec_sine_pos_embed.pe",
+                  "batch_norm.num_batches_tracked")
+
+
+def mae_ast_hot_path(what: str, cfg: EncoderConfig, sd) -> Dict[str, np.ndarray]:
+    """The tensors an MAE-AST handle reads, out of a strict state dict (or of an already cut one): every hot-path parameter is
+    required, ``enc_sine_pos_embed.pe`` — ``(1, max_token_length, D)`` in the file — is cut to its leading ``cfg.ma_pos_rows`` rows
+    (the file's table is the operand: it is not recomputed), the keys of ``MAE_AST_UNUSED`` are ignored and any other key fails."""
+    shapes = param_shapes(cfg)
+    for k in sd:
+        if k not in shapes and not k.startswith(MAE_AST_UNUSED):
+            raise ValueError(f"{what}: unexpected parameter {k} (not a tensor of MAE_AST with this configuration)")
+    sd = dict(sd)
+    if "enc_sine_pos_embed.pe" in sd:
+        pe = sd["enc_sine_pos_embed.pe"]
+        pe = pe.detach().cpu().float().numpy() if hasattr(pe, "detach") else np.asarray(pe, dtype=np.float32)
+        D = cfg.encoder_embed_dim
+        if pe.ndim == 3:
+            if pe.shape != (1, cfg.ma_max_token_length, D):
+                raise ValueError(f"{what}: parameter enc_sine_pos_embed.pe has shape {tuple(pe.shape)}, expected "
+                                 f"{(1, cfg.ma_max_token_length, D)}")
+            pe = pe[0, :cfg.ma_pos_rows]
+        sd["enc_sine_pos_embed.pe"] = np.ascontiguousarray(pe)
+    return _hot_path_weights(what, cfg, sd)
+
+
+def load_mae_ast_checkpoint(ckpt) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"cfg": {"model": MAE_AST_Config, "task": {feature_dim, sample_rate, ...}}, "model": state_dict}`` (mae_ast/expert.py:28-45)
+    — the path of a file holding one, or the dict.  The reference loads with ``strict=True``; here every tensor the forward reads is
+    required, the ones it never reads are ignored by name (``MAE_AST_UNUSED``) and anything else fails."""
+    what = ckpt if isinstance(ckpt, str) else "the MAE-AST checkpoint"
+    if not isinstance(ckpt, dict):
+        import torch
+
+        ckpt = torch.load(ckpt, map_location="cpu", weights_only=False)
+    if "cfg" not in ckpt or "model" not in ckpt:
+        raise ValueError(f"{what} is not a valid checkpoint since the required key: {'cfg' if 'cfg' not in ckpt else 'model'} is missing")
+    c = _plain(ckpt["cfg"])
+    for key in ("model", "task"):
+        if key not in c:
+            raise ValueError(f"{what}: cfg has no {key!r} block")
+    cfg = config_from_mae_ast(_plain(c["model"]), _plain(c["task"]))
+    return cfg, mae_ast_hot_path(what, cfg, ckpt["model"])
+
+
+def mae_ast_cfg_blocks(cfg: EncoderConfig) -> Dict:
+    """``checkpoint["cfg"]`` of a ``family="mae_ast"`` configuration: every field of ``MAE_AST_Config`` (the reference builds a
+    ``SimpleNamespace`` from the dict, so a missing one is an AttributeError) and the task fields the model and the expert read."""
+    model = dict(ast_kernel_size_chan=cfg.ma_kc, ast_kernel_size_time=cfg.ma_kt, ast_kernel_stride_chan=cfg.ma_stride_c,
+                 ast_kernel_stride_time=cfg.ma_stride_t, encoder_layers=cfg.encoder_layers, encoder_embed_dim=cfg.encoder_embed_dim,
+                 encoder_ffn_embed_dim=cfg.encoder_ffn_embed_dim, encoder_attention_heads=cfg.encoder_attention_heads,
+                 activation_fn=cfg.ma_activation, layer_norm_first=cfg.layer_norm_first, feature_grad_mult=1.0,
+                 use_post_enc_proj=False, decoder_embed_dim=cfg.encoder_embed_dim, decoder_layers=cfg.ma_decoder_layers,
+                 decoder_layerdrop=0.0, dropout=0.1, attention_dropout=0.1, activation_dropout=0.0, encoder_layerdrop=0.0,
+                 dropout_input=0.0, random_mask_prob=0.75, mask_length=10, mask_selection="static", mask_other=0,
+                 no_mask_overlap=False, mask_min_space=0, conv_pos=128, conv_pos_groups=16, checkpoint_activations=False,
+                 max_token_length=cfg.ma_max_token_length, enc_sine_pos=cfg.ma_enc_sine_pos, enc_conv_pos=cfg.ma_enc_conv_pos,
+                 dec_sine_pos=cfg.ma_dec_sine_pos, dec_conv_pos=False)
+    task = dict(feature_dim=cfg.ma_feature_dim, sample_rate=cfg.ma_sample_rate, feature_rate=100, feature_type="fbank",
+                mask_type="random_mask" if cfg.ma_kc == 128 else "chunk_patch")
+    return dict(model=model, task=task)
+
+
 def load_decoar_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
     """``{"model": state_dict}`` (upstream/decoar/expert.py:30-36; decoar_layers/expert.py:30-47 reads the same file and renames
     ``{forward,backward}_lstm.X_lN`` to its per-layer modules).  The file carries no configuration — the reference's ``Decoar()``
@@ -316,6 +381,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_vggish_checkpoint(ckpt)
     if family == "byol_a":
         return load_byol_a_checkpoint(ckpt)
+    if family == "mae_ast":
+        return load_mae_ast_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -369,6 +436,11 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
         return
     if cfg.family == "decoar":  # upstream/decoar/expert.py:30-36
         torch.save({"model": sd}, path)
+        return
+    if cfg.family == "mae_ast":  # upstream/mae_ast/expert.py:28-38
+        if "batch_norm.num_batches_tracked" in sd:
+            sd["batch_norm.num_batches_tracked"] = sd["batch_norm.num_batches_tracked"].to(torch.int64).reshape(())
+        torch.save({"cfg": mae_ast_cfg_blocks(cfg), "model": sd}, path)
         return
     if cfg.family == "byol_a":  # upstream/byol_a/byol_a.py:58-80: a plain state dict
         torch.save(sd, path)

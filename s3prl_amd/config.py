@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -215,6 +215,24 @@ class EncoderConfig:
     ba_norm_std: float = 5.0389895
     ba_bn_eps: float = 1e-5           # nn.BatchNorm2d's default
 
+    # MAE-AST (family "mae_ast", upstream/mae_ast/{expert,mae_ast}.py): a kaldi log-mel front end at 128 bins, eval BatchNorm2d(1) x 0.5,
+    # nn.Unfold into ``ma_kt`` x ``ma_kc`` patches, Linear, the checkpoint's sinusoidal position rows, ``encoder_layers`` Transformer
+    # layers with key padding.  ``conv_layers`` = [(D, 400, 160)] carries the frame geometry; the states are ``encoder_layers`` x
+    # (B, F // kt, (128 // kc) * D): the layer outputs, not the embedding.  The BatchNorm statistics are checkpoint tensors
+    ma_kt: int = 16                   # ast_kernel_size_time (= ast_kernel_stride_time)
+    ma_kc: int = 16                   # ast_kernel_size_chan (= ast_kernel_stride_chan)
+    ma_stride_t: int = 16             # ast_kernel_stride_time: anything but the kernel is refused
+    ma_stride_c: int = 16             # ast_kernel_stride_chan
+    ma_feature_dim: int = 128         # task.feature_dim (the reference's mask rule hard-codes 128)
+    ma_sample_rate: int = 16000       # task.sample_rate
+    ma_bn_eps: float = 1e-5           # nn.BatchNorm2d's default
+    ma_max_token_length: int = 48000  # rows of the checkpoint's sinusoidal tables
+    ma_enc_sine_pos: bool = True      # enc_sine_pos (False is refused: no released checkpoint)
+    ma_enc_conv_pos: bool = False     # enc_conv_pos (True is refused)
+    ma_activation: str = "gelu"       # activation_fn (anything else is refused)
+    ma_decoder_layers: int = 2        # the decoder is in the strict state dict and never runs
+    ma_dec_sine_pos: bool = True
+
     # ---- derived -------------------------------------------------------------------------
     @property
     def conv_dim(self) -> int:
@@ -234,12 +252,16 @@ class EncoderConfig:
         feat_final + every layer output + the prediction heads (distiller/expert.py:43-52)."""
         if self.family == "multires_hubert":  # every block: its layer inputs + its output (multires_hubert/expert.py:49-91)
             return sum(n + 1 for n in self.block_layers)
+        if self.family == "mae_ast":  # the layer outputs; the embedding is not among them (mae_ast.py:671-677)
+            return self.encoder_layers
         return self.encoder_layers + 1 + self.pred_heads
 
     @property
     def downsample_rate(self) -> int:
         if self.family == "vggish":  # vggish/expert.py:21-22 (the examples are 15360 samples apart; the reference says 16000)
             return 16000
+        if self.family == "mae_ast":  # mae_ast/expert.py:57-58
+            return self.ma_kt * 160
         r = 1
         for _, _, s in self.conv_layers:
             r *= s
@@ -259,6 +281,8 @@ class EncoderConfig:
             return 1 + n // 160 if n > 200 else 0
         if self.family == "decoar":  # ceil(fbank frames / subsample)
             return -(-self.conv_lengths(n)[-1] // self.decoar_subsample)
+        if self.family == "mae_ast":  # time steps of kt frames; the frames behind the last whole step are dropped by nn.Unfold
+            return self.conv_lengths(n)[-1] // self.ma_kt
         if self.family == "byol_a":  # segments: len(range(0, n, stride)) (byol_a/expert.py:85)
             return -(-n // self.conv_layers[0][2]) if n > 0 else 0
         if self.family == "vggish":  # examples: complete groups of vg_example_frames un-padded frames (audio.py:90-111)
@@ -277,6 +301,8 @@ class EncoderConfig:
         T = self.num_frames(n_max)
         if T <= 0:
             return 0
+        if self.family == "mae_ast":  # forward_padding_mask (mae_ast.py:305-325): a step that is only partly real counts as real
+            return min(T, max(-(-self.conv_lengths(length)[-1] // self.ma_kt), 0))
         if self.family == "mockingjay" and self.mj_frontend == "mel":
             # preprocessor.py:204-205: batch-dependent, Python floats and Python's round; without CMVN no feature row is zero
             return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
@@ -395,6 +421,8 @@ class EncoderConfig:
             return self._validate_vggish()
         if self.family == "byol_a":
             return self._validate_byol_a()
+        if self.family == "mae_ast":
+            return self._validate_mae_ast()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -614,6 +642,52 @@ class EncoderConfig:
             raise ValueError("byol_a norm_std and bn_eps must be positive")
         if self.encoder_embed_dim != d or self.encoder_layers != 0:
             raise ValueError("byol_a: encoder_embed_dim must be feature_d and encoder_layers 0 (byol_a_config sets them)")
+
+    @property
+    def ma_tokens_per_step(self) -> int:
+        """V = feature_dim // kc: tokens per time step, and state rows are V * D wide (mae_ast/expert.py:51-53,94)."""
+        return self.ma_feature_dim // self.ma_kc
+
+    @property
+    def ma_pos_rows(self) -> int:
+        """Leading rows of ``enc_sine_pos_embed.pe`` that travel to the device."""
+        return min(self.ma_max_token_length, 8192)
+
+    def ma_key_counts(self, lengths) -> List[int]:
+        """``kv_b = min(ceil(F_b / kt) * V, Ttok)`` of a batch (forward_padding_mask, mae_ast.py:305-325)."""
+        V, Ttok = self.ma_tokens_per_step, self.num_frames(max(lengths)) * self.ma_tokens_per_step
+        return [min(-(-self.conv_lengths(n)[-1] // self.ma_kt) * V, Ttok) for n in lengths]
+
+    def _validate_mae_ast(self) -> None:
+        """What the HIP path builds of MAE-AST; everything else is refused by name (s3enc_create_mae_ast repeats what it can see)."""
+        D, H = self.encoder_embed_dim, self.encoder_attention_heads
+        if self.ma_enc_conv_pos:
+            raise ValueError("mae_ast enc_conv_pos=True is not built (no released checkpoint uses the convolutional position embedding)")
+        if not self.ma_enc_sine_pos:
+            raise ValueError("mae_ast enc_sine_pos=False is not built (the released checkpoints add the sinusoidal table)")
+        if (self.ma_stride_t, self.ma_stride_c) != (self.ma_kt, self.ma_kc):
+            raise ValueError(f"mae_ast kernel stride ({self.ma_stride_t}, {self.ma_stride_c}) must equal the kernel size "
+                             f"({self.ma_kt}, {self.ma_kc}) on both axes")
+        if self.ma_feature_dim != 128:
+            raise ValueError(f"mae_ast feature_dim must be 128 (the reference's padding-mask rule hard-codes 128 mel bins), got {self.ma_feature_dim}")
+        if self.ma_kc not in (16, 32, 64, 128):
+            raise ValueError(f"mae_ast ast_kernel_size_chan must be 16, 32, 64 or 128 (the patch kernel's set), got {self.ma_kc}")
+        if not 1 <= self.ma_kt <= 32:
+            raise ValueError(f"mae_ast ast_kernel_size_time must be 1..32 (the patch kernel's set), got {self.ma_kt}")
+        if self.ma_sample_rate != 16000:
+            raise ValueError(f"mae_ast sample_rate must be 16000, got {self.ma_sample_rate}")
+        if H < 1 or D != 64 * H:
+            raise ValueError(f"mae_ast encoder_embed_dim / encoder_attention_heads must be 64 (the attention kernel's head width), got {D} / {H}")
+        if self.ma_activation != "gelu":
+            raise ValueError(f"mae_ast activation_fn={self.ma_activation!r} is not built: only 'gelu'")
+        if self.encoder_layers < 1:
+            raise ValueError("mae_ast encoder_layers must be positive")
+        if self.encoder_ffn_embed_dim % 4 or self.encoder_ffn_embed_dim < 4:
+            raise ValueError("mae_ast encoder_ffn_embed_dim must be a multiple of 4")
+        if self.ma_max_token_length < 1 or not self.ma_bn_eps > 0:
+            raise ValueError("mae_ast max_token_length and the BatchNorm eps must be positive")
+        if self.conv_layers != [(D, 400, 160)]:
+            raise ValueError("mae_ast: conv_layers carries the frame geometry as one (D, 400, 160) entry (mae_ast_config sets it)")
 
     def _validate_decoar(self) -> None:
         """What the HIP path builds of DeCoAR; everything else is refused by name (s3enc_create_decoar repeats it)."""
@@ -889,6 +963,38 @@ def byol_a_config(feature_d: int = 2048, window_secs: float = 1.0, stride_secs: 
                         encoder_embed_dim=int(feature_d), ba_window_secs=float(window_secs), ba_stride_secs=float(stride_secs), **flags)
     cfg.validate()
     return cfg
+
+
+def mae_ast_config(kt: int = 16, kc: int = 16, embed_dim: int = 768, layers: int = 12, heads: int = 12, ffn: int = 3072,
+                   layer_norm_first: bool = False, max_token_length: int = 48000, stride_t: int = None, stride_c: int = None,
+                   feature_dim: int = 128, sample_rate: int = 16000, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "mae_ast" (mae_ast/mae_ast.py:35-199; the defaults are ``mae_ast_patch``)."""
+    cfg = EncoderConfig(family="mae_ast", conv_layers=[(int(embed_dim), 400, 160)], encoder_layers=int(layers),
+                        encoder_embed_dim=int(embed_dim), encoder_ffn_embed_dim=int(ffn), encoder_attention_heads=int(heads),
+                        layer_norm_first=bool(layer_norm_first), ma_kt=int(kt), ma_kc=int(kc),
+                        ma_stride_t=int(kt if stride_t is None else stride_t), ma_stride_c=int(kc if stride_c is None else stride_c),
+                        ma_feature_dim=int(feature_dim), ma_sample_rate=int(sample_rate), ma_max_token_length=int(max_token_length),
+                        **flags)
+    cfg.validate()
+    return cfg
+
+
+def config_from_mae_ast(model_cfg: Dict, task_cfg: Dict) -> EncoderConfig:
+    """``checkpoint["cfg"]["model"]`` / ``["task"]`` of an MAE-AST file (mae_ast/expert.py:28-50); a missing model key takes the
+    default of ``MAE_AST_Config``."""
+    m, t = dict(model_cfg), dict(task_cfg)
+    for key in ("feature_dim", "sample_rate"):
+        if key not in t:
+            raise ValueError(f"mae_ast checkpoint: cfg.task has no {key!r}")
+    kt, kc = int(m.get("ast_kernel_size_time", 16)), int(m.get("ast_kernel_size_chan", 16))
+    return mae_ast_config(kt=kt, kc=kc, embed_dim=m.get("encoder_embed_dim", 768), layers=m.get("encoder_layers", 12),
+                          heads=m.get("encoder_attention_heads", 12), ffn=m.get("encoder_ffn_embed_dim", 3072),
+                          layer_norm_first=m.get("layer_norm_first", False), max_token_length=m.get("max_token_length", 48000),
+                          stride_t=m.get("ast_kernel_stride_time", 16), stride_c=m.get("ast_kernel_stride_chan", 16),
+                          feature_dim=t["feature_dim"], sample_rate=t["sample_rate"],
+                          ma_enc_sine_pos=bool(m.get("enc_sine_pos", False)), ma_enc_conv_pos=bool(m.get("enc_conv_pos", False)),
+                          ma_activation=str(m.get("activation_fn", "gelu")), ma_decoder_layers=int(m.get("decoder_layers", 2)),
+                          ma_dec_sine_pos=bool(m.get("dec_sine_pos", False)))
 
 
 def decoar_config(hidden: int = 1024, num_layers: int = 4, per_layer: bool = False, feat_dim: int = 80, subsample: int = 1,

@@ -155,7 +155,7 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 12) return fail("config: unknown family");
+    if (c.family < 0 || c.family > 13) return fail("config: unknown family");
     if (c.family == S3ENC_WAV2VEC) return 0;  // s3enc_create_ex: wav2vec_check_config on both configuration blocks
     if (c.family == S3ENC_CPC) return 0;      // s3enc_create_cpc: cpc_check_config on both configuration blocks
     if (c.family == S3ENC_APC) return 0;      // s3enc_create_apc: apc_check_config on both configuration blocks
@@ -164,6 +164,7 @@ int check_config(const s3enc_config& c) {
     if (c.family == S3ENC_NPC) return 0;         // s3enc_create_npc: npc_check_config on both configuration blocks
     if (c.family == S3ENC_VGGISH) return 0;      // s3enc_create_vggish: vggish_check_config on both configuration blocks
     if (c.family == S3ENC_BYOL_A) return 0;      // s3enc_create_byol_a: byol_a_check_config on both configuration blocks
+    if (c.family == S3ENC_MAE_AST) return 0;     // s3enc_create_mae_ast: mae_ast_check_config on both configuration blocks
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
         const int k = c.mr_kernel;
@@ -248,6 +249,7 @@ static int wrong_entry(const char* entry, int own, int family) {
         {S3ENC_NPC, "npc", "S3ENC_NPC", "s3enc_create_npc", "the NPC family needs its front-end / convolution block"},
         {S3ENC_VGGISH, "vggish", "S3ENC_VGGISH", "s3enc_create_vggish", "the VGGish family needs its front-end / layer block"},
         {S3ENC_BYOL_A, "byol_a", "S3ENC_BYOL_A", "s3enc_create_byol_a", "the BYOL-A family needs its segment block"},
+        {S3ENC_MAE_AST, "mae_ast", "S3ENC_MAE_AST", "s3enc_create_mae_ast", "the MAE-AST family needs its patch / BatchNorm block"},
     };
     if (family == own) return 0;
     for (const auto& f : F)
@@ -268,8 +270,8 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
                        const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_decoar_config* dc,
-                       const s3enc_npc_config* npc, const s3enc_vggish_config* vg, const s3enc_byol_a_config* ba, const s3enc_tensor* tensors,
-                       int32_t n_tensors, int32_t device, s3enc_handle* out);
+                       const s3enc_npc_config* npc, const s3enc_vggish_config* vg, const s3enc_byol_a_config* ba, const s3enc_mae_ast_config* ma,
+                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
 
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out) {
@@ -277,7 +279,7 @@ int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, co
         if (out) *out = nullptr;
         return 1;
     }
-    return create_impl(cfg, w2v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, w2v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -285,7 +287,7 @@ int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const
     if (!cfg || !cpc || !tensors || !out) return fail("s3enc_create_cpc: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_cpc", S3ENC_CPC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, cpc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, cpc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -293,7 +295,7 @@ int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const
     if (!cfg || !apc || !tensors || !out) return fail("s3enc_create_apc: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_apc", S3ENC_APC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, apc, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, apc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -301,7 +303,7 @@ int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_conf
     if (!cfg || !mj || !tensors || !out) return fail("s3enc_create_mockingjay: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_mockingjay", S3ENC_MOCKINGJAY, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, mj, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, nullptr, mj, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* decoar, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -309,7 +311,7 @@ int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* deco
     if (!cfg || !decoar || !tensors || !out) return fail("s3enc_create_decoar: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_decoar", S3ENC_DECOAR, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, decoar, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, decoar, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_npc(const s3enc_config* cfg, const s3enc_npc_config* npc, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -317,7 +319,7 @@ int s3enc_create_npc(const s3enc_config* cfg, const s3enc_npc_config* npc, const
     if (!cfg || !npc || !tensors || !out) return fail("s3enc_create_npc: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_npc", S3ENC_NPC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, npc, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, npc, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_vggish(const s3enc_config* cfg, const s3enc_vggish_config* vggish, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -325,7 +327,7 @@ int s3enc_create_vggish(const s3enc_config* cfg, const s3enc_vggish_config* vggi
     if (!cfg || !vggish || !tensors || !out) return fail("s3enc_create_vggish: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_vggish", S3ENC_VGGISH, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, vggish, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, vggish, nullptr, nullptr, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_byol_a(const s3enc_config* cfg, const s3enc_byol_a_config* byol_a, const s3enc_tensor* tensors, int32_t n_tensors,
@@ -333,13 +335,21 @@ int s3enc_create_byol_a(const s3enc_config* cfg, const s3enc_byol_a_config* byol
     if (!cfg || !byol_a || !tensors || !out) return fail("s3enc_create_byol_a: null argument");
     *out = nullptr;
     if (wrong_entry("s3enc_create_byol_a", S3ENC_BYOL_A, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, byol_a, tensors, n_tensors, device, out);
+    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, byol_a, nullptr, tensors, n_tensors, device, out);
+}
+
+int s3enc_create_mae_ast(const s3enc_config* cfg, const s3enc_mae_ast_config* mae_ast, const s3enc_tensor* tensors, int32_t n_tensors,
+                         int32_t device, s3enc_handle* out) {
+    if (!cfg || !mae_ast || !tensors || !out) return fail("s3enc_create_mae_ast: null argument");
+    *out = nullptr;
+    if (wrong_entry("s3enc_create_mae_ast", S3ENC_MAE_AST, cfg->family)) return 1;
+    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mae_ast, tensors, n_tensors, device, out);
 }
 
 static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
                        const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_decoar_config* dc,
-                       const s3enc_npc_config* npc, const s3enc_vggish_config* vg, const s3enc_byol_a_config* ba, const s3enc_tensor* tensors,
-                       int32_t n_tensors, int32_t device, s3enc_handle* out) {
+                       const s3enc_npc_config* npc, const s3enc_vggish_config* vg, const s3enc_byol_a_config* ba, const s3enc_mae_ast_config* ma,
+                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
@@ -354,6 +364,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         case S3ENC_NPC: if (npc_check_config(*cfg, *npc)) return 1; break;
         case S3ENC_VGGISH: if (vggish_check_config(*cfg, *vg)) return 1; break;
         case S3ENC_BYOL_A: if (byol_a_check_config(*cfg, *ba)) return 1; break;
+        case S3ENC_MAE_AST: if (mae_ast_check_config(*cfg, *ma)) return 1; break;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -384,6 +395,7 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
         case S3ENC_NPC: e->npc_cfg = *npc; family_rc = npc_create(e.get(), ck); break;
         case S3ENC_VGGISH: e->vggish_cfg = *vg; family_rc = vggish_create(e.get(), ck); break;
         case S3ENC_BYOL_A: e->byol_a_cfg = *ba; family_rc = byol_a_create(e.get(), ck); break;
+        case S3ENC_MAE_AST: e->mae_ast_cfg = *ma; family_rc = mae_ast_create(e.get(), ck); break;
     }
     if (family_rc >= 0) return family_rc ? 1 : finish_create(std::move(e), out);
     const s3enc_config& c = e->cfg;
@@ -818,6 +830,10 @@ int s3enc_num_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
         *T = (int32_t)byol_a_num_segments(h->byol_a_cfg, n_samples);
         return 0;
     }
+    if (h->cfg.family == S3ENC_MAE_AST) {  // time steps of kt frames: a state row is the V tokens of one step
+        *T = (int32_t)mae_ast_num_steps(h->mae_ast_cfg, n_samples);
+        return 0;
+    }
     *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
                                               : conv_len(h->cfg, n_samples, h->cfg.n_conv));
     return 0;
@@ -840,6 +856,10 @@ int s3enc_num_output_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
         *T = (int32_t)byol_a_num_segments(h->byol_a_cfg, n_samples);
         return 0;
     }
+    if (h->cfg.family == S3ENC_MAE_AST) {  // time steps of kt frames: a state row is the V tokens of one step
+        *T = (int32_t)mae_ast_num_steps(h->mae_ast_cfg, n_samples);
+        return 0;
+    }
     *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
                                               : output_frames(h->cfg, n_samples));
     return 0;
@@ -848,6 +868,7 @@ int s3enc_downsample_rate(s3enc_handle h, int32_t* rate) {
     if (!h || !rate) return fail("s3enc_downsample_rate: null argument");
     int r = 1;
     for (int i = 0; i < h->cfg.n_conv; ++i) r *= h->cfg.conv_stride[i];
+    if (h->cfg.family == S3ENC_MAE_AST) r = h->mae_ast_cfg.kt * 160;  // mae_ast/expert.py:57-58
     if (h->cfg.family == S3ENC_BYOL_A) r = h->byol_a_cfg.stride;  // byol_a/expert.py:64-65: int(stride_secs * 16000)
     if (h->cfg.family == S3ENC_VGGISH) r = 16000;  // vggish/expert.py:21-22 (the examples are 15360 samples apart; the reference says 16000)
     *rate = r;
@@ -868,6 +889,10 @@ int s3enc_valid_frames(s3enc_handle h, int64_t length, int64_t n_max, int32_t* v
     if (h->cfg.family == S3ENC_DECOAR) {  // the utterance's own frame count (its packed length)
         const long T = decoar_num_frames(h->cfg, h->decoar_cfg, n_max), v = decoar_num_frames(h->cfg, h->decoar_cfg, length);
         *valid = (int32_t)(T <= 0 ? 0 : std::max(0L, std::min(v, T)));
+        return 0;
+    }
+    if (h->cfg.family == S3ENC_MAE_AST) {  // forward_padding_mask: a step that is only partly real counts as real
+        *valid = (int32_t)mae_ast_valid_steps(h->mae_ast_cfg, length, n_max);
         return 0;
     }
     if (h->cfg.family == S3ENC_BYOL_A) {  // the utterance's own segments; the rows behind them are the reference's values, not zeros
@@ -1156,6 +1181,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         case S3ENC_NPC: return npc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
         case S3ENC_VGGISH: return vggish_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
         case S3ENC_BYOL_A: return byol_a_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
+        case S3ENC_MAE_AST: return mae_ast_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     }
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
@@ -1912,6 +1938,11 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
         return fail("s3enc_num_states: feature_selection is not defined for VGGish (one hidden_states list)");
     if (h->cfg.family == S3ENC_BYOL_A && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: feature_selection is not defined for BYOL-A (one hidden_states list)");
+    if (h->cfg.family == S3ENC_MAE_AST) {
+        if (selection != S3ENC_SEL_HIDDEN) return fail("s3enc_num_states: feature_selection is not defined for MAE-AST (one hidden_states list)");
+        *n = h->cfg.encoder_layers;  // the layer outputs; the embedding is not among them (mae_ast.py:671-677)
+        return 0;
+    }
     *n = num_states(h->cfg, selection);
     return 0;
 }

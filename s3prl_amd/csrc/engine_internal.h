@@ -11,6 +11,7 @@
 //   npc.hip     NPC: the log-mel front end, ConvBlocks and masked convolutions on convtaps.hip's two-run implicit GEMM
 //   vggish.hip  VGGish: the un-padded log-mel examples, the 3 x 3 conv + pool stack on conv2d.hip, three Linears, the quantiser
 //   byol_a.hip  BYOL-A: per-segment FFT log-mel (melspec.hip), conv + BatchNorm + floor-pool on conv2d.hip, two Linears, max + mean
+//   mae_ast.hip MAE-AST: per-utterance kaldi fbank, the fused patch embedding (patchembed.hip), pre- / post-LN Transformer layers
 //   (a family file holds its configuration check, its weights and its forward schedule: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
 #pragma once
@@ -457,6 +458,13 @@ struct MjW {
     std::vector<MjLayerW> layers;
 };
 
+// MAE-AST (mae_ast.hip): the patch Linear with the eval BatchNorm folded in (W' = s W, b' = b - s mean rowsum(W)), the leading rows
+// of the checkpoint's own sinusoidal table, encoder.layer_norm (post-LN only) and the layers as Mockingjay's struct holds them
+struct MaeAstW {
+    DevBuf pw, pb, pos, eln_g, eln_b;
+    std::vector<MjLayerW> layers;
+};
+
 struct ProfRec {
     int kind;
     hipEvent_t a, b;
@@ -527,6 +535,8 @@ struct s3enc_encoder {
     s3enc_vggish_config vggish_cfg = {};  // ... and its second configuration block (s3enc_create_vggish)
     std::unique_ptr<ByolAW> byol_a;     // S3ENC_BYOL_A
     s3enc_byol_a_config byol_a_cfg = {};  // ... and its second configuration block (s3enc_create_byol_a)
+    std::unique_ptr<MaeAstW> mae_ast;   // S3ENC_MAE_AST
+    s3enc_mae_ast_config mae_ast_cfg = {};  // ... and its second configuration block (s3enc_create_mae_ast)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -840,6 +850,14 @@ int byol_a_create(s3enc_encoder* e, const Ckpt& ck);
 long byol_a_num_segments(const s3enc_byol_a_config& x, long n_samples);  // len(range(0, n, stride))
 int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+// mae_ast.hip: the S3ENC_MAE_AST family (kaldi fbank at 128 bins -> fused patch embedding + position rows -> Transformer layers with
+// key padding; rows behind an utterance's valid count are the reference's values, queries over the live keys)
+int mae_ast_check_config(const s3enc_config& c, const s3enc_mae_ast_config& x);
+int mae_ast_create(s3enc_encoder* e, const Ckpt& ck);
+long mae_ast_num_steps(const s3enc_mae_ast_config& x, long n_samples);                 // F(n) / kt
+long mae_ast_valid_steps(const s3enc_mae_ast_config& x, long length, long n_max);      // min(ceil(F(length) / kt), F(n_max) / kt)
+int mae_ast_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
 // mockingjay.hip: the S3ENC_MOCKINGJAY family (spectrogram front end + input representation + post-LN BERT layers, chunked)
 int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x);
 int mj_create(s3enc_encoder* e, const Ckpt& ck);

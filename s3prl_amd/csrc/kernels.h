@@ -97,6 +97,9 @@ struct Tuning {
                            // 128-wide tile, half of whose MFMA columns are then padding (bit-identical; the A/B of profiles/byol_a_fp32.md)
     int melspec_fft = 1;   // melspec.hip: 1 = the 1024-point STFT as a real FFT in LDS, one workgroup per frame; 0 = the overlapping-row GEMM
                            // against the folded hann x DFT matrix (fbank.hip's form at K = 1024: the yardstick and the fallback)
+    int patch_embed_fused = 1;  // patchembed.hip: 1 = the patch embedding as ONE implicit GEMM that reads the image in place, 0 = a gather kernel
+                           // that writes the (B * tokens, kt * kc) rows, the tile GEMM, then the position add (the yardstick and a second
+                           // implementation, held to the fixture bound; the A/B of profiles/mae_ast_fp32.md)
     int comm_self_p2p = 0; // comm.hip, S3ENC_EXCHANGE_DIRECT: 1 = a rank's OWN block also travels as an ncclSend-to-self / ncclRecv-from-self
                            // pair inside the state's group instead of a device copy — on a one-GPU box this is the only way the
                            // all-pairs code (symbols, counts, datatype, group bracketing, stream order behind the layer events)
@@ -255,6 +258,27 @@ struct Conv2dParams {
 void pack_conv2d3x3(const float* w, int N, int C, std::vector<float>& out);  // host: nn.Conv2d's (N, C, 3, 3) -> the kernel's image
 const char* conv2d3x3_refusal(const Conv2dParams& p);  // null, or why launch_conv2d3x3 would refuse
 hipError_t launch_conv2d3x3(const Conv2dParams& p, hipStream_t stream);
+
+// patchembed.hip: exact-fp32 patch embedding of (frames, 128) images as an implicit GEMM over the tokens of all utterances (MAE-AST's
+// nn.Unfold((kt, kc), stride = kernel) + Linear + position row): token t * V + v of utterance b is the kt x kc patch at image row
+// t * kt, column v * kc, V = 128 / kc, its content in (time, channel) row-major order — the Linear's own K order.
+struct PatchEmbedParams {
+    const float* img;   // utterance b at img + b * img_bs: rows of 128 floats; rows at or past Tt * kt are never read
+    long img_bs;        // floats, a multiple of 4, at least Tt * kt * 128
+    const float* W;     // (N, kt * kc) row-major
+    const float* bias;  // [N] or null
+    const float* pos;   // (>= Tt * V, N) or null: row m is added to token m of utterance b where m < kv[b]
+    const int* kv;      // device [B], with pos
+    int B, Tt, kt, kc, N;
+    int vshift, sshift;  // log2(128 / kc), log2(kc / 16): patch_embed_geometry fills them
+    float* out;         // (B, Tt * V, N) contiguous
+};
+void patch_embed_geometry(PatchEmbedParams& p);            // vshift / sshift from kc (0 / 0 for a kc the kernel refuses)
+const char* patch_embed_refusal(const PatchEmbedParams& p);  // null, or why launch_patch_embed would refuse
+hipError_t launch_patch_embed(const PatchEmbedParams& p, hipStream_t stream);
+// the two-step form: a gather into `rows` (patch_embed_rows_elems floats, 16-byte aligned), launch_gemm, the position add
+size_t patch_embed_rows_elems(const PatchEmbedParams& p);
+hipError_t launch_patch_embed_two_step(const PatchEmbedParams& p, float* rows, hipStream_t stream);
 
 // ---- frontend.hip ---------------------------------------------------------------------------------------
 // Waveform table: wav b is `ptrs[b]` with `lens[b]` valid samples; reads beyond are zeros (the padding).

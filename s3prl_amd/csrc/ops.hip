@@ -28,6 +28,7 @@ int tuning_set(Tuning& t, const char* key, int value, const char** err) {
         {"conv0_fast", &Tuning::conv0_fast, 0, 1},           {"conv_f22", &Tuning::conv_f22, 0, 1},
         {"rnn_split", &Tuning::rnn_split, -1, 8},           {"npc_skip_taps", &Tuning::npc_skip_taps, 0, 1},
         {"conv2d_n64", &Tuning::conv2d_n64, 0, 1},           {"melspec_fft", &Tuning::melspec_fft, 0, 1},
+        {"patch_embed_fused", &Tuning::patch_embed_fused, 0, 1},
         {"gemm32_tail", &Tuning::gemm32_tail, 0, 2},         {"gemm32_tail_units", &Tuning::gemm32_tail_units, 0, 1 << 20},
     };
     static thread_local char msg[160];
@@ -617,6 +618,40 @@ int s3enc_op_melspec1024(const float* segments, int32_t nseg, int32_t L, float* 
     }
     HIP_TRY(launch_melspec(p, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the tables and the scratch are freed on return
+    return 0;
+}
+
+int s3enc_op_patch_embed(const float* img, int64_t img_bs, const float* w_host, const float* bias, const float* pos, const int32_t* kv,
+                         int32_t B, int32_t Tt, int32_t kt, int32_t kc, int32_t N, float* out, void* stream) {
+    if (!img || !w_host || !out) return fail("s3enc_op_patch_embed: null argument");
+    if (B <= 0 || Tt <= 0 || N <= 0) return fail("s3enc_op_patch_embed: bad shape");
+    PatchEmbedParams p{};
+    p.img = img;
+    p.img_bs = img_bs;
+    p.bias = bias;
+    p.pos = pos;
+    p.kv = kv;
+    p.B = B;
+    p.Tt = Tt;
+    p.kt = kt;
+    p.kc = kc;
+    p.N = N;
+    p.out = out;
+    patch_embed_geometry(p);
+    alignas(16) static float stand_in[4];  // the checks that need no device memory first
+    p.W = stand_in;
+    if (const char* why = patch_embed_refusal(p)) return fail(std::string("s3enc_op_patch_embed: ") + why);
+    std::vector<float> w(w_host, w_host + (size_t)N * kt * kc);
+    DevBuf dw, rows;
+    HIP_TRY(upload_f32(dw, w));
+    p.W = (const float*)dw.p;
+    if (tuning().patch_embed_fused) {
+        HIP_TRY(launch_patch_embed(p, (hipStream_t)stream));
+    } else {
+        HIP_TRY(rows.ensure(patch_embed_rows_elems(p) * 4 + 64));
+        HIP_TRY(launch_patch_embed_two_step(p, (float*)rows.p, (hipStream_t)stream));
+    }
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the weights and the gathered rows are freed on return
     return 0;
 }
 

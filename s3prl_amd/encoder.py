@@ -44,6 +44,12 @@ class HipEncoder:
             raise ValueError(f"VGGish is built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "byol_a" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             raise ValueError(f"BYOL-A is built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "mae_ast" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"MAE-AST is built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.family == "mae_ast":  # a full state dict is cut to what the handle reads (the position table to its leading rows)
+            from .ckpt import mae_ast_hot_path
+
+            weights = mae_ast_hot_path("the MAE-AST weights", cfg, weights)
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")
@@ -93,12 +99,17 @@ class HipEncoder:
             elif cfg.family == "byol_a":  # its segment geometry travels beside the (unchanged) s3enc_config
                 ba = _lib.make_byol_a_config(cfg)
                 rc = self._lib.s3enc_create_byol_a(C.byref(ccfg), C.byref(ba), tensors, len(weights), self.device, C.byref(h))
+            elif cfg.family == "mae_ast":  # its patch geometry and BatchNorm statistics travel beside the (unchanged) s3enc_config
+                ma = _lib.make_mae_ast_config(cfg, weights)
+                rc = self._lib.s3enc_create_mae_ast(C.byref(ccfg), C.byref(ma), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")
         self._h = h
         self.num_layers = cfg.encoder_layers
         self.embed_dim = cfg.encoder_embed_dim
+        if cfg.family == "mae_ast":  # a state row holds the V tokens of one time step (mae_ast/expert.py:94)
+            self.embed_dim = cfg.ma_tokens_per_step * cfg.encoder_embed_dim
         self._forwards = 0   # forwards issued / the last one known to have been judged by check_finite (error messages name the range)
         self._checked = 0
 
@@ -215,6 +226,16 @@ class HipEncoder:
             if min(self.cfg.conv_lengths(n)[-1] for n in lengths) < 2:
                 raise ValueError(f"an utterance of {min(lengths)} samples has fewer than 2 analysis windows (DeCoAR's front end "
                                  "normalises by the standard deviation over time: one frame has none)")
+        if self.cfg.family == "mae_ast":
+            for i, n in enumerate(lengths):
+                if n < 400:
+                    raise ValueError(f"utterance {i} has {n} samples, fewer than one 400-sample analysis window of the MAE-AST front end")
+            if self.cfg.conv_lengths(nm)[-1] < self.cfg.ma_kt:
+                raise ValueError(f"the batch has {self.cfg.conv_lengths(nm)[-1]} frames, fewer than one patch of {self.cfg.ma_kt} frames "
+                                 "(F_max < kt)")
+            if self.num_frames(nm) * self.cfg.ma_tokens_per_step > self.cfg.ma_pos_rows:
+                raise ValueError(f"the batch needs {self.num_frames(nm) * self.cfg.ma_tokens_per_step} position rows, the handle holds "
+                                 f"{self.cfg.ma_pos_rows} (the leading rows of the checkpoint's enc_sine_pos_embed.pe)")
         if self.cfg.family == "mockingjay" and self.cfg.mj_frontend == "mel" and min(lengths) <= 200:
             raise ValueError(f"an utterance of {min(lengths)} samples has no reflect-padded centred STFT frame (torch.stft refuses "
                              "n <= 200 samples)")

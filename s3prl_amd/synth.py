@@ -36,6 +36,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _vggish_shapes(cfg)
     if cfg.family == "byol_a":
         return _byol_a_shapes(cfg)
+    if cfg.family == "mae_ast":
+        return _mae_ast_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -272,6 +274,47 @@ def _byol_a_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     return s
 
 
+def _mae_ast_shapes(cfg: EncoderConfig, full: bool = False) -> Dict[str, tuple]:
+    """MAE_AST (upstream/mae_ast/mae_ast.py:202-281), reference state_dict names.  The hot path: the patch Linear, the BatchNorm's
+    running statistics, the leading ``ma_pos_rows`` rows of the encoder's sinusoidal table, ``encoder.layer_norm`` and the encoder
+    layers.  ``full``: the whole strict state dict — the table as ``(1, max_token_length, D)``, the decoder and its table, the
+    reconstruction / classification heads, the mask embeddings, ``LayerNorm(feature_dim)`` and ``num_batches_tracked``."""
+    D, F, K = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.ma_kt * cfg.ma_kc
+    s: Dict[str, tuple] = {"post_extract_proj.weight": (D, K), "post_extract_proj.bias": (D,)}
+    if full:
+        s["layer_norm.weight"], s["layer_norm.bias"] = (cfg.ma_feature_dim,), (cfg.ma_feature_dim,)
+    s["batch_norm.running_mean"], s["batch_norm.running_var"] = (1,), (1,)
+    if full:
+        s["batch_norm.num_batches_tracked"] = ()
+        s["encoder_mask_emb"] = (D,)
+    s["enc_sine_pos_embed.pe"] = (1, cfg.ma_max_token_length, D) if full else (cfg.ma_pos_rows, D)
+    for l in range(cfg.encoder_layers):
+        _layer_shapes(s, f"encoder.layers.{l}", D, F)
+    s["encoder.layer_norm.weight"], s["encoder.layer_norm.bias"] = (D,), (D,)
+    if full:
+        s["decoder_mask_emb"] = (D,)
+        if cfg.ma_dec_sine_pos:
+            s["dec_sine_pos_embed.pe"] = (1, cfg.ma_max_token_length, D)
+        for l in range(cfg.ma_decoder_layers):
+            _layer_shapes(s, f"decoder.layers.{l}", D, F)
+        s["decoder.layer_norm.weight"], s["decoder.layer_norm.bias"] = (D,), (D,)
+        for head in ("final_proj_reconstruction", "final_proj_classification"):
+            s[f"{head}.weight"], s[f"{head}.bias"] = (K, D), (K,)
+    return s
+
+
+def mae_ast_sine_table(rows: int, D: int) -> np.ndarray:
+    """``SinusoidalPositionalEncoding.pe`` (mae_ast.py:802-812) by the reference's float32 formula: ``(1, rows, D)``."""
+    import math
+
+    position = np.arange(rows, dtype=np.float32)[:, None]
+    div_term = np.exp(np.arange(0, D, 2).astype(np.float32) * np.float32(-math.log(10000.0) / D)).astype(np.float32)
+    pe = np.zeros((1, rows, D), dtype=np.float32)
+    pe[0, :, 0::2] = np.sin(position * div_term)
+    pe[0, :, 1::2] = np.cos(position * div_term)
+    return pe
+
+
 def _decoar_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     """Decoar (upstream/decoar/decoar.py:21-39), the checkpoint's names: the projection and the two multi-layer nn.LSTM modules
     (decoar_layers/expert.py:35-47 renames them to its per-layer modules; both experts read this one file)."""
@@ -430,10 +473,19 @@ VGGISH_EMB_MEAN = 1.0
 def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
     rng = np.random.default_rng(seed)
     out: Dict[str, np.ndarray] = {}
-    for name, shape in param_shapes(cfg).items():
+    # MAE-AST: the FULL strict state dict, so that the file a test writes is one the reference's expert loads
+    for name, shape in (_mae_ast_shapes(cfg, full=True) if cfg.family == "mae_ast" else param_shapes(cfg)).items():
         leaf = name.rsplit(".", 1)[-1]
         if name.endswith("relative_attention_bias.weight"):
             w = rng.standard_normal(shape) * 0.5
+        elif name.endswith("sine_pos_embed.pe"):
+            w = mae_ast_sine_table(shape[1], shape[2])
+        elif cfg.family == "mae_ast" and name.startswith("batch_norm."):
+            # running statistics at log-mel scale (an AudioSet-style normaliser): the fold moves the bias by s * mean * rowsum(W)
+            w = {"running_mean": lambda: -4.0 + 0.3 * rng.standard_normal(shape), "running_var": lambda: 20.0 + rng.uniform(-2.0, 2.0, size=shape),
+                 "num_batches_tracked": lambda: np.full(shape, 1000.0)}[leaf]()
+        elif name.endswith("_mask_emb"):
+            w = rng.uniform(0.0, 1.0, size=shape)
         elif name.startswith("gEncoder.batchNorm"):  # ChannelNorm (1, C, 1): gains 1 + 0.1 N(0, 1), shifts 0.05 N(0, 1)
             w = (1.0 if leaf == "weight" else 0.0) + (0.1 if leaf == "weight" else 0.05) * rng.standard_normal(shape)
         elif name.startswith("gEncoder.conv") and leaf == "weight":  # (out, in, k): unit variance in front of the channel norm
@@ -734,6 +786,21 @@ def named_config(name: str) -> EncoderConfig:
         from .config import byol_a_config
 
         return byol_a_config(**byol_a[name])
+    # MAE-AST: kaldi log-mel at 128 bins, kt x kc patches, sinusoidal positions, Transformer layers with key padding
+    tiny_ma = dict(embed_dim=128, layers=2, heads=2, ffn=256, max_token_length=640)
+    mae_ast = {
+        "mae_ast_patch": dict(kt=16, kc=16), "mae_ast_frame": dict(kt=2, kc=128),
+        # the released shapes with position tables of 1024 rows (the full-size fixtures: a 48000-row table is 147 MB a piece)
+        "mae_ast_patch_t1024": dict(kt=16, kc=16, max_token_length=1024), "mae_ast_frame_t1024": dict(kt=2, kc=128, max_token_length=1024),
+        "tiny_mae_ast": dict(kt=16, kc=16, **tiny_ma),
+        "tiny_mae_ast_frame": dict(kt=2, kc=128, **tiny_ma),
+        "tiny_mae_ast_preln": dict(kt=16, kc=16, **{**tiny_ma, "layers": 3}, layer_norm_first=True),
+        "tiny_mae_ast_k3x32": dict(kt=3, kc=32, **tiny_ma),
+    }
+    if name in mae_ast:
+        from .config import mae_ast_config
+
+        return mae_ast_config(**mae_ast[name])
     # Mockingjay / TERA / AudioALBERT: a log-mel (or kaldi fbank) front end into post-LN BERT layers, long inputs in chunks
     tiny_mj = dict(hidden=128, layers=2, heads=2, intermediate=256, input_dim=16, sequence_length=0)
     mj = {
@@ -756,7 +823,7 @@ def named_config(name: str) -> EncoderConfig:
 
         return mockingjay_config(**mj[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(byol_a) + list(mj))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(byol_a) + list(mae_ast) + list(mj))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
