@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Callable, NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libs3enc.so")
@@ -157,16 +158,7 @@ _PROTOS = {
     "s3enc_version": (C.c_int, []),
     "s3enc_last_error": (C.c_char_p, []),
     "s3enc_create": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
-    "s3enc_create_ex": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3Wav2vecConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
-    "s3enc_create_cpc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3CpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
-    "s3enc_create_apc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3ApcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
-    "s3enc_create_mockingjay": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3MockingjayConfig), C.POINTER(S3Tensor), _I32, _I32,
-                                          C.POINTER(_VP)]),
-    "s3enc_create_decoar": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3DecoarConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
-    "s3enc_create_npc": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3NpcConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
-    "s3enc_create_vggish": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3VggishConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
-    "s3enc_create_byol_a": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3ByolAConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
-    "s3enc_create_mae_ast": (C.c_int, [C.POINTER(S3Config), C.POINTER(S3MaeAstConfig), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)]),
+    # (s3enc_create_ex and the later s3enc_create_*: one per entry of BLOCK_FAMILIES, added below it)
     "s3enc_destroy": (C.c_int, [_VP]),
     "s3enc_num_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
     "s3enc_num_output_frames": (C.c_int, [_VP, _I64, C.POINTER(_I32)]),
@@ -478,3 +470,32 @@ def make_mae_ast_config(cfg, weights) -> S3MaeAstConfig:
     c.bn_mean, c.bn_var = as_float(weights["batch_norm.running_mean"]), as_float(weights["batch_norm.running_var"])
     c.bn_eps, c.pos_rows = float(cfg.ma_bn_eps), int(cfg.ma_pos_rows)
     return c
+
+
+class BlockFamily(NamedTuple):
+    """A family whose handle takes a second configuration block through a create entry of its own (csrc: its FamilyOps record)."""
+    block: type                  # the ctypes struct of the block
+    make: Callable               # its make_*_config: EncoderConfig (and the weights, with reads_weights) -> block
+    create: str                  # the create symbol that takes the block
+    built: str                   # who "is" / "are" built for compute dtype fp32 only, with the verb
+    reads_weights: bool = False  # make_*_config(cfg, weights)
+
+    def make_block(self, cfg, weights):
+        return self.make(cfg, weights) if self.reads_weights else self.make(cfg)
+
+
+# keyed as FAMILY; a family that is not here is created by s3enc_create from s3enc_config alone
+BLOCK_FAMILIES = {
+    "wav2vec": BlockFamily(S3Wav2vecConfig, make_wav2vec_config, "s3enc_create_ex", "wav2vec / vq-wav2vec are"),
+    "cpc": BlockFamily(S3CpcConfig, make_cpc_config, "s3enc_create_cpc", "modified CPC is"),
+    "apc": BlockFamily(S3ApcConfig, make_apc_config, "s3enc_create_apc", "APC / VQ-APC are"),
+    "mockingjay": BlockFamily(S3MockingjayConfig, make_mockingjay_config, "s3enc_create_mockingjay", "Mockingjay / TERA / AudioALBERT are"),
+    "decoar": BlockFamily(S3DecoarConfig, make_decoar_config, "s3enc_create_decoar", "DeCoAR is"),
+    "npc": BlockFamily(S3NpcConfig, make_npc_config, "s3enc_create_npc", "NPC is"),
+    "vggish": BlockFamily(S3VggishConfig, make_vggish_config, "s3enc_create_vggish", "VGGish is"),
+    "byol_a": BlockFamily(S3ByolAConfig, make_byol_a_config, "s3enc_create_byol_a", "BYOL-A is"),
+    "mae_ast": BlockFamily(S3MaeAstConfig, make_mae_ast_config, "s3enc_create_mae_ast", "MAE-AST is", reads_weights=True),
+}
+assert set(BLOCK_FAMILIES) <= set(FAMILY)
+_PROTOS.update({f.create: (C.c_int, [C.POINTER(S3Config), C.POINTER(f.block), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)])
+                for f in BLOCK_FAMILIES.values()})

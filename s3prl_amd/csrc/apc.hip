@@ -32,7 +32,7 @@ s3::FbankParams apc_fbank_params(const s3enc_apc_config& x) {
 }
 }  // namespace
 
-int apc_check_config(const s3enc_config& c, const s3enc_apc_config& x) {
+static int apc_check_config(const s3enc_config& c, const s3enc_apc_config& x) {
     static const char* dt[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
@@ -56,7 +56,7 @@ int apc_check_config(const s3enc_config& c, const s3enc_apc_config& x) {
     return 0;
 }
 
-int apc_create(s3enc_encoder* e, const Ckpt& ck) {
+static int apc_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_apc_config& x = e->apc_cfg;
     e->apc.reset(new ApcW());
     for (int l = 0; l < x.num_layers; ++l)
@@ -64,7 +64,7 @@ int apc_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const s3enc_apc_config& x = e->apc_cfg;
     const ApcW& w = *e->apc;
@@ -185,5 +185,14 @@ int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     }
     return 0;
 }
+
+
+// frames, mask rule and rate are those of its one-layer "conv stack" (window, hop): valid_frames counts an utterance's own whole windows
+FamilyOps kApcFamily = {
+    S3ENC_APC, "apc", "S3ENC_APC", "s3enc_create_apc", "the APC family needs its front-end / GRU block",
+    "APC (one hidden_states list of 3 states)",
+    [](const s3enc_config& c, const void* b) { return apc_check_config(c, *(const s3enc_apc_config*)b); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->apc_cfg = *(const s3enc_apc_config*)b; return apc_create(e, ck); },
+    apc_forward};
 
 }  // namespace s3e

@@ -48,11 +48,11 @@ const int kConvIdx[3] = {0, 4, 8};  // the Conv2d modules of the reference's nn.
 
 }  // namespace
 
-long byol_a_num_segments(const s3enc_byol_a_config& x, long n_samples) {
+static long byol_a_num_segments(const s3enc_byol_a_config& x, long n_samples) {
     return n_samples < 1 ? 0 : (n_samples + x.stride - 1) / x.stride;  // len(range(0, n, stride))
 }
 
-int byol_a_check_config(const s3enc_config& c, const s3enc_byol_a_config& x) {
+static int byol_a_check_config(const s3enc_config& c, const s3enc_byol_a_config& x) {
     static const char* dt[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
@@ -77,7 +77,7 @@ int byol_a_check_config(const s3enc_config& c, const s3enc_byol_a_config& x) {
     return 0;
 }
 
-int byol_a_create(s3enc_encoder* e, const Ckpt& ck) {
+static int byol_a_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_byol_a_config& x = e->byol_a_cfg;
     e->byol_a.reset(new ByolAW());
     ByolAW& w = *e->byol_a;
@@ -121,7 +121,7 @@ int byol_a_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const s3enc_byol_a_config& x = e->byol_a_cfg;
     const ByolAW& w = *e->byol_a;
@@ -315,5 +315,18 @@ int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int6
     HIP_TRY(sink.done(0));
     return 0;
 }
+
+
+// frames: segments; valid: the utterance's own segments (the rows behind them are the reference's values, not zeros); rate:
+// byol_a/expert.py:64-65, int(stride_secs * 16000)
+FamilyOps kByolAFamily = {
+    S3ENC_BYOL_A, "byol_a", "S3ENC_BYOL_A", "s3enc_create_byol_a", "the BYOL-A family needs its segment block",
+    "BYOL-A (one hidden_states list)",
+    [](const s3enc_config& c, const void* b) { return byol_a_check_config(c, *(const s3enc_byol_a_config*)b); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->byol_a_cfg = *(const s3enc_byol_a_config*)b; return byol_a_create(e, ck); },
+    byol_a_forward,
+    [](const s3enc_encoder* h, long n) { return byol_a_num_segments(h->byol_a_cfg, n); },
+    nullptr,
+    [](const s3enc_encoder* h) { return (int)h->byol_a_cfg.stride; }};
 
 }  // namespace s3e

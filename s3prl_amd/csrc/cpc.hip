@@ -184,7 +184,7 @@ hipError_t launch_cpc_conv0(const CpcConv0Params& p, hipStream_t s) {
 // ---- the handle's side: configuration, weights, forward ------------------------------------------------------------------
 namespace s3e {
 
-long cpc_conv_len(const s3enc_config& c, const s3enc_cpc_config& x, long n, int upto /*exclusive*/) {
+static long cpc_conv_len(const s3enc_config& c, const s3enc_cpc_config& x, long n, int upto /*exclusive*/) {
     for (int i = 0; i < upto; ++i) {
         const long padded = n + 2L * x.conv_pad[i];
         n = (n > 0 && padded >= c.conv_kernel[i]) ? (padded - c.conv_kernel[i]) / c.conv_stride[i] + 1 : 0;
@@ -192,7 +192,7 @@ long cpc_conv_len(const s3enc_config& c, const s3enc_cpc_config& x, long n, int 
     return n;
 }
 
-int cpc_check_config(const s3enc_config& c, const s3enc_cpc_config& x) {
+static int cpc_check_config(const s3enc_config& c, const s3enc_cpc_config& x) {
     static const char* dt[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
@@ -223,7 +223,7 @@ int cpc_check_config(const s3enc_config& c, const s3enc_cpc_config& x) {
     return 0;
 }
 
-int cpc_create(s3enc_encoder* e, const Ckpt& ck) {
+static int cpc_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_config& c = e->cfg;
     const s3enc_cpc_config& x = e->cpc_cfg;
     const int C = c.conv_dim, H = x.ar_hidden, G = x.ar_mode == 0 ? 4 : 3;
@@ -256,7 +256,7 @@ int cpc_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const s3enc_config& c = e->cfg;
     const s3enc_cpc_config& x = e->cpc_cfg;
@@ -428,5 +428,15 @@ int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     HIP_TRY(sink.done(1));
     return 0;
 }
+
+
+// no mask: the frames the utterance's own samples reach through the padded stack (the wav2vec convention)
+FamilyOps kCpcFamily = {
+    S3ENC_CPC, "cpc", "S3ENC_CPC", "s3enc_create_cpc", "the modified-CPC family needs its padding / recurrent-network block",
+    "modified CPC (one hidden_states list of 2 states)",
+    [](const s3enc_config& c, const void* b) { return cpc_check_config(c, *(const s3enc_cpc_config*)b); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->cpc_cfg = *(const s3enc_cpc_config*)b; return cpc_create(e, ck); },
+    cpc_forward,
+    [](const s3enc_encoder* h, long n) { return cpc_conv_len(h->cfg, h->cpc_cfg, n, h->cfg.n_conv); }};
 
 }  // namespace s3e

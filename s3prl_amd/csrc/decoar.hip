@@ -34,7 +34,7 @@ s3::FbankParams decoar_fbank_params(const s3enc_decoar_config& x) {
 }
 }  // namespace
 
-int decoar_check_config(const s3enc_config& c, const s3enc_decoar_config& x) {
+static int decoar_check_config(const s3enc_config& c, const s3enc_decoar_config& x) {
     static const char* dt[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
@@ -58,7 +58,7 @@ int decoar_check_config(const s3enc_config& c, const s3enc_decoar_config& x) {
     return 0;
 }
 
-int decoar_create(s3enc_encoder* e, const Ckpt& ck) {
+static int decoar_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_decoar_config& x = e->decoar_cfg;
     const int H = x.hidden, F = x.num_mel_bins;
     e->decoar.reset(new DecoarW());
@@ -95,12 +95,13 @@ int decoar_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-long decoar_num_frames(const s3enc_config&, const s3enc_decoar_config& x, long n_samples) {
+// ceil(fbank frames / subsample)
+static long decoar_num_frames(const s3enc_config&, const s3enc_decoar_config& x, long n_samples) {
     const long f = s3::fbank_num_frames(n_samples, decoar_fbank_params(x));
     return f < 1 ? 0 : (f + x.subsample - 1) / x.subsample;
 }
 
-int decoar_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int decoar_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const s3enc_decoar_config& x = e->decoar_cfg;
     const DecoarW& w = *e->decoar;
@@ -232,5 +233,15 @@ int decoar_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int6
     }
     return 0;
 }
+
+
+// valid: the utterance's own frame count (its packed length)
+FamilyOps kDecoarFamily = {
+    S3ENC_DECOAR, "decoar", "S3ENC_DECOAR", "s3enc_create_decoar", "the DeCoAR family needs its front-end / LSTM block",
+    "DeCoAR (one hidden_states list)",
+    [](const s3enc_config& c, const void* b) { return decoar_check_config(c, *(const s3enc_decoar_config*)b); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->decoar_cfg = *(const s3enc_decoar_config*)b; return decoar_create(e, ck); },
+    decoar_forward,
+    [](const s3enc_encoder* h, long n) { return decoar_num_frames(h->cfg, h->decoar_cfg, n); }};
 
 }  // namespace s3e

@@ -130,6 +130,16 @@ int stage_commit(s3enc_encoder* e, const char* hp, void* dst, size_t bytes, hipS
 
 namespace {
 
+// The families that come with a second configuration block (FamilyOps, engine_internal.h), in the order their entries were added:
+// the one list of them the engine has.
+const FamilyOps* const kFamilies[] = {&kWav2vecFamily, &kCpcFamily,    &kApcFamily,   &kMockingjayFamily, &kDecoarFamily,
+                                      &kNpcFamily,     &kVggishFamily, &kByolAFamily, &kMaeAstFamily};
+const FamilyOps* family_ops(int family) {  // null: a Transformer family
+    for (const FamilyOps* f : kFamilies)
+        if (f->family == family) return f;
+    return nullptr;
+}
+
 // WavLM bucket table (wavlm/modules.py:418-462): table[h][rel + R] = E[bucket(rel)][h] for rel = key - query in [-R, R]
 void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R, std::vector<float>& table) {
     const int H = c.heads, nb = c.num_buckets / 2, max_exact = nb / 2;
@@ -156,15 +166,7 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 
 int check_config(const s3enc_config& c) {
     if (c.family < 0 || c.family > 13) return fail("config: unknown family");
-    if (c.family == S3ENC_WAV2VEC) return 0;  // s3enc_create_ex: wav2vec_check_config on both configuration blocks
-    if (c.family == S3ENC_CPC) return 0;      // s3enc_create_cpc: cpc_check_config on both configuration blocks
-    if (c.family == S3ENC_APC) return 0;      // s3enc_create_apc: apc_check_config on both configuration blocks
-    if (c.family == S3ENC_MOCKINGJAY) return 0;  // s3enc_create_mockingjay: mj_check_config on both configuration blocks
-    if (c.family == S3ENC_DECOAR) return 0;      // s3enc_create_decoar: decoar_check_config on both configuration blocks
-    if (c.family == S3ENC_NPC) return 0;         // s3enc_create_npc: npc_check_config on both configuration blocks
-    if (c.family == S3ENC_VGGISH) return 0;      // s3enc_create_vggish: vggish_check_config on both configuration blocks
-    if (c.family == S3ENC_BYOL_A) return 0;      // s3enc_create_byol_a: byol_a_check_config on both configuration blocks
-    if (c.family == S3ENC_MAE_AST) return 0;     // s3enc_create_mae_ast: mae_ast_check_config on both configuration blocks
+    if (family_ops(c.family)) return 0;  // its record's own check runs on both configuration blocks (create_impl)
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
         const int k = c.mr_kernel;
@@ -232,31 +234,28 @@ static int finish_create(std::unique_ptr<s3enc_encoder> e, s3enc_handle* out) {
     return 0;
 }
 
-// The families that come with a second configuration block, each through the entry point that takes it.  `own`: the family whose
-// block the calling entry takes (-1: none).  An entry refuses the families whose entry was added after it by name (`entry` prefixes
-// those refusals), and any other family than its own as not its block's.
+// Each family of kFamilies comes through the entry point that takes its block.  `own`: the family whose block the calling entry
+// takes (-1: none).  An entry refuses the families whose entry was added after it by name (`entry` prefixes those refusals), and
+// any other family than its own as not its block's.
 static int wrong_entry(const char* entry, int own, int family) {
-    static const struct {
-        int family;
-        const char *block, *name, *entry, *needs;
-    } F[] = {
-        {S3ENC_WAV2VEC, "wav2vec", "S3ENC_WAV2VEC", "s3enc_create_ex", "the wav2vec family needs its aggregator / quantizer block"},
-        {S3ENC_CPC, "cpc", "S3ENC_CPC", "s3enc_create_cpc", "the modified-CPC family needs its padding / recurrent-network block"},
-        {S3ENC_APC, "apc", "S3ENC_APC", "s3enc_create_apc", "the APC family needs its front-end / GRU block"},
-        {S3ENC_MOCKINGJAY, "mockingjay", "S3ENC_MOCKINGJAY", "s3enc_create_mockingjay",
-         "the Mockingjay / TERA / AudioALBERT family needs its front-end block"},
-        {S3ENC_DECOAR, "decoar", "S3ENC_DECOAR", "s3enc_create_decoar", "the DeCoAR family needs its front-end / LSTM block"},
-        {S3ENC_NPC, "npc", "S3ENC_NPC", "s3enc_create_npc", "the NPC family needs its front-end / convolution block"},
-        {S3ENC_VGGISH, "vggish", "S3ENC_VGGISH", "s3enc_create_vggish", "the VGGish family needs its front-end / layer block"},
-        {S3ENC_BYOL_A, "byol_a", "S3ENC_BYOL_A", "s3enc_create_byol_a", "the BYOL-A family needs its segment block"},
-        {S3ENC_MAE_AST, "mae_ast", "S3ENC_MAE_AST", "s3enc_create_mae_ast", "the MAE-AST family needs its patch / BatchNorm block"},
-    };
     if (family == own) return 0;
-    for (const auto& f : F)
-        if (f.family == family && family > own) return fail(std::string(entry) + ": " + f.needs + ": use " + f.entry);
-    for (const auto& f : F)
-        if (f.family == own) return fail(std::string(f.entry) + ": the " + f.block + " block belongs to family " + f.name + " only");
+    for (const FamilyOps* f : kFamilies)
+        if (f->family == family && family > own) return fail(std::string(entry) + ": " + f->needs + ": use " + f->entry);
+    for (const FamilyOps* f : kFamilies)
+        if (f->family == own) return fail(std::string(f->entry) + ": the " + f->block + " block belongs to family " + f->name + " only");
     return 0;
+}
+
+static int create_impl(const s3enc_config* cfg, int own, const void* block, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device,
+                       s3enc_handle* out);
+
+// an entry whose block is required: s3enc_create_cpc and every later one
+static int create_family(const FamilyOps& f, const s3enc_config* cfg, const void* block, const s3enc_tensor* tensors, int32_t n_tensors,
+                         int32_t device, s3enc_handle* out) {
+    if (!cfg || !block || !tensors || !out) return fail(std::string(f.entry) + ": null argument");
+    *out = nullptr;
+    if (wrong_entry(f.entry, f.family, cfg->family)) return 1;
+    return create_impl(cfg, f.family, block, tensors, n_tensors, device, out);
 }
 
 extern "C" {
@@ -268,104 +267,57 @@ int s3enc_create(const s3enc_config* cfg, const s3enc_tensor* tensors, int32_t n
     return s3enc_create_ex(cfg, nullptr, tensors, n_tensors, device, out);
 }
 
-static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_decoar_config* dc,
-                       const s3enc_npc_config* npc, const s3enc_vggish_config* vg, const s3enc_byol_a_config* ba, const s3enc_mae_ast_config* ma,
-                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out);
-
 int s3enc_create_ex(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_tensor* tensors, int32_t n_tensors,
                     int32_t device, s3enc_handle* out) {
     if (cfg && cfg->family > S3ENC_WAV2VEC && wrong_entry("s3enc_create", -1, cfg->family)) {  // a later family: needs its own entry
         if (out) *out = nullptr;
         return 1;
     }
-    return create_impl(cfg, w2v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_impl(cfg, w2v ? S3ENC_WAV2VEC : -1, w2v, tensors, n_tensors, device, out);
 }
 
 int s3enc_create_cpc(const s3enc_config* cfg, const s3enc_cpc_config* cpc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out) {
-    if (!cfg || !cpc || !tensors || !out) return fail("s3enc_create_cpc: null argument");
-    *out = nullptr;
-    if (wrong_entry("s3enc_create_cpc", S3ENC_CPC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, cpc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_family(kCpcFamily, cfg, cpc, tensors, n_tensors, device, out);
 }
-
 int s3enc_create_apc(const s3enc_config* cfg, const s3enc_apc_config* apc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out) {
-    if (!cfg || !apc || !tensors || !out) return fail("s3enc_create_apc: null argument");
-    *out = nullptr;
-    if (wrong_entry("s3enc_create_apc", S3ENC_APC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, apc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_family(kApcFamily, cfg, apc, tensors, n_tensors, device, out);
 }
-
 int s3enc_create_mockingjay(const s3enc_config* cfg, const s3enc_mockingjay_config* mj, const s3enc_tensor* tensors, int32_t n_tensors,
                             int32_t device, s3enc_handle* out) {
-    if (!cfg || !mj || !tensors || !out) return fail("s3enc_create_mockingjay: null argument");
-    *out = nullptr;
-    if (wrong_entry("s3enc_create_mockingjay", S3ENC_MOCKINGJAY, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, mj, nullptr, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_family(kMockingjayFamily, cfg, mj, tensors, n_tensors, device, out);
 }
-
 int s3enc_create_decoar(const s3enc_config* cfg, const s3enc_decoar_config* decoar, const s3enc_tensor* tensors, int32_t n_tensors,
                         int32_t device, s3enc_handle* out) {
-    if (!cfg || !decoar || !tensors || !out) return fail("s3enc_create_decoar: null argument");
-    *out = nullptr;
-    if (wrong_entry("s3enc_create_decoar", S3ENC_DECOAR, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, decoar, nullptr, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_family(kDecoarFamily, cfg, decoar, tensors, n_tensors, device, out);
 }
-
 int s3enc_create_npc(const s3enc_config* cfg, const s3enc_npc_config* npc, const s3enc_tensor* tensors, int32_t n_tensors,
                      int32_t device, s3enc_handle* out) {
-    if (!cfg || !npc || !tensors || !out) return fail("s3enc_create_npc: null argument");
-    *out = nullptr;
-    if (wrong_entry("s3enc_create_npc", S3ENC_NPC, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, npc, nullptr, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_family(kNpcFamily, cfg, npc, tensors, n_tensors, device, out);
 }
-
 int s3enc_create_vggish(const s3enc_config* cfg, const s3enc_vggish_config* vggish, const s3enc_tensor* tensors, int32_t n_tensors,
                         int32_t device, s3enc_handle* out) {
-    if (!cfg || !vggish || !tensors || !out) return fail("s3enc_create_vggish: null argument");
-    *out = nullptr;
-    if (wrong_entry("s3enc_create_vggish", S3ENC_VGGISH, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, vggish, nullptr, nullptr, tensors, n_tensors, device, out);
+    return create_family(kVggishFamily, cfg, vggish, tensors, n_tensors, device, out);
 }
-
 int s3enc_create_byol_a(const s3enc_config* cfg, const s3enc_byol_a_config* byol_a, const s3enc_tensor* tensors, int32_t n_tensors,
                         int32_t device, s3enc_handle* out) {
-    if (!cfg || !byol_a || !tensors || !out) return fail("s3enc_create_byol_a: null argument");
-    *out = nullptr;
-    if (wrong_entry("s3enc_create_byol_a", S3ENC_BYOL_A, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, byol_a, nullptr, tensors, n_tensors, device, out);
+    return create_family(kByolAFamily, cfg, byol_a, tensors, n_tensors, device, out);
 }
-
 int s3enc_create_mae_ast(const s3enc_config* cfg, const s3enc_mae_ast_config* mae_ast, const s3enc_tensor* tensors, int32_t n_tensors,
                          int32_t device, s3enc_handle* out) {
-    if (!cfg || !mae_ast || !tensors || !out) return fail("s3enc_create_mae_ast: null argument");
-    *out = nullptr;
-    if (wrong_entry("s3enc_create_mae_ast", S3ENC_MAE_AST, cfg->family)) return 1;
-    return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mae_ast, tensors, n_tensors, device, out);
+    return create_family(kMaeAstFamily, cfg, mae_ast, tensors, n_tensors, device, out);
 }
 
-static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v, const s3enc_cpc_config* cpc,
-                       const s3enc_apc_config* apc, const s3enc_mockingjay_config* mj, const s3enc_decoar_config* dc,
-                       const s3enc_npc_config* npc, const s3enc_vggish_config* vg, const s3enc_byol_a_config* ba, const s3enc_mae_ast_config* ma,
-                       const s3enc_tensor* tensors, int32_t n_tensors, int32_t device, s3enc_handle* out) {
+static int create_impl(const s3enc_config* cfg, int own, const void* block, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device,
+                       s3enc_handle* out) {
     if (!cfg || !tensors || !out) return fail("s3enc_create: null argument");
     *out = nullptr;
     if (check_config(*cfg)) return 1;
-    // s3enc_create_ex: a wav2vec block with another family, the wav2vec family without its block
-    if ((w2v || cfg->family == S3ENC_WAV2VEC) && wrong_entry("s3enc_create", w2v ? S3ENC_WAV2VEC : -1, cfg->family)) return 1;
-    switch (cfg->family) {  // (the entry points have refused every other family that came without its own block)
-        case S3ENC_WAV2VEC: if (wav2vec_check_config(W2vCfg(*cfg, *w2v))) return 1; break;
-        case S3ENC_CPC: if (cpc_check_config(*cfg, *cpc)) return 1; break;
-        case S3ENC_APC: if (apc_check_config(*cfg, *apc)) return 1; break;
-        case S3ENC_MOCKINGJAY: if (mj_check_config(*cfg, *mj)) return 1; break;
-        case S3ENC_DECOAR: if (decoar_check_config(*cfg, *dc)) return 1; break;
-        case S3ENC_NPC: if (npc_check_config(*cfg, *npc)) return 1; break;
-        case S3ENC_VGGISH: if (vggish_check_config(*cfg, *vg)) return 1; break;
-        case S3ENC_BYOL_A: if (byol_a_check_config(*cfg, *ba)) return 1; break;
-        case S3ENC_MAE_AST: if (mae_ast_check_config(*cfg, *ma)) return 1; break;
-    }
+    // s3enc_create_ex: a wav2vec block with another family, the wav2vec family without its block (a later entry comes with own == family)
+    if (wrong_entry("s3enc_create", own, cfg->family)) return 1;
+    const FamilyOps* ops = family_ops(cfg->family);  // (non-null: the entry points have refused the family that came without its block)
+    if (ops && ops->check(*cfg, block)) return 1;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail("s3enc_create: no HIP device visible — libs3enc has no CPU fallback");
@@ -385,20 +337,9 @@ static int create_impl(const s3enc_config* cfg, const s3enc_wav2vec_config* w2v,
     e->x2 = cfg->compute_dtype == 4;  // S3ENC_F16X2: the fp16 data flow, GEMM weights split into two fp16 terms
     e->dtype = e->x3 ? (int)F32 : (e->x2 ? (int)F16 : cfg->compute_dtype);
     e->es = e->dtype == F32 ? 4 : 2;
-    int family_rc = -1;  // stays -1 for the Transformer families, whose weights are packed below
-    switch (cfg->family) {
-        case S3ENC_WAV2VEC: e->w2v_cfg = *w2v; family_rc = wav2vec_create(e.get(), ck); break;
-        case S3ENC_CPC: e->cpc_cfg = *cpc; family_rc = cpc_create(e.get(), ck); break;
-        case S3ENC_APC: e->apc_cfg = *apc; family_rc = apc_create(e.get(), ck); break;
-        case S3ENC_MOCKINGJAY: e->mj_cfg = *mj; family_rc = mj_create(e.get(), ck); break;
-        case S3ENC_DECOAR: e->decoar_cfg = *dc; family_rc = decoar_create(e.get(), ck); break;
-        case S3ENC_NPC: e->npc_cfg = *npc; family_rc = npc_create(e.get(), ck); break;
-        case S3ENC_VGGISH: e->vggish_cfg = *vg; family_rc = vggish_create(e.get(), ck); break;
-        case S3ENC_BYOL_A: e->byol_a_cfg = *ba; family_rc = byol_a_create(e.get(), ck); break;
-        case S3ENC_MAE_AST: e->mae_ast_cfg = *ma; family_rc = mae_ast_create(e.get(), ck); break;
-    }
-    if (family_rc >= 0) return family_rc ? 1 : finish_create(std::move(e), out);
-    const s3enc_config& c = e->cfg;
+    e->ops = ops;
+    if (ops) return ops->create(e.get(), ck, block) ? 1 : finish_create(std::move(e), out);
+    const s3enc_config& c = e->cfg;  // the Transformer families: their weights are packed here
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads;
     const bool multires = c.family == S3ENC_MULTIRES;
     const std::string enc0 = multires ? "encoders.0" : "encoder";  // only the first block keeps its positional conv
@@ -812,100 +753,38 @@ int s3enc_destroy(s3enc_handle h) {
     return 0;
 }
 
+// frames of an n-sample input; `output`: of the states a forward writes (multires-HuBERT cuts them to a common length)
+static long frames_of(s3enc_handle h, long n_samples, bool output) {
+    if (h->ops && h->ops->frames) return h->ops->frames(h, n_samples);
+    return output ? output_frames(h->cfg, n_samples) : conv_len(h->cfg, n_samples, h->cfg.n_conv);
+}
 int s3enc_num_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
     if (!h || !T) return fail("s3enc_num_frames: null argument");
-    if (h->cfg.family == S3ENC_MOCKINGJAY) {  // the stand-alone count; inside a batch see s3enc_valid_frames
-        *T = (int32_t)mj_num_frames(h->cfg, h->mj_cfg, n_samples);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_DECOAR) {
-        *T = (int32_t)decoar_num_frames(h->cfg, h->decoar_cfg, n_samples);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_VGGISH) {  // examples, not frames
-        *T = (int32_t)vggish_num_examples(h->vggish_cfg, n_samples);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_BYOL_A) {  // segments, not frames
-        *T = (int32_t)byol_a_num_segments(h->byol_a_cfg, n_samples);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_MAE_AST) {  // time steps of kt frames: a state row is the V tokens of one step
-        *T = (int32_t)mae_ast_num_steps(h->mae_ast_cfg, n_samples);
-        return 0;
-    }
-    *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
-                                              : conv_len(h->cfg, n_samples, h->cfg.n_conv));
+    *T = (int32_t)frames_of(h, n_samples, false);
     return 0;
 }
 int s3enc_num_output_frames(s3enc_handle h, int64_t n_samples, int32_t* T) {
     if (!h || !T) return fail("s3enc_num_output_frames: null argument");
-    if (h->cfg.family == S3ENC_MOCKINGJAY) {
-        *T = (int32_t)mj_num_frames(h->cfg, h->mj_cfg, n_samples);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_DECOAR) {
-        *T = (int32_t)decoar_num_frames(h->cfg, h->decoar_cfg, n_samples);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_VGGISH) {  // examples, not frames
-        *T = (int32_t)vggish_num_examples(h->vggish_cfg, n_samples);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_BYOL_A) {  // segments, not frames
-        *T = (int32_t)byol_a_num_segments(h->byol_a_cfg, n_samples);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_MAE_AST) {  // time steps of kt frames: a state row is the V tokens of one step
-        *T = (int32_t)mae_ast_num_steps(h->mae_ast_cfg, n_samples);
-        return 0;
-    }
-    *T = (int32_t)(h->cfg.family == S3ENC_CPC ? cpc_conv_len(h->cfg, h->cpc_cfg, n_samples, h->cfg.n_conv)
-                                              : output_frames(h->cfg, n_samples));
+    *T = (int32_t)frames_of(h, n_samples, true);
     return 0;
 }
 int s3enc_downsample_rate(s3enc_handle h, int32_t* rate) {
     if (!h || !rate) return fail("s3enc_downsample_rate: null argument");
     int r = 1;
     for (int i = 0; i < h->cfg.n_conv; ++i) r *= h->cfg.conv_stride[i];
-    if (h->cfg.family == S3ENC_MAE_AST) r = h->mae_ast_cfg.kt * 160;  // mae_ast/expert.py:57-58
-    if (h->cfg.family == S3ENC_BYOL_A) r = h->byol_a_cfg.stride;  // byol_a/expert.py:64-65: int(stride_secs * 16000)
-    if (h->cfg.family == S3ENC_VGGISH) r = 16000;  // vggish/expert.py:21-22 (the examples are 15360 samples apart; the reference says 16000)
-    *rate = r;
+    *rate = h->ops && h->ops->rate ? h->ops->rate(h) : r;
     return 0;
 }
 int s3enc_valid_frames(s3enc_handle h, int64_t length, int64_t n_max, int32_t* valid) {
     if (!h || !valid) return fail("s3enc_valid_frames: null argument");
-    if (h->cfg.family == S3ENC_CPC) {  // no mask: the frames the utterance's own samples reach (the wav2vec convention)
-        const long T = cpc_conv_len(h->cfg, h->cpc_cfg, n_max, h->cfg.n_conv);
-        const long v = cpc_conv_len(h->cfg, h->cpc_cfg, length, h->cfg.n_conv);
-        *valid = (int32_t)(T <= 0 ? 0 : std::max(0L, std::min(v, T)));
-        return 0;
+    const FamilyOps* f = h->ops;
+    if (f && f->valid) {
+        *valid = f->valid(h, length, n_max);
+    } else if (f && f->frames) {  // a family's own count and no mask rule: what the utterance's own samples reach, within the batch's
+        *valid = (int32_t)std::max(0L, std::min(f->frames(h, length), f->frames(h, n_max)));
+    } else {
+        *valid = valid_frames(h->cfg, length, n_max);
     }
-    if (h->cfg.family == S3ENC_MOCKINGJAY) {  // mel + CMVN: round(length / (n_max / T)), batch-dependent
-        *valid = mj_valid_frames(h->cfg, h->mj_cfg, length, n_max);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_DECOAR) {  // the utterance's own frame count (its packed length)
-        const long T = decoar_num_frames(h->cfg, h->decoar_cfg, n_max), v = decoar_num_frames(h->cfg, h->decoar_cfg, length);
-        *valid = (int32_t)(T <= 0 ? 0 : std::max(0L, std::min(v, T)));
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_MAE_AST) {  // forward_padding_mask: a step that is only partly real counts as real
-        *valid = (int32_t)mae_ast_valid_steps(h->mae_ast_cfg, length, n_max);
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_BYOL_A) {  // the utterance's own segments; the rows behind them are the reference's values, not zeros
-        const long T = byol_a_num_segments(h->byol_a_cfg, n_max), v = byol_a_num_segments(h->byol_a_cfg, length);
-        *valid = (int32_t)std::max(0L, std::min(v, T));
-        return 0;
-    }
-    if (h->cfg.family == S3ENC_VGGISH) {  // the utterance's own examples; the rows behind them are exact zeros
-        const long T = vggish_num_examples(h->vggish_cfg, n_max), v = vggish_num_examples(h->vggish_cfg, length);
-        *valid = (int32_t)(T <= 0 ? 0 : std::max(0L, std::min(v, T)));
-        return 0;
-    }
-    *valid = valid_frames(h->cfg, length, n_max);
     return 0;
 }
 
@@ -1172,17 +1051,7 @@ int forward_impl(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
 
 int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                  const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
-    switch (e->cfg.family) {
-        case S3ENC_WAV2VEC: return wav2vec_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-        case S3ENC_CPC: return cpc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-        case S3ENC_APC: return apc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-        case S3ENC_MOCKINGJAY: return mj_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-        case S3ENC_DECOAR: return decoar_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-        case S3ENC_NPC: return npc_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-        case S3ENC_VGGISH: return vggish_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-        case S3ENC_BYOL_A: return byol_a_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-        case S3ENC_MAE_AST: return mae_ast_forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
-    }
+    if (e->ops) return e->ops->forward(e, wav_ptrs_host, lengths, B, n_max_in, fo, out, layer_stride, st);
     const s3enc_config& c = e->cfg;
     const int C = c.conv_dim, D = c.embed_dim, F = c.ffn_dim, H = c.heads, NL = c.encoder_layers;
     const int dt = e->dtype, es = e->es;
@@ -1924,26 +1793,9 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
         return fail("s3enc_num_states: DistilHuBERT / multires-HuBERT have one selection (their hidden_states list)");
     if (h->cfg.layer_type == 1 && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: feature_selection is not defined for a Conformer encoder");
-    if (h->cfg.family == S3ENC_CPC && selection != S3ENC_SEL_HIDDEN)
-        return fail("s3enc_num_states: feature_selection is not defined for modified CPC (one hidden_states list of 2 states)");
-    if (h->cfg.family == S3ENC_APC && selection != S3ENC_SEL_HIDDEN)
-        return fail("s3enc_num_states: feature_selection is not defined for APC (one hidden_states list of 3 states)");
-    if (h->cfg.family == S3ENC_MOCKINGJAY && selection != S3ENC_SEL_HIDDEN)
-        return fail("s3enc_num_states: feature_selection is not defined for Mockingjay / TERA / AudioALBERT (one hidden_states list)");
-    if (h->cfg.family == S3ENC_DECOAR && selection != S3ENC_SEL_HIDDEN)
-        return fail("s3enc_num_states: feature_selection is not defined for DeCoAR (one hidden_states list)");
-    if (h->cfg.family == S3ENC_NPC && selection != S3ENC_SEL_HIDDEN)
-        return fail("s3enc_num_states: feature_selection is not defined for NPC (one hidden_states list)");
-    if (h->cfg.family == S3ENC_VGGISH && selection != S3ENC_SEL_HIDDEN)
-        return fail("s3enc_num_states: feature_selection is not defined for VGGish (one hidden_states list)");
-    if (h->cfg.family == S3ENC_BYOL_A && selection != S3ENC_SEL_HIDDEN)
-        return fail("s3enc_num_states: feature_selection is not defined for BYOL-A (one hidden_states list)");
-    if (h->cfg.family == S3ENC_MAE_AST) {
-        if (selection != S3ENC_SEL_HIDDEN) return fail("s3enc_num_states: feature_selection is not defined for MAE-AST (one hidden_states list)");
-        *n = h->cfg.encoder_layers;  // the layer outputs; the embedding is not among them (mae_ast.py:671-677)
-        return 0;
-    }
-    *n = num_states(h->cfg, selection);
+    if (h->ops && h->ops->one_list && selection != S3ENC_SEL_HIDDEN)
+        return fail(std::string("s3enc_num_states: feature_selection is not defined for ") + h->ops->one_list);
+    *n = h->ops && h->ops->states ? h->ops->states(h) : num_states(h->cfg, selection);
     return 0;
 }
 

@@ -12,7 +12,8 @@
 //   vggish.hip  VGGish: the un-padded log-mel examples, the 3 x 3 conv + pool stack on conv2d.hip, three Linears, the quantiser
 //   byol_a.hip  BYOL-A: per-segment FFT log-mel (melspec.hip), conv + BatchNorm + floor-pool on conv2d.hip, two Linears, max + mean
 //   mae_ast.hip MAE-AST: per-utterance kaldi fbank, the fused patch embedding (patchembed.hip), pre- / post-LN Transformer layers
-//   (a family file holds its configuration check, its weights and its forward schedule: nothing of the plumbing above)
+//   (a family file holds its configuration check, its weights, its forward schedule and its shape rules, and hands them to the engine
+//   as one FamilyOps record: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
 #pragma once
 #include <hip/hip_runtime.h>
@@ -469,6 +470,7 @@ struct ProfRec {
     int kind;
     hipEvent_t a, b;
 };
+struct FamilyOps;
 
 }  // namespace s3e
 
@@ -537,6 +539,7 @@ struct s3enc_encoder {
     s3enc_byol_a_config byol_a_cfg = {};  // ... and its second configuration block (s3enc_create_byol_a)
     std::unique_ptr<MaeAstW> mae_ast;   // S3ENC_MAE_AST
     s3enc_mae_ast_config mae_ast_cfg = {};  // ... and its second configuration block (s3enc_create_mae_ast)
+    const FamilyOps* ops = nullptr;     // the record of a family with a second configuration block (set at create time)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
 
@@ -803,67 +806,27 @@ int num_states(const s3enc_config& c, int selection);
 int multires_tail(s3enc_handle e, hipStream_t st, int B, const MrPlan& plan, const std::vector<const int*>& d_valid, float* xproj,
                   void* out, long layer_stride, const FwdOpts& fo);
 
-// wav2vec.hip: the S3ENC_WAV2VEC family (its own configuration check, weights and forward schedule)
-// the family's configuration as one object: the extractor fields of s3enc_config beside the aggregator / quantizer block
-struct W2vCfg : s3enc_config, s3enc_wav2vec_config {
-    W2vCfg(const s3enc_config& a, const s3enc_wav2vec_config& b) : s3enc_config(a), s3enc_wav2vec_config(b) {}
+// ---- the families that come with a second configuration block ------------------------------------------------------------------------
+// All the engine knows about such a family is its record: a family file defines it at its end, beside the thin adapters to its own
+// functions, and engine.hip lists the records (kFamilies).  The handle points at its family's record; null: a Transformer family.
+struct FamilyOps {
+    int family;
+    const char *block, *name, *entry, *needs;  // the refusals of an entry that met the wrong family (engine.hip, wrong_entry)
+    const char* one_list;  // s3enc_num_states: "feature_selection is not defined for <one_list>"; null: every selection is defined
+    int (*check)(const s3enc_config& c, const void* block);
+    int (*create)(s3enc_encoder* e, const Ckpt& ck, const void* block);  // copies the block into the handle, then packs the weights
+    int (*forward)(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+    // the shape rules; null: the rule the Transformer families have
+    long (*frames)(const s3enc_encoder* h, long n_samples);         // s3enc_num_frames / s3enc_num_output_frames
+    int (*valid)(const s3enc_encoder* h, long length, long n_max);  // s3enc_valid_frames; null with `frames`: the utterance's own
+                                                                    // count of them, clamped to the batch's
+    int (*rate)(const s3enc_encoder* h);                            // s3enc_downsample_rate
+    int (*states)(const s3enc_encoder* h);                          // s3enc_num_states
 };
-int wav2vec_check_config(const W2vCfg& c);
-int wav2vec_create(s3enc_encoder* e, const Ckpt& ck);
-int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
-
-// cpc.hip: the S3ENC_CPC family (its own configuration check, weights and forward schedule); frames through the padded conv stack
-long cpc_conv_len(const s3enc_config& c, const s3enc_cpc_config& x, long n, int upto /*exclusive*/);
-int cpc_check_config(const s3enc_config& c, const s3enc_cpc_config& x);
-int cpc_create(s3enc_encoder* e, const Ckpt& ck);
-int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
-
-// apc.hip: the S3ENC_APC family (kaldi log-mel front end + GRU layers on packed sequences)
-int apc_check_config(const s3enc_config& c, const s3enc_apc_config& x);
-int apc_create(s3enc_encoder* e, const Ckpt& ck);
-int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
-
-// decoar.hip: the S3ENC_DECOAR family (kaldi log-mel front end + Linear + forward / backward LSTM stacks on packed sequences)
-int decoar_check_config(const s3enc_config& c, const s3enc_decoar_config& x);
-int decoar_create(s3enc_encoder* e, const Ckpt& ck);
-long decoar_num_frames(const s3enc_config& c, const s3enc_decoar_config& x, long n_samples);  // ceil(fbank frames / subsample)
-int decoar_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
-// npc.hip: the S3ENC_NPC family (kaldi log-mel front end + ConvBlocks + masked convolutions; no length masking)
-int npc_check_config(const s3enc_config& c, const s3enc_npc_config& x);
-int npc_create(s3enc_encoder* e, const Ckpt& ck);
-int npc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
-// vggish.hip: the S3ENC_VGGISH family (un-padded log-mel examples + 3 x 3 conv / pool stack + Linears + quantiser; zero pad rows)
-int vggish_check_config(const s3enc_config& c, const s3enc_vggish_config& x);
-int vggish_create(s3enc_encoder* e, const Ckpt& ck);
-long vggish_num_examples(const s3enc_vggish_config& x, long n_samples);  // E of an n-sample utterance, 0 when it holds no example
-int vggish_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
-// byol_a.hip: the S3ENC_BYOL_A family (segments -> FFT log-mel -> conv / BatchNorm / floor-pool stack -> Linears -> max + mean; the
-// rows behind an utterance's own segments are the reference's values, not zeros)
-int byol_a_check_config(const s3enc_config& c, const s3enc_byol_a_config& x);
-int byol_a_create(s3enc_encoder* e, const Ckpt& ck);
-long byol_a_num_segments(const s3enc_byol_a_config& x, long n_samples);  // len(range(0, n, stride))
-int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
-// mae_ast.hip: the S3ENC_MAE_AST family (kaldi fbank at 128 bins -> fused patch embedding + position rows -> Transformer layers with
-// key padding; rows behind an utterance's valid count are the reference's values, queries over the live keys)
-int mae_ast_check_config(const s3enc_config& c, const s3enc_mae_ast_config& x);
-int mae_ast_create(s3enc_encoder* e, const Ckpt& ck);
-long mae_ast_num_steps(const s3enc_mae_ast_config& x, long n_samples);                 // F(n) / kt
-long mae_ast_valid_steps(const s3enc_mae_ast_config& x, long length, long n_max);      // min(ceil(F(length) / kt), F(n_max) / kt)
-int mae_ast_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
-// mockingjay.hip: the S3ENC_MOCKINGJAY family (spectrogram front end + input representation + post-LN BERT layers, chunked)
-int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x);
-int mj_create(s3enc_encoder* e, const Ckpt& ck);
-long mj_num_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long n);
-int mj_valid_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long length, long n_max);
-int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-               const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st);
+// (read-only, but not declared const: the compiler would emit a constant-initialised const object into the device code as well, where
+// the host functions it points to do not exist)
+extern FamilyOps kWav2vecFamily, kCpcFamily, kApcFamily, kMockingjayFamily, kDecoarFamily, kNpcFamily, kVggishFamily, kByolAFamily,
+    kMaeAstFamily;
 
 }  // namespace s3e

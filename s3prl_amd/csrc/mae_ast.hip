@@ -39,14 +39,15 @@ s3::FbankParams mae_fbank_params() {  // torchaudio.compliance.kaldi.fbank's def
 long mae_frames(long n) { return n < 400 ? 0 : 1 + (n - 400) / 160; }
 }  // namespace
 
-long mae_ast_num_steps(const s3enc_mae_ast_config& x, long n_samples) { return mae_frames(n_samples) / x.kt; }
+static long mae_ast_num_steps(const s3enc_mae_ast_config& x, long n_samples) { return mae_frames(n_samples) / x.kt; }
 
-long mae_ast_valid_steps(const s3enc_mae_ast_config& x, long length, long n_max) {
+// min(ceil(F(length) / kt), F(n_max) / kt)
+static long mae_ast_valid_steps(const s3enc_mae_ast_config& x, long length, long n_max) {
     const long Tt = mae_frames(n_max) / x.kt, v = (mae_frames(length) + x.kt - 1) / x.kt;
     return std::max(0L, std::min(v, Tt));
 }
 
-int mae_ast_check_config(const s3enc_config& c, const s3enc_mae_ast_config& x) {
+static int mae_ast_check_config(const s3enc_config& c, const s3enc_mae_ast_config& x) {
     static const char* dt[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
@@ -67,7 +68,7 @@ int mae_ast_check_config(const s3enc_config& c, const s3enc_mae_ast_config& x) {
     return 0;
 }
 
-int mae_ast_create(s3enc_encoder* e, const Ckpt& ck) {
+static int mae_ast_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_mae_ast_config& x = e->mae_ast_cfg;
     const s3enc_config& c = e->cfg;
     const int D = c.embed_dim, FF = c.ffn_dim, K = x.kt * x.kc;
@@ -134,7 +135,7 @@ int mae_ast_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-int mae_ast_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int mae_ast_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                     const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const s3enc_mae_ast_config& x = e->mae_ast_cfg;
     const s3enc_config& c = e->cfg;
@@ -306,5 +307,19 @@ int mae_ast_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int
     }
     return 0;
 }
+
+
+// frames: time steps of kt frames (a state row is the V tokens of one step); valid: forward_padding_mask, a step that is only partly
+// real counts as real; rate: mae_ast/expert.py:57-58; states: the layer outputs, the embedding is not among them (mae_ast.py:671-677)
+FamilyOps kMaeAstFamily = {
+    S3ENC_MAE_AST, "mae_ast", "S3ENC_MAE_AST", "s3enc_create_mae_ast", "the MAE-AST family needs its patch / BatchNorm block",
+    "MAE-AST (one hidden_states list)",
+    [](const s3enc_config& c, const void* b) { return mae_ast_check_config(c, *(const s3enc_mae_ast_config*)b); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->mae_ast_cfg = *(const s3enc_mae_ast_config*)b; return mae_ast_create(e, ck); },
+    mae_ast_forward,
+    [](const s3enc_encoder* h, long n) { return mae_ast_num_steps(h->mae_ast_cfg, n); },
+    [](const s3enc_encoder* h, long length, long n_max) { return (int)mae_ast_valid_steps(h->mae_ast_cfg, length, n_max); },
+    [](const s3enc_encoder* h) { return h->mae_ast_cfg.kt * 160; },
+    [](const s3enc_encoder* h) { return h->cfg.encoder_layers; }};
 
 }  // namespace s3e

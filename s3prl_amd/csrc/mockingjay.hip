@@ -137,11 +137,11 @@ void mj_position_rows(int rows, int D, std::vector<float>& out) {
         }
 }
 
-long mj_num_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long n) {
+static long mj_num_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long n) {
     return x.frontend == 1 ? (n > 200 ? logmel_num_frames(n) : 0) : conv_len(c, n, c.n_conv);
 }
 
-int mj_valid_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long length, long n_max) {
+static int mj_valid_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, long length, long n_max) {
     const long T = mj_num_frames(c, x, n_max);
     if (T <= 0) return 0;
     long v;
@@ -150,7 +150,7 @@ int mj_valid_frames(const s3enc_config& c, const s3enc_mockingjay_config& x, lon
     return (int)std::max(0L, std::min(v, T));
 }
 
-int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x) {
+static int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x) {
     static const char* dt[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
@@ -185,7 +185,7 @@ int mj_check_config(const s3enc_config& c, const s3enc_mockingjay_config& x) {
     return 0;
 }
 
-int mj_create(s3enc_encoder* e, const Ckpt& ck) {
+static int mj_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_mockingjay_config& x = e->mj_cfg;
     const s3enc_config& c = e->cfg;
     const int D = c.embed_dim, FF = c.ffn_dim, F = x.input_dim;
@@ -244,7 +244,7 @@ int mj_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const s3enc_mockingjay_config& x = e->mj_cfg;
     const s3enc_config& c = e->cfg;
@@ -439,5 +439,16 @@ int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t*
     }
     return 0;
 }
+
+
+// frames: the stand-alone count; inside a batch the mel front end's CMVN makes the valid count batch-dependent (mj_valid_frames)
+FamilyOps kMockingjayFamily = {
+    S3ENC_MOCKINGJAY, "mockingjay", "S3ENC_MOCKINGJAY", "s3enc_create_mockingjay",
+    "the Mockingjay / TERA / AudioALBERT family needs its front-end block", "Mockingjay / TERA / AudioALBERT (one hidden_states list)",
+    [](const s3enc_config& c, const void* b) { return mj_check_config(c, *(const s3enc_mockingjay_config*)b); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->mj_cfg = *(const s3enc_mockingjay_config*)b; return mj_create(e, ck); },
+    mj_forward,
+    [](const s3enc_encoder* h, long n) { return mj_num_frames(h->cfg, h->mj_cfg, n); },
+    [](const s3enc_encoder* h, long length, long n_max) { return mj_valid_frames(h->cfg, h->mj_cfg, length, n_max); }};
 
 }  // namespace s3e

@@ -40,7 +40,7 @@ bool npc_has_mask(const s3enc_npc_config& x, int i) { return !x.disable_cross_la
 int npc_mask(const s3enc_npc_config& x, int i) { return x.mask_size + 2 * (i + 1); }
 }  // namespace
 
-int npc_check_config(const s3enc_config& c, const s3enc_npc_config& x) {
+static int npc_check_config(const s3enc_config& c, const s3enc_npc_config& x) {
     static const char* dt[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
@@ -70,7 +70,7 @@ int npc_check_config(const s3enc_config& c, const s3enc_npc_config& x) {
     return 0;
 }
 
-int npc_create(s3enc_encoder* e, const Ckpt& ck) {
+static int npc_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_npc_config& x = e->npc_cfg;
     e->npc.reset(new NpcW());
     NpcW& w = *e->npc;
@@ -131,7 +131,7 @@ int npc_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-int npc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int npc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                 const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const s3enc_npc_config& x = e->npc_cfg;
     const NpcW& w = *e->npc;
@@ -286,5 +286,14 @@ int npc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t
     HIP_TRY(sink.done(NS - 1));
     return 0;
 }
+
+
+// frames, mask rule and rate are those of its one-layer "conv stack" (window, hop), as APC's
+FamilyOps kNpcFamily = {
+    S3ENC_NPC, "npc", "S3ENC_NPC", "s3enc_create_npc", "the NPC family needs its front-end / convolution block",
+    "NPC (one hidden_states list)",
+    [](const s3enc_config& c, const void* b) { return npc_check_config(c, *(const s3enc_npc_config*)b); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->npc_cfg = *(const s3enc_npc_config*)b; return npc_create(e, ck); },
+    npc_forward};
 
 }  // namespace s3e

@@ -90,13 +90,14 @@ int vggish_seq_index(const s3enc_vggish_config& x, int i) {
 
 }  // namespace
 
-long vggish_num_examples(const s3enc_vggish_config& x, long n_samples) {
+// E of an n-sample utterance, 0 when it holds no example
+static long vggish_num_examples(const s3enc_vggish_config& x, long n_samples) {
     if (n_samples < x.window) return 0;
     const long F = 1 + (n_samples - x.window) / x.shift;
     return F < x.example_frames ? 0 : 1 + (F - x.example_frames) / x.example_hop;
 }
 
-int vggish_check_config(const s3enc_config& c, const s3enc_vggish_config& x) {
+static int vggish_check_config(const s3enc_config& c, const s3enc_vggish_config& x) {
     static const char* dt[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
@@ -134,7 +135,7 @@ int vggish_check_config(const s3enc_config& c, const s3enc_vggish_config& x) {
     return 0;
 }
 
-int vggish_create(s3enc_encoder* e, const Ckpt& ck) {
+static int vggish_create(s3enc_encoder* e, const Ckpt& ck) {
     const s3enc_vggish_config& x = e->vggish_cfg;
     e->vggish.reset(new VggishW());
     VggishW& w = *e->vggish;
@@ -200,7 +201,7 @@ int vggish_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-int vggish_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int vggish_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                    const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const s3enc_vggish_config& x = e->vggish_cfg;
     const VggishW& w = *e->vggish;
@@ -399,5 +400,18 @@ int vggish_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int6
     HIP_TRY(sink.done(0));
     return 0;
 }
+
+
+// frames: examples; valid: the utterance's own examples (the rows behind them are exact zeros); rate: vggish/expert.py:21-22 (the
+// examples are 15360 samples apart; the reference says 16000)
+FamilyOps kVggishFamily = {
+    S3ENC_VGGISH, "vggish", "S3ENC_VGGISH", "s3enc_create_vggish", "the VGGish family needs its front-end / layer block",
+    "VGGish (one hidden_states list)",
+    [](const s3enc_config& c, const void* b) { return vggish_check_config(c, *(const s3enc_vggish_config*)b); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->vggish_cfg = *(const s3enc_vggish_config*)b; return vggish_create(e, ck); },
+    vggish_forward,
+    [](const s3enc_encoder* h, long n) { return vggish_num_examples(h->vggish_cfg, n); },
+    nullptr,
+    [](const s3enc_encoder*) { return 16000; }};
 
 }  // namespace s3e

@@ -291,7 +291,12 @@ namespace s3e {
 
 static const char* dtype_name(int d) { return d == 1 ? "bf16" : d == 2 ? "fp16" : d == 3 ? "fp32x3" : d == 4 ? "fp16x2" : "fp32"; }
 
-int wav2vec_check_config(const W2vCfg& c) {
+// the family's configuration as one object: the extractor fields of s3enc_config beside the aggregator / quantizer block
+struct W2vCfg : s3enc_config, s3enc_wav2vec_config {
+    W2vCfg(const s3enc_config& a, const s3enc_wav2vec_config& b) : s3enc_config(a), s3enc_wav2vec_config(b) {}
+};
+
+static int wav2vec_check_config(const W2vCfg& c) {
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
     if (c.compute_dtype != S3ENC_F32)
         return fail(std::string("config: wav2vec / vq-wav2vec (conv extractor + aggregator) are built for compute dtype fp32 only; ") +
@@ -327,7 +332,7 @@ int wav2vec_check_config(const W2vCfg& c) {
     return 0;
 }
 
-int wav2vec_create(s3enc_encoder* e, const Ckpt& ck) {
+static int wav2vec_create(s3enc_encoder* e, const Ckpt& ck) {
     const W2vCfg c(e->cfg, e->w2v_cfg);
     const int C = c.conv_dim;
     e->w2v.reset(new W2vW());
@@ -419,7 +424,7 @@ int wav2vec_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+static int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
                     const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
     const W2vCfg c(e->cfg, e->w2v_cfg);
     const W2vW& w = *e->w2v;
@@ -711,5 +716,13 @@ int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int
     }
     return 0;
 }
+
+
+// every selection is defined; frames, mask rule and rate are the conv stack's (valid_frames: the frames an utterance's own samples reach)
+FamilyOps kWav2vecFamily = {
+    S3ENC_WAV2VEC, "wav2vec", "S3ENC_WAV2VEC", "s3enc_create_ex", "the wav2vec family needs its aggregator / quantizer block", nullptr,
+    [](const s3enc_config& c, const void* b) { return wav2vec_check_config(W2vCfg(c, *(const s3enc_wav2vec_config*)b)); },
+    [](s3enc_encoder* e, const Ckpt& ck, const void* b) { e->w2v_cfg = *(const s3enc_wav2vec_config*)b; return wav2vec_create(e, ck); },
+    wav2vec_forward};
 
 }  // namespace s3e

@@ -28,24 +28,9 @@ class HipEncoder:
         if cfg.layer_type == "conformer" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
             # s3enc_create refuses it with this message too; raised here as the configuration error it is
             raise ValueError(f"conformer layers ({cfg.pos_enc_type}) are built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "wav2vec" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"wav2vec / vq-wav2vec are built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "cpc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"modified CPC is built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "apc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"APC / VQ-APC are built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "mockingjay" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"Mockingjay / TERA / AudioALBERT are built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "decoar" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"DeCoAR is built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "npc" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"NPC is built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "vggish" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"VGGish is built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "byol_a" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"BYOL-A is built for compute dtype fp32 only; {dtype} is not built")
-        if cfg.family == "mae_ast" and _lib.DTYPES.get(dtype, -1) != _lib.F32:
-            raise ValueError(f"MAE-AST is built for compute dtype fp32 only; {dtype} is not built")
+        family = _lib.BLOCK_FAMILIES.get(cfg.family)  # None: created by s3enc_create from s3enc_config alone
+        if family and _lib.DTYPES.get(dtype, -1) != _lib.F32:
+            raise ValueError(f"{family.built} built for compute dtype fp32 only; {dtype} is not built")
         if cfg.family == "mae_ast":  # a full state dict is cut to what the handle reads (the position table to its leading rows)
             from .ckpt import mae_ast_hot_path
 
@@ -75,33 +60,9 @@ class HipEncoder:
                 tensors[i].shape[j] = int(s)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            if cfg.family == "wav2vec":  # its aggregator / quantizer block travels beside the (unchanged) s3enc_config
-                w2v = _lib.make_wav2vec_config(cfg)
-                rc = self._lib.s3enc_create_ex(C.byref(ccfg), C.byref(w2v), tensors, len(weights), self.device, C.byref(h))
-            elif cfg.family == "cpc":  # its paddings and recurrent network travel beside the (unchanged) s3enc_config
-                cpc = _lib.make_cpc_config(cfg)
-                rc = self._lib.s3enc_create_cpc(C.byref(ccfg), C.byref(cpc), tensors, len(weights), self.device, C.byref(h))
-            elif cfg.family == "apc":  # its front end and GRU stack travel beside the (unchanged) s3enc_config
-                apc = _lib.make_apc_config(cfg)
-                rc = self._lib.s3enc_create_apc(C.byref(ccfg), C.byref(apc), tensors, len(weights), self.device, C.byref(h))
-            elif cfg.family == "mockingjay":  # its front end and input representation travel beside the (unchanged) s3enc_config
-                mj = _lib.make_mockingjay_config(cfg)
-                rc = self._lib.s3enc_create_mockingjay(C.byref(ccfg), C.byref(mj), tensors, len(weights), self.device, C.byref(h))
-            elif cfg.family == "decoar":  # its front end and LSTM stacks travel beside the (unchanged) s3enc_config
-                dc = _lib.make_decoar_config(cfg)
-                rc = self._lib.s3enc_create_decoar(C.byref(ccfg), C.byref(dc), tensors, len(weights), self.device, C.byref(h))
-            elif cfg.family == "npc":  # its front end and convolution stack travel beside the (unchanged) s3enc_config
-                npc = _lib.make_npc_config(cfg)
-                rc = self._lib.s3enc_create_npc(C.byref(ccfg), C.byref(npc), tensors, len(weights), self.device, C.byref(h))
-            elif cfg.family == "vggish":  # its front end and layer list travel beside the (unchanged) s3enc_config
-                vg = _lib.make_vggish_config(cfg)
-                rc = self._lib.s3enc_create_vggish(C.byref(ccfg), C.byref(vg), tensors, len(weights), self.device, C.byref(h))
-            elif cfg.family == "byol_a":  # its segment geometry travels beside the (unchanged) s3enc_config
-                ba = _lib.make_byol_a_config(cfg)
-                rc = self._lib.s3enc_create_byol_a(C.byref(ccfg), C.byref(ba), tensors, len(weights), self.device, C.byref(h))
-            elif cfg.family == "mae_ast":  # its patch geometry and BatchNorm statistics travel beside the (unchanged) s3enc_config
-                ma = _lib.make_mae_ast_config(cfg, weights)
-                rc = self._lib.s3enc_create_mae_ast(C.byref(ccfg), C.byref(ma), tensors, len(weights), self.device, C.byref(h))
+            if family:  # what the family adds travels in its own block beside the (unchanged) s3enc_config
+                block = family.make_block(cfg, weights)
+                rc = getattr(self._lib, family.create)(C.byref(ccfg), C.byref(block), tensors, len(weights), self.device, C.byref(h))
             else:
                 rc = self._lib.s3enc_create(C.byref(ccfg), tensors, len(weights), self.device, C.byref(h))
             _lib.check(rc, "s3enc_create")
