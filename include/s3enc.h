@@ -96,7 +96,19 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * rows at or behind an utterance's valid count are the reference's values, not zeros: zero log-mel rows through the folded
         * Linear, no position row, queries over the utterance's live keys.  compute_dtype S3ENC_F32 only; built by
         * s3enc_create_mae_ast. */
-       S3ENC_MAE_AST = 13 };
+       S3ENC_MAE_AST = 13,
+       /* BYOL-S (upstream/byol_s/{expert.py,serab_byols/{serab,utils}.py,byol_a/models/{resnetish,audio_ntt}.py}; byol_s_default,
+        * byol_s_resnetish34): the batch zero-padded to n_max, every row padded with window / 2 zeros in front and window - window / 2
+        * behind and cut into windows of `window` samples every `step` samples (HEAR's centred frames), S = n_max / step + 1; per
+        * window BYOL-A's front end with win_length = 400 (a periodic hann(400) centred in the 1024-point frame), log(mel +
+        * FLT_EPSILON); the statistics of ALL B * S windows of the batch, mean = x.mean() / (B S) and std = x.std() / (B S) (unbiased; both
+        * divided by the number of windows, the reference's own arithmetic); (x - mean) / std; then either AudioNTT2020 (`default`:
+        * BYOL-A's network) or a ResNet of BasicBlocks (`resnetish`: a 7 x 7 stem + BatchNorm + ReLU + MaxPool2d(3, 2, 1), four
+        * layers of blocks at 64 / 128 / 256 / 512 channels, the first block of layers 2-4 at stride 2 with a 1 x 1 shortcut), and
+        * mean + max over time.  One state of (B, S, 2048).  NOTHING is masked and a row depends on the WHOLE batch through the two
+        * statistics, its zero padding included; the rows behind an utterance's own len / step + 1 windows are the reference's
+        * values, not zeros.  BatchNorm runs on its running statistics.  compute_dtype S3ENC_F32 only; built by s3enc_create_byol_s. */
+       S3ENC_BYOL_S = 14 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -425,6 +437,26 @@ typedef struct s3enc_mae_ast_config {
     int32_t pos_rows;                               /* rows of enc_sine_pos_embed.pe handed over: min(max_token_length, 8192) */
 } s3enc_mae_ast_config;
 
+/* S3ENC_BYOL_S only: the second configuration block of s3enc_create_byol_s.  s3enc_config carries the window geometry as n_conv = 1,
+ * conv_kernel[0] / conv_stride[0] = window / step in samples, conv_dim = embed_dim = 2048, encoder_layers = 0 (one state).  The
+ * caller computes window = int(window_secs * 1000 / 1000 * 16000) and step = int(hop_secs * 1000 / 1000.0 * 16000) with the
+ * reference's own expressions (expert.py:22-23, serab.py:151-153, utils.py:79).  Checkpoint tensors, the reference's plain state_dict:
+ * default: features.{0,4,8}.{weight,bias}, features.{1,5,9}.{weight,bias,running_mean,running_var}, fc.0 (2048, 512), fc.3 (2048,
+ * 2048); resnetish: conv1.weight (64, 1, 7, 7), bn1.*, layerL.B.{conv1,conv2}.weight, layerL.B.{bn1,bn2}.*, and for the first block
+ * of layers 2-4 layerL.0.downsample.0.weight (planes, inplanes, 1, 1) and layerL.0.downsample.1.*; no convolution has a bias.
+ * s3enc_create_byol_s refuses by name: every compute dtype but fp32, the networks cvt and clstm, Bottleneck blocks, a block count
+ * outside 1..64, a window of at most 512 samples (the reflection is undefined), for `default` a window below 1120 samples, a step
+ * below one sample. */
+enum { S3ENC_BYOL_S_DEFAULT = 0, S3ENC_BYOL_S_RESNETISH = 1, S3ENC_BYOL_S_CVT = 2, S3ENC_BYOL_S_CLSTM = 3 };
+typedef struct s3enc_byol_s_config {
+    int32_t network;                                /* S3ENC_BYOL_S_DEFAULT / _RESNETISH (the other two are refused by name) */
+    int32_t blocks[4];                              /* resnetish: BasicBlocks per layer, 3 4 6 3 (resnetish34) */
+    int32_t bottleneck;                             /* 1: Bottleneck blocks (resnetish50): refused by name */
+    int32_t window;                                 /* samples per window: 16000 */
+    int32_t step;                                   /* samples between two window starts: 800 */
+    float bn_eps;                                   /* 1e-5 */
+} s3enc_byol_s_config;
+
 /* A named fp32 host tensor of the checkpoint, named exactly like the reference state_dict entry
  * ("encoder.layers.3.fc1.weight", ...).  Replaces model.load_state_dict(...)
  * (upstream/hubert/convert.py:37-56, wav2vec2/convert.py:26-39, wavlm/expert.py:37-40). */
@@ -517,6 +549,15 @@ int s3enc_create_byol_a(const s3enc_config* cfg, const s3enc_byol_a_config* byol
  * and length), a batch with F_max < kt, a batch with more tokens than pos_rows (with the count).  Tuning key patch_embed_fused. */
 int s3enc_create_mae_ast(const s3enc_config* cfg, const s3enc_mae_ast_config* mae_ast, const s3enc_tensor* tensors, int32_t n_tensors,
                          int32_t device, s3enc_handle* out);
+/* The S3ENC_BYOL_S family: s3enc_config beside its own block (the other create entries refuse the family by name).  Replaces
+ * UpstreamExpert.__init__ of upstream/byol_s/expert.py.  On the handle: s3enc_num_frames(n) is the number of windows S = n / step +
+ * 1; s3enc_valid_frames is the utterance's own len / step + 1 — the rows behind it are NOT zeros but the reference's values;
+ * s3enc_downsample_rate is step; s3enc_num_states is 1 for S3ENC_SEL_HIDDEN (the other selections are refused), out_dtype must be
+ * S3ENC_F32.  A row depends on the whole batch (the two statistics): a batch must not be split.  Debug taps of the last forward:
+ * "logmel" (B S, frames, 64) un-normalised, "stats" the two statistics {mean / (B S), std / (B S)}.  Tuning keys byol_s_chunk,
+ * stem_fused, conv2d_n64. */
+int s3enc_create_byol_s(const s3enc_config* cfg, const s3enc_byol_s_config* byol_s, const s3enc_tensor* tensors, int32_t n_tensors,
+                        int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -761,6 +802,12 @@ int s3enc_debug_gemm_schedule(int32_t M, int32_t N, int32_t batches, int32_t tm,
  *                   the image in place (patchembed.hip), 0 = a gather kernel that writes the (B * tokens, kt * kc) rows, the tile GEMM
  *                   and a position add — the yardstick and a second implementation, held to the fixture bound; measured 0.0625
  *                   against 0.0798 ms per 32 x 10 s mae_ast_patch embedding, the forwards indistinguishable (profiles/mae_ast_fp32.md);
+ *   "stem_fused":   S3ENC_BYOL_S resnetish handles: 1 = the stem's 7 x 7 convolution, affine, ReLU and 3 x 3 / stride-2 max-pool in one
+ *                   kernel (2.25 x the multiply-adds, no un-pooled map), 0 (default) = the un-pooled map written once and pooled by
+ *                   a second kernel — the same bits; measured 223.0 against 222.2 ms per forward (profiles/byol_s_fp32.md);
+ *   "byol_s_chunk": S3ENC_BYOL_S handles: windows per pass of the network (default 1024, 1..4096): the workspace is bounded by it
+ *                   (about 6.2 MB per window) and does not grow with B x S; a window's bits do not depend on it; measured 246.9 /
+ *                   222.2 / 207.5 / 193.2 ms per 32 x 10 s byol_s_resnetish34 forward at 128 / 256 / 512 / 1024;
  *   "conv_f22":     S3ENC_F32: 1 (default) = conv layers 1.. with kernel 3 and stride 2 (conv1-4 of every extractor) run in the
  *                   two-output form (convf22.hip: 5 block products per pair of outputs instead of 6, fp32 operands and accumulation,
  *                   a different association — results differ in the last bits), 0 = the implicit GEMM;
@@ -926,6 +973,33 @@ int s3enc_op_conv2d3x3_affine(const float* x, const float* w_host, const float* 
  * depend on its 1024 samples only), 0 = the overlapping-row GEMM against the folded hann x DFT matrix.  Refused by message: L <= 512
  * (the reflection is undefined), L < 1120 (fewer than 8 frames).  Synchronises. */
 int s3enc_op_melspec1024(const float* segments, int32_t nseg, int32_t L, float* out, float* power, void* stream);
+
+/* BYOL-S's front end: s3enc_op_melspec1024 with MelSpectrogram(win_length = 400) — a periodic hann(400) behind 312 zeros inside the
+ * 1024-point frame — and no normalisation: out (nseg, frames, 64) = log(mel + FLT_EPSILON).  Always the FFT kernel.  Refused by
+ * message: L <= 512.  Synchronises. */
+int s3enc_op_melspec400(const float* segments, int32_t nseg, int32_t L, float* out, float* power, void* stream);
+
+/* The general form of s3enc_op_conv2d3x3_affine (conv2d.hip, the GEN instantiations; a ResNet BasicBlock's layers): Conv2d(C, N, k,
+ * stride, padding = (k - 1) / 2) on channel-last images, then act(acc * scale[n] + shift[n] + res[b][y][x][n]).
+ *   x: device fp32 (B, H + 2, W + 2, C) with a zero border, for k = 1 as well (the border is then never read).  w_host: HOST fp32
+ *   (N, C, k, k) as nn.Conv2d holds it.  k: 3 or 1.  stride: 1 or 2; Ho = (H + 2 p - k) / stride + 1, rounded down, Wo alike.  bias /
+ *   scale / shift: as for s3enc_op_conv2d3x3_affine.  res: device fp32 (B, Ho, Wo, N) contiguous, or null.  dst: the interior of a
+ *   (B, Ho + 2 dst_pad, Wo + 2 dst_pad, ldo) image whose border is never touched.  C a multiple of 16, N a multiple of 4.
+ *   The M axis is the output pixels of all examples and the K order is fixed (kernel rows, taps, the step's order): an example's bits
+ *   depend neither on B, nor on its place, nor on the tile; k = 3, stride = 1, res = null is bit for bit s3enc_op_conv2d3x3_affine
+ *   without pooling.  Synchronises. */
+int s3enc_op_conv2d_res(const float* x, const float* w_host, const float* bias, const float* scale, const float* shift, const float* res,
+                        int32_t B, int32_t H, int32_t W, int32_t C, int32_t N, int32_t k, int32_t stride, int32_t act, float* dst,
+                        int32_t dst_pad, int64_t ldo, void* stream);
+
+/* BYOL-S's ResNet stem (stem.hip): Conv2d(1, 64, 7, stride 1, padding 3, no bias) -> per-channel affine -> ReLU -> MaxPool2d(3, 2, 1)
+ * on (H, 64) single-channel images.  x: device fp32 (B, H + 8, 64 + 8), the 4 outermost rows / columns zeros.  w_host: HOST fp32 (64,
+ * 1, 7, 7).  scale / shift: device fp32 [64].  dst: a (B, Hp + 2, 32 + 2, 64) image, Hp = (H - 1) / 2 + 1: its interior is written, its
+ * border is never touched.  fused = 1: one kernel; fused = 0: map, device fp32 (B, H + 2, 64 + 2, 64) with a zero border, receives the
+ * un-pooled activation and a second kernel pools it — the same bits.  Negative zero behind the ReLU is written as +0; a NaN stays a
+ * NaN.  Synchronises. */
+int s3enc_op_stem7x7_pool(const float* x, const float* w_host, const float* scale, const float* shift, int32_t B, int32_t H, int32_t fused,
+                          float* dst, float* map, void* stream);
 
 /* The patch embedding of (frames, 128) fp32 images as an implicit GEMM over the tokens of all utterances (patchembed.hip): nn.Unfold
  * with kernel = stride = (kt, kc), Linear(kt * kc, N) and a position row in one pass.

@@ -20,7 +20,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13, "byol_s": 14}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -132,6 +132,15 @@ class S3MaeAstConfig(C.Structure):
                 ("bn_eps", C.c_float), ("pos_rows", C.c_int32)]
 
 
+BYOL_S_NETWORK = {"default": 0, "resnetish": 1, "cvt": 2, "clstm": 3}          # s3enc_byol_s_config.network
+
+
+class S3ByolSConfig(C.Structure):
+    """s3enc_byol_s_config: the window / network block of a BYOL-S handle (s3enc_create_byol_s)."""
+    _fields_ = [("network", C.c_int32), ("blocks", C.c_int32 * 4), ("bottleneck", C.c_int32), ("window", C.c_int32),
+                ("step", C.c_int32), ("bn_eps", C.c_float)]
+
+
 class S3ForwardOpts(C.Structure):
     _fields_ = [("selection", C.c_int32), ("out_dtype", C.c_int32), ("featurize", C.c_int32),
                 ("feat_normalize", C.c_int32), ("feat_w", C.POINTER(C.c_float))]
@@ -212,6 +221,9 @@ _PROTOS = {
     "s3enc_op_conv2d3x3": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
     "s3enc_op_conv2d3x3_affine": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
     "s3enc_op_melspec1024": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
+    "s3enc_op_melspec400": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
+    "s3enc_op_conv2d_res": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
+    "s3enc_op_stem7x7_pool": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_patch_embed": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
@@ -472,6 +484,20 @@ def make_mae_ast_config(cfg, weights) -> S3MaeAstConfig:
     return c
 
 
+def make_byol_s_config(cfg) -> S3ByolSConfig:
+    """The second configuration block of a ``family="byol_s"`` EncoderConfig (``s3enc_create_byol_s``)."""
+    if cfg.family != "byol_s":
+        raise S3EncError("make_byol_s_config needs a byol_s configuration")
+    c = S3ByolSConfig()
+    c.network = BYOL_S_NETWORK[cfg.bs_network]
+    for i, b in enumerate(cfg.bs_blocks):
+        c.blocks[i] = int(b)
+    c.bottleneck = int(cfg.bs_block != "basic")
+    _, c.window, c.step = (int(v) for v in cfg.conv_layers[0])
+    c.bn_eps = float(cfg.bs_bn_eps)
+    return c
+
+
 class BlockFamily(NamedTuple):
     """A family whose handle takes a second configuration block through a create entry of its own (csrc: its FamilyOps record)."""
     block: type                  # the ctypes struct of the block
@@ -495,6 +521,7 @@ BLOCK_FAMILIES = {
     "vggish": BlockFamily(S3VggishConfig, make_vggish_config, "s3enc_create_vggish", "VGGish is"),
     "byol_a": BlockFamily(S3ByolAConfig, make_byol_a_config, "s3enc_create_byol_a", "BYOL-A is"),
     "mae_ast": BlockFamily(S3MaeAstConfig, make_mae_ast_config, "s3enc_create_mae_ast", "MAE-AST is", reads_weights=True),
+    "byol_s": BlockFamily(S3ByolSConfig, make_byol_s_config, "s3enc_create_byol_s", "BYOL-S is"),
 }
 assert set(BLOCK_FAMILIES) <= set(FAMILY)
 _PROTOS.update({f.create: (C.c_int, [C.POINTER(S3Config), C.POINTER(f.block), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)])

@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, byol_a_config, config_from_mae_ast, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, byol_a_config, byol_s_config, config_from_mae_ast, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import param_shapes
 
 _REQUIRED = {
@@ -265,6 +265,42 @@ def mae_ast_cfg_blocks(cfg: EncoderConfig) -> Dict:
     return dict(model=model, task=task)
 
 
+def load_byol_s_checkpoint(ckpt, model_name: str = None, window_secs: float = 1, hop_secs: float = 0.05, blocks=None
+                           ) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """A BYOL-S weight file (upstream/byol_s/serab_byols/serab.py:74-103: ``model.load_state_dict(torch.load(path))``, a PLAIN
+    state dict, loaded strictly) or the dict it holds.  The file carries no configuration.  ``model_name`` is the reference's:
+    "default" (``features.*`` / ``fc.*``), "resnetish34" (``conv1`` / ``bn1`` / ``layerL.B.*``), "cvt" and "clstm" (refused by name);
+    without one it is read off the keys.  The ResNet's block counts are read off the ``layerL.B`` keys (``blocks`` checks them);
+    ``num_batches_tracked`` is training state and is ignored."""
+    import re
+
+    what = ckpt if isinstance(ckpt, str) else "the BYOL-S checkpoint"
+    if not isinstance(ckpt, dict):
+        import torch
+
+        ckpt = torch.load(ckpt, map_location="cpu", weights_only=False)
+    if model_name is None:
+        model_name = "default" if "fc.0.weight" in ckpt else "resnetish"  # (any block counts)
+    if model_name in ("cvt", "clstm"):
+        raise ValueError(f"byol_s network {model_name} is not built (default and resnetish are)")
+    if model_name == "default":
+        cfg = byol_s_config("default", window_secs=window_secs, hop_secs=hop_secs)
+        return cfg, _hot_path_weights(what, cfg, ckpt)
+    if not model_name.startswith("resnetish"):
+        raise ValueError(f"unknown byol_s model_name {model_name!r}")
+    if any(re.match(r"layer\d+\.\d+\.(conv3|bn3)\.", k) for k in ckpt):
+        raise ValueError(f"{what}: byol_s Bottleneck blocks (resnetish50) are not built: BasicBlock layers only")
+    found = [1 + max([int(m.group(1)) for m in (re.match(rf"layer{L}\.(\d+)\.conv1\.weight$", k) for k in ckpt) if m], default=-1)
+             for L in (1, 2, 3, 4)]
+    if min(found) < 1:
+        raise ValueError(f"{what}: missing parameter layer{1 + found.index(min(found))}.0.conv1.weight")
+    want = {"resnetish34": (3, 4, 6, 3), "resnetish18": (2, 2, 2, 2), "resnetish10": (1, 1, 1, 1)}.get(model_name) if blocks is None else tuple(blocks)
+    if want is not None and tuple(found) != tuple(want):
+        raise ValueError(f"{what}: {model_name} has {tuple(want)} blocks, but the checkpoint's layers hold {tuple(found)}")
+    cfg = byol_s_config("resnetish", blocks=found, window_secs=window_secs, hop_secs=hop_secs)
+    return cfg, _hot_path_weights(what, cfg, ckpt)
+
+
 def load_decoar_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
     """``{"model": state_dict}`` (upstream/decoar/expert.py:30-36; decoar_layers/expert.py:30-47 reads the same file and renames
     ``{forward,backward}_lstm.X_lN`` to its per-layer modules).  The file carries no configuration — the reference's ``Decoar()``
@@ -381,6 +417,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_vggish_checkpoint(ckpt)
     if family == "byol_a":
         return load_byol_a_checkpoint(ckpt)
+    if family == "byol_s":
+        return load_byol_s_checkpoint(ckpt)
     if family == "mae_ast":
         return load_mae_ast_checkpoint(ckpt)
 
@@ -442,7 +480,7 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
             sd["batch_norm.num_batches_tracked"] = sd["batch_norm.num_batches_tracked"].to(torch.int64).reshape(())
         torch.save({"cfg": mae_ast_cfg_blocks(cfg), "model": sd}, path)
         return
-    if cfg.family == "byol_a":  # upstream/byol_a/byol_a.py:58-80: a plain state dict
+    if cfg.family in ("byol_a", "byol_s"):  # upstream/byol_a/byol_a.py:58-80, byol_s/serab_byols/serab.py:100-102: a plain state dict
         torch.save(sd, path)
         return
     if cfg.family == "vggish":  # upstream/vggish/hubconf.py:22-31: the two state dicts in one file

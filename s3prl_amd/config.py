@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast", "byol_s")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -233,6 +233,16 @@ class EncoderConfig:
     ma_decoder_layers: int = 2        # the decoder is in the strict state dict and never runs
     ma_dec_sine_pos: bool = True
 
+    # BYOL-S (family "byol_s", upstream/byol_s/{expert.py,serab_byols,byol_a/models}): centred windows of ``window`` samples every
+    # ``step`` samples, a hann(400) log-mel front end, the statistics of the whole batch, AudioNTT2020 ("default") or a ResNet of
+    # BasicBlocks ("resnetish"), mean + max over time.  ``conv_layers`` = [(2048, window, step)] in samples; one state
+    bs_network: str = "default"       # "default" | "resnetish"; "cvt" and "clstm" are refused by name
+    bs_blocks: Tuple[int, ...] = (3, 4, 6, 3)  # resnetish: BasicBlocks per layer (resnetish34)
+    bs_block: str = "basic"           # "bottleneck" (resnetish50) is refused by name
+    bs_window_secs: float = 1.0       # the expert's constructor arguments as given
+    bs_hop_secs: float = 0.05
+    bs_bn_eps: float = 1e-5           # nn.BatchNorm2d's default
+
     # ---- derived -------------------------------------------------------------------------
     @property
     def conv_dim(self) -> int:
@@ -283,6 +293,8 @@ class EncoderConfig:
             return -(-self.conv_lengths(n)[-1] // self.decoar_subsample)
         if self.family == "mae_ast":  # time steps of kt frames; the frames behind the last whole step are dropped by nn.Unfold
             return self.conv_lengths(n)[-1] // self.ma_kt
+        if self.family == "byol_s":  # windows: frame_audio's loop (byol_s/serab_byols/utils.py:79-96)
+            return n // self.conv_layers[0][2] + 1 if n >= 0 else 0
         if self.family == "byol_a":  # segments: len(range(0, n, stride)) (byol_a/expert.py:85)
             return -(-n // self.conv_layers[0][2]) if n > 0 else 0
         if self.family == "vggish":  # examples: complete groups of vg_example_frames un-padded frames (audio.py:90-111)
@@ -308,7 +320,7 @@ class EncoderConfig:
             return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
         if self.family == "mockingjay":
             return min(T, max(self.num_frames(length), 0))
-        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "npc", "vggish", "byol_a"):  # byol_a: the utterance's own segments (the rows behind them are the reference's values, not zeros); vggish: the utterance's own examples, exact zeros behind them; distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
+        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "npc", "vggish", "byol_a", "byol_s"):  # byol_s: the utterance's own windows (the rows behind them are the reference's values, not zeros); byol_a: the utterance's own segments (the rows behind them are the reference's values, not zeros); vggish: the utterance's own examples, exact zeros behind them; distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -423,6 +435,8 @@ class EncoderConfig:
             return self._validate_byol_a()
         if self.family == "mae_ast":
             return self._validate_mae_ast()
+        if self.family == "byol_s":
+            return self._validate_byol_s()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.layer_type == "conformer":
@@ -642,6 +656,35 @@ class EncoderConfig:
             raise ValueError("byol_a norm_std and bn_eps must be positive")
         if self.encoder_embed_dim != d or self.encoder_layers != 0:
             raise ValueError("byol_a: encoder_embed_dim must be feature_d and encoder_layers 0 (byol_a_config sets them)")
+
+    def _validate_byol_s(self) -> None:
+        """What the HIP path builds of BYOL-S; everything else is refused by name (s3enc_create_byol_s repeats it)."""
+        if self.bs_network in ("cvt", "clstm"):
+            raise ValueError(f"byol_s network {self.bs_network} is not built (default and resnetish are)")
+        if self.bs_network not in ("default", "resnetish"):
+            raise ValueError(f"unknown byol_s network {self.bs_network!r}")
+        if self.bs_network == "resnetish":
+            if self.bs_block != "basic":
+                raise ValueError("byol_s Bottleneck blocks (resnetish50) are not built: BasicBlock layers only")
+            if len(self.bs_blocks) != 4 or any(not 1 <= int(b) <= 64 for b in self.bs_blocks):
+                raise ValueError(f"byol_s needs four layers of 1..64 BasicBlocks, got {tuple(self.bs_blocks)}")
+        if len(self.conv_layers) != 1:
+            raise ValueError("byol_s: conv_layers carries the window geometry as one (2048, window, step) entry (byol_s_config sets it)")
+        d, window, step = self.conv_layers[0]
+        if window <= 512:
+            raise ValueError(f"byol_s window of {window} samples is too short: a window of at most 512 samples cannot be reflect-padded "
+                             "by 512 (n_fft / 2)")
+        if self.bs_network == "default" and window < 1120:
+            raise ValueError(f"byol_s window of {window} samples is too short for the default network: fewer than 8 frames (1120 "
+                             "samples), nothing survives three 2 x 2 pools")
+        if step < 1:
+            raise ValueError(f"byol_s step must be at least one sample, got {step}")
+        if (window, step) != byol_s_samples(self.bs_window_secs, self.bs_hop_secs):
+            raise ValueError("byol_s: conv_layers does not match window_secs / hop_secs (byol_s_config sets it)")
+        if not self.bs_bn_eps > 0:
+            raise ValueError("byol_s bn_eps must be positive")
+        if d != 2048 or self.encoder_embed_dim != 2048 or self.encoder_layers != 0:
+            raise ValueError("byol_s: the state is 2048 wide and encoder_layers 0 (byol_s_config sets them)")
 
     @property
     def ma_tokens_per_step(self) -> int:
@@ -951,6 +994,24 @@ def vggish_config(layers=None, fc=(4096, 4096, 128), example_frames: int = 96, n
                         vg_example_frames=int(example_frames),
                         vg_example_hop=int(example_frames if example_hop is None else example_hop), vg_layers=pairs, vg_fc=fc,
                         vg_postprocess=bool(postprocess), vg_quant_min=float(quant_min), vg_quant_max=float(quant_max), **flags)
+    cfg.validate()
+    return cfg
+
+
+def byol_s_samples(window_secs: float, hop_secs: float) -> Tuple[int, int]:
+    """(window, step) in samples, with the reference's own expressions: expert.py:22-23 turns the seconds into milliseconds,
+    serab.py:151-153 and utils.py:72,79 turn those into samples."""
+    frame_duration, hop_size = window_secs * 1000, hop_secs * 1000
+    return int((frame_duration / 1000) * 16000), int(hop_size / 1000.0 * 16000)
+
+
+def byol_s_config(network: str = "default", blocks=(3, 4, 6, 3), window_secs: float = 1, hop_secs: float = 0.05, block: str = "basic",
+                  **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "byol_s" (byol_s/expert.py:12-28).  The samples, not the seconds, travel through the ABI."""
+    window, step = byol_s_samples(window_secs, hop_secs)
+    cfg = EncoderConfig(family="byol_s", conv_layers=[(2048, window, step)], encoder_layers=0, encoder_embed_dim=2048,
+                        bs_network=str(network), bs_blocks=tuple(int(b) for b in blocks), bs_block=str(block),
+                        bs_window_secs=float(window_secs), bs_hop_secs=float(hop_secs), **flags)
     cfg.validate()
     return cfg
 

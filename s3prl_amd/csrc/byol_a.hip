@@ -77,10 +77,13 @@ static int byol_a_check_config(const s3enc_config& c, const s3enc_byol_a_config&
     return 0;
 }
 
-static int byol_a_create(s3enc_encoder* e, const Ckpt& ck) {
-    const s3enc_byol_a_config& x = e->byol_a_cfg;
-    e->byol_a.reset(new ByolAW());
-    ByolAW& w = *e->byol_a;
+hipError_t launch_byol_tail(const float* y, int T8, int d, long nseg, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(byol_a_tail_kernel, dim3((unsigned)((nseg * d + 255) / 256)), dim3(256), 0, st, y, T8, d, nseg, out);
+    return hipGetLastError();
+}
+
+// AudioNTT2020's weights (BYOL-S's `default` network is the same module: byol_s.hip)
+int byol_a_load(ByolAW& w, const Ckpt& ck, long feature_d, float bn_eps) {
     std::vector<float> t, tt, packed, bias, g, b, rm, rv;
     int cin = 1;
     for (int i = 0; i < 3; ++i) {
@@ -99,7 +102,7 @@ static int byol_a_create(s3enc_encoder* e, const Ckpt& ck) {
         GET(bn + ".running_var", 64, rv);
         std::vector<float> sc(64), sh(64);
         for (int n = 0; n < 64; ++n) {
-            const double var = (double)rv[n] + (double)x.bn_eps;
+            const double var = (double)rv[n] + (double)bn_eps;
             if (!(var > 0.0)) return fail("checkpoint: " + bn + ".running_var[" + std::to_string(n) + "] + eps is not positive");
             const double s = (double)g[n] / std::sqrt(var);
             sc[n] = (float)s;
@@ -109,7 +112,7 @@ static int byol_a_create(s3enc_encoder* e, const Ckpt& ck) {
         UP(upload_f32(w.shift[i], sh));
         cin = 64;
     }
-    const long d = x.feature_d;
+    const long d = feature_d;
     GET("fc.0.weight", d * 512, t);
     UP(upload_f32(w.fw[0], t));
     GET("fc.0.bias", d, t);
@@ -121,127 +124,56 @@ static int byol_a_create(s3enc_encoder* e, const Ckpt& ck) {
     return 0;
 }
 
-static int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
-                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
-    const s3enc_byol_a_config& x = e->byol_a_cfg;
-    const ByolAW& w = *e->byol_a;
-    const int D = x.feature_d, L = x.window;
-    if (fo.selection != S3ENC_SEL_HIDDEN)
-        return fail("s3enc_forward: feature_selection is not defined for BYOL-A (the reference expert has one hidden_states list)");
-    if (fo.featurize && !fo.w) return fail("s3enc_forward: featurize needs feat_w");
-    if (!fo.featurize && fo.out_dtype != F32) return fail("s3enc_forward: out_dtype must be S3ENC_F32 for a BYOL-A handle");
-    if (e->aux_codewords || e->aux_codeids) return fail("s3enc_forward_aux: codewords / codeids are outputs of a wav2vec handle with a vector quantizer");
-    if (B > 65535) return fail("s3enc_forward: batch too large");
-    long n_max;
-    if (batch_n_max(wav_ptrs_host, lengths, B, n_max_in, n_max)) return 1;
-    const long S = byol_a_num_segments(x, n_max);
-    if (S < 1) return fail("s3enc_forward: an empty batch has no BYOL-A segment");
-    const long nseg = (long)B * S;
-    const int T = (int)s3::melspec_num_frames(L), T8 = T >> 3;
-    const long rows = nseg * T8;
-    if (nseg > (1L << 20) || rows * std::max(D, 512) > 0x7fffffffL) return fail("s3enc_forward: batch too large");
-    for (int b = 0; b < B; ++b) {
-        if (((uintptr_t)wav_ptrs_host[b]) & 3) return fail("s3enc_forward: utterance " + std::to_string(b) + " is not 4-byte aligned");
-        // stride > window only: the reference pads every utterance to starts[-1] + window and raises when that is shorter than it
-        if ((long)lengths[b] > (S - 1) * x.stride + L)
-            return fail("s3enc_forward: utterance " + std::to_string(b) + " has " + std::to_string((long)lengths[b]) + " samples, more than the " +
-                        std::to_string((S - 1) * x.stride + L) + " the " + std::to_string(S) + " segments of this batch reach (stride " +
-                        std::to_string(x.stride) + " > window " + std::to_string(L) + ": the reference's zero padding would be negative and it raises)");
-    }
-    if (check_out(out, fo, layer_stride, nseg * D)) return 1;
-    DeviceGuard dg(e->device);
-    if (!dg.ok) return fail("s3enc_forward: hipSetDevice failed");
+static int byol_a_create(s3enc_encoder* e, const Ckpt& ck) {
+    e->byol_a.reset(new ByolAW());
+    return byol_a_load(*e->byol_a, ck, e->byol_a_cfg.feature_d, e->byol_a_cfg.bn_eps);
+}
 
-    // ---- layer geometry: H = time, W = mel ----
-    struct Geo {
-        int H, W, C, Ho, Wo, pad;
-        size_t out_elems;
-    };
+// ---- the network behind the front end, on nseg bordered (T + 2) x (64 + 2) images: layer geometry with H = time, W = mel ----
+namespace {
+struct Geo {
+    int H, W, C, Ho, Wo, pad;
+    size_t out_elems;
+};
+void net_geo(long nseg, int T, Geo (&geo)[3]) {
+    int H = T, W = 64, C = 1;
+    for (int i = 0; i < 3; ++i) {
+        Geo& g = geo[i];
+        g.H = H;
+        g.W = W;
+        g.C = C;
+        g.Ho = H / 2;
+        g.Wo = W / 2;
+        g.pad = i == 2 ? 0 : 1;
+        g.out_elems = (size_t)nseg * (g.Ho + 2 * g.pad) * (g.Wo + 2 * g.pad) * 64;
+        H = g.Ho;
+        W = g.Wo;
+        C = 64;
+    }
+}
+}  // namespace
+
+int byol_a_net_plan(long nseg, int T, int D, Bump& wb, ByolANet& nb) {
     Geo geo[3];
-    {
-        int H = T, W = 64, C = 1;
-        for (int i = 0; i < 3; ++i) {
-            Geo& g = geo[i];
-            g.H = H;
-            g.W = W;
-            g.C = C;
-            g.Ho = H / 2;
-            g.Wo = W / 2;
-            g.pad = i == 2 ? 0 : 1;
-            g.out_elems = (size_t)nseg * (g.Ho + 2 * g.pad) * (g.Wo + 2 * g.pad) * 64;
-            if (g.out_elems * 4 >= (1ul << 32) - 64)
-                return fail("s3enc_forward: batch too large (" + std::to_string(nseg) + " segments: layer " + std::to_string(i) +
-                            "'s activation is not addressable with 32-bit offsets)");
-            H = g.Ho;
-            W = g.Wo;
-            C = 64;
-        }
+    net_geo(nseg, T, geo);
+    for (int i = 0; i < 3; ++i) {
+        if (geo[i].out_elems * 4 >= (1ul << 32) - 64)
+            return fail("s3enc_forward: batch too large (" + std::to_string(nseg) + " segments: layer " + std::to_string(i) +
+                        "'s activation is not addressable with 32-bit offsets)");
+        nb.act[i] = (float*)wb.take(geo[i].out_elems * 4);
     }
-    const size_t img_elems = (size_t)nseg * (T + 2) * 66;
-    if (img_elems * 4 >= (1ul << 32) - 64) return fail("s3enc_forward: batch too large");
-    const int fft = s3::tuning().melspec_fft;
+    for (int i = 0; i < 2; ++i) nb.fcb[i] = (float*)wb.take((size_t)nseg * (T >> 3) * D * 4);
+    return 0;
+}
 
-    // ---- the segment table: first sample and readable samples of segment b * S + s ----
-    const size_t ptr_bytes = (size_t)nseg * sizeof(const float*), tbl_bytes = ptr_bytes + (size_t)nseg * sizeof(int);
-    HIP_TRY(e->small.ensure_on_stream(tbl_bytes + 1024, st));
-    char* hp;
-    if (stage_begin(e, tbl_bytes, st, hp)) return 1;
-    {
-        const float** hptr = (const float**)hp;
-        int* hval = (int*)(hp + ptr_bytes);
-        for (int b = 0; b < B; ++b)
-            for (long s = 0; s < S; ++s) {
-                const long start = s * x.stride, left = (long)lengths[b] - start;
-                hptr[b * S + s] = left > 0 ? wav_ptrs_host[b] + start : wav_ptrs_host[b];
-                hval[b * S + s] = (int)(left > L ? L : (left < 0 ? 0 : left));
-            }
-    }
-    if (stage_commit(e, hp, e->small.p, tbl_bytes, st)) return 1;
-    const float* const* d_ptr = (const float* const*)e->small.p;
-    const int* d_val = (const int*)((char*)e->small.p + ptr_bytes);
-
-    // ---- workspace ----
-    float *img, *act[3], *fcb[2], *post = nullptr, *sig = nullptr, *spec = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {
-        Bump wb(pass ? e->ws.p : nullptr);
-        img = (float*)wb.take(img_elems * 4);
-        for (int i = 0; i < 3; ++i) act[i] = (float*)wb.take(geo[i].out_elems * 4);
-        for (int i = 0; i < 2; ++i) fcb[i] = (float*)wb.take((size_t)rows * D * 4);
-        if (fo.featurize) post = (float*)wb.take((size_t)nseg * D * 4);
-        if (!fft) {
-            sig = (float*)wb.take(s3::melspec_sig_elems(nseg, L) * 4);
-            spec = (float*)wb.take(s3::melspec_spec_elems(nseg, L) * 4);
-        }
-        if (!pass) HIP_TRY(e->ws.ensure_on_stream(wb.off + 4096, st));
-    }
-    e->taps.clear();
-
-    Sink sink{e, st, fo.featurize ? 2 : 0, out, (long)layer_stride, F32, nseg, D, fo.w, fo.feat_norm};
-    HIP_TRY(sink.zero_without_terms(1, nseg));
-
-    // ---- front end ----
-    {
-        const double frames = (double)nseg * T;
-        Prof pr(e, st, fft ? "melspec:fft" : "melspec:gemm", fft ? frames * 5e4 : frames * (2.0 * 1026 * 1024 + 4.0 * 513),
-                4.0 * ((double)nseg * L + (double)img_elems));
-        HIP_TRY(hipMemsetAsync(img, 0, img_elems * 4, st));
-        s3::MelspecParams m{};
-        m.ptrs = d_ptr;
-        m.valid = d_val;
-        m.nseg = (int)nseg;
-        m.L = L;
-        m.mean = x.norm_mean;
-        m.std_ = x.norm_std;
-        m.out = img + 66 + 1;
-        m.o_bs = (long)(T + 2) * 66;
-        m.o_row = 66;
-        m.fft = fft;
-        m.sig = sig;
-        m.spec = spec;
-        if (const char* why = s3::melspec_refusal(m)) return fail(std::string("s3enc_forward: the BYOL-A front end refuses: ") + why);
-        HIP_TRY(s3::launch_melspec(m, st));
-    }
-
+int byol_a_net_run(s3enc_encoder* e, const ByolAW& w, int D, const float* img, long nseg, int T, const ByolANet& nb, float* dst,
+                   hipStream_t st) {
+    Geo geo[3];
+    net_geo(nseg, T, geo);
+    const int T8 = T >> 3;
+    const long rows = nseg * T8;
+    float* const* act = nb.act;
+    float* const* fcb = nb.fcb;
     // ---- conv + BatchNorm + ReLU + floor pool, three times ----
     for (int i = 0; i < 3; ++i) {
         const Geo& g = geo[i];
@@ -298,16 +230,112 @@ static int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, con
             HIP_TRY(launch_relu(fcb[0], rows * D, st));
         }
     }
+    Prof pr(e, st, "byol_a_tail", 2.0 * rows * D, 4.0 * ((double)rows * D + (double)nseg * D));
+    HIP_TRY(launch_byol_tail(fcb[1], T8, D, nseg, dst, st));
+    return 0;
+}
+
+static int byol_a_forward(s3enc_handle e, const float* const* wav_ptrs_host, const int64_t* lengths, int32_t B, int64_t n_max_in,
+                   const FwdOpts& fo, void* out, int64_t layer_stride, hipStream_t st) {
+    const s3enc_byol_a_config& x = e->byol_a_cfg;
+    const ByolAW& w = *e->byol_a;
+    const int D = x.feature_d, L = x.window;
+    if (fo.selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_forward: feature_selection is not defined for BYOL-A (the reference expert has one hidden_states list)");
+    if (fo.featurize && !fo.w) return fail("s3enc_forward: featurize needs feat_w");
+    if (!fo.featurize && fo.out_dtype != F32) return fail("s3enc_forward: out_dtype must be S3ENC_F32 for a BYOL-A handle");
+    if (e->aux_codewords || e->aux_codeids) return fail("s3enc_forward_aux: codewords / codeids are outputs of a wav2vec handle with a vector quantizer");
+    if (B > 65535) return fail("s3enc_forward: batch too large");
+    long n_max;
+    if (batch_n_max(wav_ptrs_host, lengths, B, n_max_in, n_max)) return 1;
+    const long S = byol_a_num_segments(x, n_max);
+    if (S < 1) return fail("s3enc_forward: an empty batch has no BYOL-A segment");
+    const long nseg = (long)B * S;
+    const int T = (int)s3::melspec_num_frames(L), T8 = T >> 3;
+    const long rows = nseg * T8;
+    if (nseg > (1L << 20) || rows * std::max(D, 512) > 0x7fffffffL) return fail("s3enc_forward: batch too large");
+    for (int b = 0; b < B; ++b) {
+        if (((uintptr_t)wav_ptrs_host[b]) & 3) return fail("s3enc_forward: utterance " + std::to_string(b) + " is not 4-byte aligned");
+        // stride > window only: the reference pads every utterance to starts[-1] + window and raises when that is shorter than it
+        if ((long)lengths[b] > (S - 1) * x.stride + L)
+            return fail("s3enc_forward: utterance " + std::to_string(b) + " has " + std::to_string((long)lengths[b]) + " samples, more than the " +
+                        std::to_string((S - 1) * x.stride + L) + " the " + std::to_string(S) + " segments of this batch reach (stride " +
+                        std::to_string(x.stride) + " > window " + std::to_string(L) + ": the reference's zero padding would be negative and it raises)");
+    }
+    if (check_out(out, fo, layer_stride, nseg * D)) return 1;
+    DeviceGuard dg(e->device);
+    if (!dg.ok) return fail("s3enc_forward: hipSetDevice failed");
+
+    const size_t img_elems = (size_t)nseg * (T + 2) * 66;
+    const int fft = s3::tuning().melspec_fft;
+
+    // ---- the segment table: first sample and readable samples of segment b * S + s ----
+    const size_t ptr_bytes = (size_t)nseg * sizeof(const float*), tbl_bytes = ptr_bytes + (size_t)nseg * sizeof(int);
+    HIP_TRY(e->small.ensure_on_stream(tbl_bytes + 1024, st));
+    char* hp;
+    if (stage_begin(e, tbl_bytes, st, hp)) return 1;
+    {
+        const float** hptr = (const float**)hp;
+        int* hval = (int*)(hp + ptr_bytes);
+        for (int b = 0; b < B; ++b)
+            for (long s = 0; s < S; ++s) {
+                const long start = s * x.stride, left = (long)lengths[b] - start;
+                hptr[b * S + s] = left > 0 ? wav_ptrs_host[b] + start : wav_ptrs_host[b];
+                hval[b * S + s] = (int)(left > L ? L : (left < 0 ? 0 : left));
+            }
+    }
+    if (stage_commit(e, hp, e->small.p, tbl_bytes, st)) return 1;
+    const float* const* d_ptr = (const float* const*)e->small.p;
+    const int* d_val = (const int*)((char*)e->small.p + ptr_bytes);
+
+    // ---- workspace ----
+    float *img, *post = nullptr, *sig = nullptr, *spec = nullptr;
+    ByolANet nb;
+    for (int pass = 0; pass < 2; ++pass) {
+        Bump wb(pass ? e->ws.p : nullptr);
+        img = (float*)wb.take(img_elems * 4);
+        if (byol_a_net_plan(nseg, T, D, wb, nb)) return 1;
+        if (img_elems * 4 >= (1ul << 32) - 64) return fail("s3enc_forward: batch too large");
+        if (fo.featurize) post = (float*)wb.take((size_t)nseg * D * 4);
+        if (!fft) {
+            sig = (float*)wb.take(s3::melspec_sig_elems(nseg, L) * 4);
+            spec = (float*)wb.take(s3::melspec_spec_elems(nseg, L) * 4);
+        }
+        if (!pass) HIP_TRY(e->ws.ensure_on_stream(wb.off + 4096, st));
+    }
+    e->taps.clear();
+
+    Sink sink{e, st, fo.featurize ? 2 : 0, out, (long)layer_stride, F32, nseg, D, fo.w, fo.feat_norm};
+    HIP_TRY(sink.zero_without_terms(1, nseg));
+
+    // ---- front end ----
+    {
+        const double frames = (double)nseg * T;
+        Prof pr(e, st, fft ? "melspec:fft" : "melspec:gemm", fft ? frames * 5e4 : frames * (2.0 * 1026 * 1024 + 4.0 * 513),
+                4.0 * ((double)nseg * L + (double)img_elems));
+        HIP_TRY(hipMemsetAsync(img, 0, img_elems * 4, st));
+        s3::MelspecParams m{};
+        m.ptrs = d_ptr;
+        m.valid = d_val;
+        m.nseg = (int)nseg;
+        m.L = L;
+        m.mean = x.norm_mean;
+        m.std_ = x.norm_std;
+        m.out = img + 66 + 1;
+        m.o_bs = (long)(T + 2) * 66;
+        m.o_row = 66;
+        m.fft = fft;
+        m.sig = sig;
+        m.spec = spec;
+        if (const char* why = s3::melspec_refusal(m)) return fail(std::string("s3enc_forward: the BYOL-A front end refuses: ") + why);
+        HIP_TRY(s3::launch_melspec(m, st));
+    }
 
     e->taps["logmel"] = {img, (long)img_elems, F32};  // the bordered segments, (B S, frames + 2, 64 + 2)
-    e->taps["fc"] = {fcb[1], rows * D, F32};          // fc.3's output before its ReLU, (B S T / 8, d)
+    e->taps["fc"] = {nb.fcb[1], rows * D, F32};       // fc.3's output before its ReLU, (B S T / 8, d)
 
     float* dst = fo.featurize ? post : sink.slot32(0);
-    {
-        Prof pr(e, st, "byol_a_tail", 2.0 * rows * D, 4.0 * ((double)rows * D + (double)nseg * D));
-        hipLaunchKernelGGL(byol_a_tail_kernel, dim3((unsigned)((nseg * D + 255) / 256)), dim3(256), 0, st, fcb[1], T8, D, nseg, dst);
-        HIP_TRY(hipGetLastError());
-    }
+    if (byol_a_net_run(e, w, D, img, nseg, T, nb, dst, st)) return 1;
     if (sink.term(0)) {
         Prof pr(e, st, "emit_state", 0, 4.0 * nseg * D * 2);
         HIP_TRY(sink.emit(0, dst));

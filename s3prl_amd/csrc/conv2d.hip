@@ -30,6 +30,13 @@
 // (W / 2): odd maps pool as nn.MaxPool2d(2, 2) does and the dropped last row / column is never enumerated, while the operand's row
 // pitch and the kernel-row jump keep the true W.  WN = 1: a 64-wide n-tile for Cout <= 64 with all four waves along M.
 //
+// BYOL-S's additions (upstream/byol_s/byol_a/models/resnetish.py:23-102), the GEN instantiations: k x k taps, k = 3 or 1, at
+// padding (k - 1) / 2 and stride 1 or 2 over the same (H + 2) x (W + 2) operand, and a residual added behind the affine and before
+// the activation.  The K walk is k runs of k C floats (k = 1: one run of C floats of the pixel's own interior position), the jump
+// between two runs is (W + 2 - k) C floats, and only a row's first A offset knows the stride: output pixel (y, x) starts at bordered
+// pixel (y s + 1 - p, x s + 1 - p).  The M axis is the Ho x Wo OUTPUT pixels of all examples.  k = 3, s = 1 without a residual is bit
+// for bit the EXT instantiation; no pooling.
+//
 // conv2d3x3_first_kernel is the C = 1 layer (K = 9 is not matrix work): a VALU kernel, one thread per (pixel or window, 4 output
 // channels), an fmaf chain over the nine taps in the same order, the same epilogue.
 #include "kernels.h"
@@ -61,6 +68,12 @@ __device__ __forceinline__ float4 act4(float4 v, const float4& b, int act) {
 __device__ __forceinline__ float4 aff4(float4 v, const float4& s, const float4& t, int act) {
     v.x = act1(fmaf(v.x, s.x, t.x), act); v.y = act1(fmaf(v.y, s.y, t.y), act); v.z = act1(fmaf(v.z, s.z, t.z), act);
     v.w = act1(fmaf(v.w, s.w, t.w), act);
+    return v;
+}
+// the residual epilogue: act(acc * s + t + r), the fma first (a BasicBlock's bn2, then `out += identity`, then ReLU)
+__device__ __forceinline__ float4 res4(float4 v, const float4& s, const float4& t, const float4& r, int act) {
+    v.x = act1(fmaf(v.x, s.x, t.x) + r.x, act); v.y = act1(fmaf(v.y, s.y, t.y) + r.y, act); v.z = act1(fmaf(v.z, s.z, t.z) + r.z, act);
+    v.w = act1(fmaf(v.w, s.w, t.w) + r.w, act);
     return v;
 }
 template <bool EXT>
@@ -102,8 +115,9 @@ __device__ __forceinline__ void pixel_of(int m, int HW, int W, int pool, int& b,
 
 // WN = waves along N: 2 is the (64 TM) x 128 tile, 1 the (128 TM) x 64 tile for Cout <= 64 (all four waves along M; a wave's block,
 // fragments and K order are the same, so the bits are too).  EXT = the affine epilogue and floor pooling (an example's M extent is
-// 4 (H / 2) (W / 2): the dropped last row / column is never enumerated); EXT = false is VGGish's kernel as it was.
-template <int TM, int WN, bool EXT>
+// 4 (H / 2) (W / 2): the dropped last row / column is never enumerated); EXT = false is VGGish's kernel as it was.  GEN (with EXT):
+// k x k taps at stride 1 or 2 and the residual, no pooling.
+template <int TM, int WN, bool EXT, bool GEN = false>
 __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
     constexpr int BM = (4 / WN) * 32 * TM, BN = 64 * WN;
     constexpr int PLANE = (BM + BN) * ROWB;
@@ -117,7 +131,9 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
     const int half = lane >> 5;
     const int l31 = lane & 31;
 
-    const int HW = EXT && p.pool ? 4 * (p.H >> 1) * (p.W >> 1) : p.H * p.W;
+    const int KS = GEN ? p.k : 3;                                     // taps per kernel row
+    const int Wq = GEN ? conv2d_out(p.W, p.k, p.stride) : p.W;        // the width the M axis enumerates
+    const int HW = GEN ? conv2d_out(p.H, p.k, p.stride) * Wq : (EXT && p.pool ? 4 * (p.H >> 1) * (p.W >> 1) : p.H * p.W);
     const int M = p.B * HW;
     const int n_tiles = (p.N + BN - 1) / BN;
     int tile;
@@ -128,10 +144,10 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
     }
     const int tn = tile % n_tiles, tm = tile / n_tiles;
     const int m0 = tm * BM, n0 = tn * BN;
-    const int Kw = 9 * p.C;                  // floats per weight row
-    const int nkr = (3 * p.C) >> 4;          // 64-byte steps of one kernel row
+    const int Kw = KS * KS * p.C;            // floats per weight row
+    const int nkr = (KS * p.C) >> 4;         // 64-byte steps of one kernel row
     const int nk = Kw >> 4;
-    const unsigned jump = (unsigned)(p.W - 1) * (unsigned)p.C * 4u;  // A bytes skipped between two kernel rows
+    const unsigned jump = (unsigned)(p.W + 2 - KS) * (unsigned)p.C * 4u;  // A bytes skipped between two kernel rows
 
     i32x4 rsrc_a, rsrc_w;
     {
@@ -150,7 +166,11 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
             int r = m0 + 16 * wave + 64 * i + (lane >> 2);
             r = r < M ? r : M - 1;
             int b, y, x;
-            pixel_of(r, HW, p.W, p.pool, b, y, x);
+            pixel_of(r, HW, Wq, GEN ? 0 : p.pool, b, y, x);
+            if constexpr (GEN) {  // the first tap of output pixel (y, x): bordered pixel (y s + 1 - p, x s + 1 - p)
+                y = y * p.stride + (KS == 1);
+                x = x * p.stride + (KS == 1);
+            }
             voff[i] = ((unsigned)b * (unsigned)p.src_bs + (unsigned)(y * (p.W + 2) + x) * (unsigned)p.C) * 4u + src_slot * 16;
         } else {
             int r = n0 + 16 * wave + 64 * (i - APASS) + (lane >> 2);
@@ -252,7 +272,7 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
             for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * half) * 64 + j * 32 + l31] = acc[i][j][r];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         const int mb = m0 + wr * (TM * 32) + i * 32;
-        if (p.pool) {
+        if (!GEN && p.pool) {
             const int Wo = p.W >> 1;
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -273,10 +293,17 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
                 const int row = t * 4 + (lane >> 4);
                 const int m = mb + row;
                 if (m < M && n_ok) {
-                    const float4 v = ep4<EXT>(*(const float4*)(stg + row * 64 + c4), scale4, bias4, p.act);
                     int b, y, x;
-                    pixel_of(m, HW, p.W, 0, b, y, x);
-                    *(float4*)(p.dst + (long)b * p.dst_bs + ((long)(y + pad) * (p.W + 2 * pad) + x + pad) * p.ld_dst + n) = v;
+                    pixel_of(m, HW, Wq, 0, b, y, x);
+                    float4 v = *(const float4*)(stg + row * 64 + c4);
+                    if (GEN && p.res) {
+                        const int rp = p.res_pad;
+                        v = res4(v, scale4, bias4, *(const float4*)(p.res + (long)b * p.res_bs + ((long)(y + rp) * (Wq + 2 * rp) + x + rp) * p.ld_res + n),
+                                 p.act);
+                    } else {
+                        v = ep4<EXT>(v, scale4, bias4, p.act);
+                    }
+                    *(float4*)(p.dst + (long)b * p.dst_bs + ((long)(y + pad) * (Wq + 2 * pad) + x + pad) * p.ld_dst + n) = v;
                 }
             }
         }
@@ -285,18 +312,21 @@ __global__ __launch_bounds__(256, 2) void conv2d3x3_kernel(Conv2dParams p) {
 }
 
 // GEMM rows of the launch: every un-pooled pixel, or under pool the four pixels of every whole window
-long m_rows(const Conv2dParams& p) { return (long)p.B * (p.pool ? 4L * (p.H / 2) * (p.W / 2) : (long)p.H * p.W); }
+long m_rows(const Conv2dParams& p) {
+    if (p.gen) return (long)p.B * conv2d_out(p.H, p.k, p.stride) * conv2d_out(p.W, p.k, p.stride);
+    return (long)p.B * (p.pool ? 4L * (p.H / 2) * (p.W / 2) : (long)p.H * p.W);
+}
 
-template <int TM, int WN, bool EXT>
+template <int TM, int WN, bool EXT, bool GEN = false>
 hipError_t go(const Conv2dParams& p, hipStream_t stream) {
     constexpr int BM = (4 / WN) * 32 * TM, BN = 64 * WN;
     constexpr int plane2 = 2 * (BM + BN) * ROWB;
     constexpr int lds = plane2 > 4 * 8192 ? plane2 : 4 * 8192;
-    hipError_t e = ensure_dynamic_lds<conv2d3x3_kernel<TM, WN, EXT>>(lds);
+    hipError_t e = ensure_dynamic_lds<conv2d3x3_kernel<TM, WN, EXT, GEN>>(lds);
     if (e != hipSuccess) return e;
     const long M = m_rows(p);
     dim3 grid((unsigned)(((M + BM - 1) / BM) * ((p.N + BN - 1) / BN)));
-    hipLaunchKernelGGL((conv2d3x3_kernel<TM, WN, EXT>), grid, dim3(256), lds, stream, p);
+    hipLaunchKernelGGL((conv2d3x3_kernel<TM, WN, EXT, GEN>), grid, dim3(256), lds, stream, p);
     return hipGetLastError();
 }
 
@@ -372,13 +402,30 @@ const char* conv2d3x3_refusal(const Conv2dParams& p) {
     if (p.pool_floor && (p.H < 2 || p.W < 2)) return "the map is smaller than one 2 x 2 pool window";
     if ((p.scale != nullptr) != (p.shift != nullptr)) return "the affine needs both scale and shift";
     if (p.scale && p.bias) return "bias and an affine together: the shift carries the bias";
+    if (p.gen < 0 || p.gen > 1) return "gen must be 0 or 1";
+    if (!p.gen && (p.k || p.stride || p.res)) return "kernel size, stride and residual belong to the general form (gen = 1)";
+    if (p.gen) {
+        if (p.k != 1 && p.k != 3) return "the kernel size must be 3 or 1";
+        if (p.stride != 1 && p.stride != 2) return "the stride must be 1 or 2";
+        if (p.pool) return "the general form does not pool";
+        if (p.C == 1) return "the general form needs Cin to be a multiple of 16";
+        if (p.res) {
+            if (p.res_pad < 0) return "res border width must not be negative";
+            if (p.ld_res < p.N) return "the res pixel pitch is smaller than Cout";
+            if ((p.ld_res | p.res_bs) & 3) return "res pixel pitch and example stride must be multiples of 4 floats (vector loads)";
+            if ((uintptr_t)p.res & 15) return "operands must be 16-byte aligned";
+            const long Ho = conv2d_out(p.H, p.k, p.stride), Wo = conv2d_out(p.W, p.k, p.stride);
+            if (p.B > 1 && p.res_bs < (Ho + 2 * p.res_pad) * (Wo + 2 * p.res_pad) * p.ld_res) return "res example stride is smaller than one bordered image";
+        }
+    }
     if (p.dst_pad < 0) return "dst border width must not be negative";
     if (p.ld_dst < p.N) return "the dst pixel pitch is smaller than Cout";
     if ((p.ld_dst | p.dst_bs) & 3) return "dst pixel pitch and example stride must be multiples of 4 floats (vector stores)";
     if (p.C != 1 && (p.src_bs & 3)) return "src example stride must be a multiple of 4 floats";
     if (p.src_bs < (long)(p.H + 2) * (p.W + 2) * p.C) return "src example stride is smaller than one bordered image";
     {
-        const long Ho = p.pool ? p.H / 2 : p.H, Wo = p.pool ? p.W / 2 : p.W;
+        const long Ho = p.gen ? conv2d_out(p.H, p.k, p.stride) : (p.pool ? p.H / 2 : p.H);
+        const long Wo = p.gen ? conv2d_out(p.W, p.k, p.stride) : (p.pool ? p.W / 2 : p.W);
         if (p.B > 1 && p.dst_bs < (Ho + 2 * p.dst_pad) * (Wo + 2 * p.dst_pad) * p.ld_dst)
             return "dst example stride is smaller than one bordered image";
     }
@@ -386,7 +433,7 @@ const char* conv2d3x3_refusal(const Conv2dParams& p) {
         return "operands must be 16-byte aligned";
     if ((uintptr_t)p.src & 3) return "operands must be 4-byte aligned";
     const unsigned long a_span = (unsigned long)p.B * (unsigned long)p.src_bs * 4ul;
-    const unsigned long w_span = (unsigned long)p.N * 9ul * (unsigned long)p.C * 4ul;
+    const unsigned long w_span = (unsigned long)p.N * (p.gen ? (unsigned long)(p.k * p.k) : 9ul) * (unsigned long)p.C * 4ul;
     if (a_span >= (1ul << 32) - 64 || w_span >= (1ul << 32) - 64) return "an operand is not addressable with 32-bit offsets";
     const long M = m_rows(p);
     if (M > 0x7fffffffL - 256) return "too many pixels";
@@ -398,6 +445,13 @@ hipError_t launch_conv2d3x3(const Conv2dParams& p, hipStream_t stream) {
     if (conv2d3x3_refusal(p)) return hipErrorInvalidValue;
     // the instantiations with the affine epilogue / floor pooling / the 64-wide tile serve only the launches that ask for them
     const bool ext = p.scale || p.pool_floor || p.n64;
+    if (p.gen) {  // the tile rules of the instantiations below
+        const long M = m_rows(p);
+        if (p.n64 && p.N <= 64 && tuning().conv2d_n64)
+            return (M > 128 && (M + 255) / 256 >= device_cus()) ? go<2, 1, true, true>(p, stream) : go<1, 1, true, true>(p, stream);
+        const bool big = M > 64 && ((M + 127) / 128) * ((p.N + 127) / 128) >= device_cus();
+        return big ? go<2, 2, true, true>(p, stream) : go<1, 2, true, true>(p, stream);
+    }
     if (p.C == 1) {
         const long items = (long)p.B * (p.pool ? (p.H / 2) * (p.W / 2) : p.H * p.W) * (p.N / 4);
         dim3 grid((unsigned)((items + 255) / 256));

@@ -133,7 +133,7 @@ namespace {
 // The families that come with a second configuration block (FamilyOps, engine_internal.h), in the order their entries were added:
 // the one list of them the engine has.
 const FamilyOps* const kFamilies[] = {&kWav2vecFamily, &kCpcFamily,    &kApcFamily,   &kMockingjayFamily, &kDecoarFamily,
-                                      &kNpcFamily,     &kVggishFamily, &kByolAFamily, &kMaeAstFamily};
+                                      &kNpcFamily,     &kVggishFamily, &kByolAFamily, &kMaeAstFamily,     &kByolSFamily};
 const FamilyOps* family_ops(int family) {  // null: a Transformer family
     for (const FamilyOps* f : kFamilies)
         if (f->family == family) return f;
@@ -165,7 +165,7 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 13) return fail("config: unknown family");
+    if (c.family < 0 || c.family > 14) return fail("config: unknown family");
     if (family_ops(c.family)) return 0;  // its record's own check runs on both configuration blocks (create_impl)
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
@@ -307,6 +307,10 @@ int s3enc_create_byol_a(const s3enc_config* cfg, const s3enc_byol_a_config* byol
 int s3enc_create_mae_ast(const s3enc_config* cfg, const s3enc_mae_ast_config* mae_ast, const s3enc_tensor* tensors, int32_t n_tensors,
                          int32_t device, s3enc_handle* out) {
     return create_family(kMaeAstFamily, cfg, mae_ast, tensors, n_tensors, device, out);
+}
+int s3enc_create_byol_s(const s3enc_config* cfg, const s3enc_byol_s_config* byol_s, const s3enc_tensor* tensors, int32_t n_tensors,
+                        int32_t device, s3enc_handle* out) {
+    return create_family(kByolSFamily, cfg, byol_s, tensors, n_tensors, device, out);
 }
 
 static int create_impl(const s3enc_config* cfg, int own, const void* block, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device,

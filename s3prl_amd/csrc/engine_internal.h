@@ -12,6 +12,8 @@
 //   vggish.hip  VGGish: the un-padded log-mel examples, the 3 x 3 conv + pool stack on conv2d.hip, three Linears, the quantiser
 //   byol_a.hip  BYOL-A: per-segment FFT log-mel (melspec.hip), conv + BatchNorm + floor-pool on conv2d.hip, two Linears, max + mean
 //   mae_ast.hip MAE-AST: per-utterance kaldi fbank, the fused patch embedding (patchembed.hip), pre- / post-LN Transformer layers
+//   byol_s.hip  BYOL-S: centred windows -> hann(400) FFT log-mel -> whole-batch statistics -> ResNet on stem.hip + conv2d.hip (or BYOL-A's
+//               network) -> max + mean, the windows in chunks
 //   (a family file holds its configuration check, its weights, its forward schedule and its shape rules, and hands them to the engine
 //   as one FamilyOps record: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
@@ -448,6 +450,24 @@ struct ByolAW {
     DevBuf fw[2], fb[2];
 };
 
+// BYOL-S (byol_s.hip): the ResNet's stem (stem.hip's tap-major image) and per BasicBlock conv2d.hip's packed images with the
+// BatchNorms as per-channel scale / shift; `ntt` is the `default` network, AudioNTT2020 itself
+struct ByolSBlockW {
+    DevBuf w1, s1, t1, w2, s2, t2, wd, sd, td;  // conv1 / bn1, conv2 / bn2, downsample.0 / .1 (first block of layers 2-4)
+    int cin = 0, cout = 0, stride = 1;
+    bool down = false;
+};
+struct ByolSW {
+    DevBuf stem_w, stem_s, stem_t;
+    std::vector<ByolSBlockW> blocks;
+    ByolAW ntt;
+};
+// byol_a.hip's network behind its front end, shared with byol_s.hip: the workspace of nseg segments
+struct ByolANet {
+    float* act[3];
+    float* fcb[2];
+};
+
 // Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table, and per layer (ONE layer with
 // share_layer) q|k|v stacked as one (3 D, D) operand with q pre-scaled by head_dim^-0.5, the other projections and LayerNorm affines
 struct MjLayerW {
@@ -539,6 +559,8 @@ struct s3enc_encoder {
     s3enc_byol_a_config byol_a_cfg = {};  // ... and its second configuration block (s3enc_create_byol_a)
     std::unique_ptr<MaeAstW> mae_ast;   // S3ENC_MAE_AST
     s3enc_mae_ast_config mae_ast_cfg = {};  // ... and its second configuration block (s3enc_create_mae_ast)
+    std::unique_ptr<ByolSW> byol_s;     // S3ENC_BYOL_S
+    s3enc_byol_s_config byol_s_cfg = {};  // ... and its second configuration block (s3enc_create_byol_s)
     const FamilyOps* ops = nullptr;     // the record of a family with a second configuration block (set at create time)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
@@ -827,6 +849,13 @@ struct FamilyOps {
 // (read-only, but not declared const: the compiler would emit a constant-initialised const object into the device code as well, where
 // the host functions it points to do not exist)
 extern FamilyOps kWav2vecFamily, kCpcFamily, kApcFamily, kMockingjayFamily, kDecoarFamily, kNpcFamily, kVggishFamily, kByolAFamily,
-    kMaeAstFamily;
+    kMaeAstFamily, kByolSFamily;
+
+// byol_a.hip, for byol_s.hip: AudioNTT2020's weights, its workspace (taken from `wb`; fails when a layer is not addressable with 32-bit
+// offsets), the network on nseg bordered (T + 2) x (64 + 2) images up to dst (nseg, D), and out = max_t relu(y) + mean_t relu(y)
+int byol_a_load(ByolAW& w, const Ckpt& ck, long feature_d, float bn_eps);
+int byol_a_net_plan(long nseg, int T, int D, Bump& wb, ByolANet& nb);
+int byol_a_net_run(s3enc_encoder* e, const ByolAW& w, int D, const float* img, long nseg, int T, const ByolANet& nb, float* dst, hipStream_t st);
+hipError_t launch_byol_tail(const float* y, int T8, int d, long nseg, float* out, hipStream_t st);
 
 }  // namespace s3e

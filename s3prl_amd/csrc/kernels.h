@@ -100,6 +100,12 @@ struct Tuning {
     int patch_embed_fused = 1;  // patchembed.hip: 1 = the patch embedding as ONE implicit GEMM that reads the image in place, 0 = a gather kernel
                            // that writes the (B * tokens, kt * kc) rows, the tile GEMM, then the position add (the yardstick and a second
                            // implementation, held to the fixture bound; the A/B of profiles/mae_ast_fp32.md)
+    int stem_fused = 0;    // byol_s.hip: 1 = the ResNet stem as one kernel (stem.hip: conv 7 x 7 + affine + ReLU + 3 x 3 / stride-2 pool, 2.25 x the
+                           // multiply-adds, no un-pooled map), 0 = the un-pooled map and a pool kernel (bit-identical; measured 223.0
+                           // against 222.2 ms per forward: profiles/byol_s_fp32.md)
+    int byol_s_chunk = 1024;  // byol_s.hip: windows per pass of the network; bounds the workspace (about 6.2 MB per window), never changes a
+                           // window's bits; 128 / 256 / 512 / 1024: 246.9 / 222.2 / 207.5 / 193.2 ms per 32 x 10 s byol_s_resnetish34 forward
+                           // (the late layers' few pixels per window fill the chip only across many windows: profiles/byol_s_fp32.md)
     int comm_self_p2p = 0; // comm.hip, S3ENC_EXCHANGE_DIRECT: 1 = a rank's OWN block also travels as an ncclSend-to-self / ncclRecv-from-self
                            // pair inside the state's group instead of a device copy — on a one-GPU box this is the only way the
                            // all-pairs code (symbols, counts, datatype, group bracketing, stream order behind the layer events)
@@ -254,10 +260,45 @@ struct Conv2dParams {
     int pool_floor;      // under pool: odd H / W allowed, Ho = H / 2 and Wo = W / 2 rounded down (nn.MaxPool2d's floor mode); the
                          // dropped last row / column is never computed
     int n64;             // 1: Cout <= 64 may run on the 64-wide n-tile (tuning().conv2d_n64); same bits as the 128-wide one
+    // BYOL-S's additions (the ResNet's layers); all zero is the launch as it was
+    int gen;             // 1: the general instantiation: k x k taps at padding (k - 1) / 2 and stride 1 or 2 over the SAME bordered
+                         // (H + 2) x (W + 2) operand, Ho = (H + 2 p - k) / stride + 1 as nn.Conv2d rounds, the epilogue act(acc *
+                         // scale[n] + shift[n] + res[pixel][n]); no pooling, C a multiple of 16.  k = 3, stride = 1, no residual is
+                         // bit for bit the launch without `gen`
+    int k;               // with gen: 3, or 1 (Wt is then the plain (N, C) matrix and the border is never read)
+    int stride;          // with gen: 1 or 2
+    const float* res;    // with gen, or null: example b at res + b * res_bs, output pixel (y, x) at + ((y + res_pad) * (Wo + 2 res_pad)
+    long res_bs;         // + x + res_pad) * ld_res; added behind the affine and before the activation (a BasicBlock's identity)
+    int res_pad;
+    long ld_res;
 };
 void pack_conv2d3x3(const float* w, int N, int C, std::vector<float>& out);  // host: nn.Conv2d's (N, C, 3, 3) -> the kernel's image
 const char* conv2d3x3_refusal(const Conv2dParams& p);  // null, or why launch_conv2d3x3 would refuse
 hipError_t launch_conv2d3x3(const Conv2dParams& p, hipStream_t stream);
+__host__ __device__ inline int conv2d_out(int H, int k, int stride) { return (H + 2 * ((k - 1) / 2) - k) / stride + 1; }  // nn.Conv2d's output size
+
+// stem.hip: BYOL-S's ResNet stem on single-channel (H, 64) images, exact fp32 on the VALU (K = 49 is not matrix work): a 7 x 7
+// convolution at stride 1 and padding 3 to 64 channels, the per-channel affine (an eval-mode BatchNorm), ReLU, and MaxPool2d(3, 2, 1):
+// Hp = (H - 1) / 2 + 1 rows of 32 pixels.  fused = 1: one kernel, every pooled pixel computes the 3 x 3 un-pooled pixels of its window
+// (2.25 x the multiply-adds, the un-pooled map never exists); fused = 0: the un-pooled map is written to `map`, a second kernel pools
+// it.  Both forms walk the 49 taps in one order and give the same bits.  Every pooled value is behind the ReLU (negative zero is
+// written as +0), so the zero border of `map` stands for -inf padding; a NaN stays a NaN.
+struct StemParams {
+    const float* src;    // example b at src + b * src_bs: an (H + 8) x (64 + 8) image whose 4 outermost rows / columns are zeros
+    long src_bs;
+    int H, B;
+    const float* Wt;     // pack_stem7x7: (49, 64), tap-major
+    const float* scale;  // [64]
+    const float* shift;  // [64]
+    float* dst;          // example b at dst + b * dst_bs: an (Hp + 2) x (32 + 2) x 64 image; its interior is written, its border never touched
+    long dst_bs;
+    int fused;
+    float* map;          // fused = 0: example b at map + b * map_bs, an (H + 2) x (64 + 2) x 64 image with a zero border
+    long map_bs;
+};
+void pack_stem7x7(const float* w, std::vector<float>& out);  // host: nn.Conv2d's (64, 1, 7, 7) -> (49, 64)
+const char* stem_refusal(const StemParams& p);               // null, or why launch_stem would refuse
+hipError_t launch_stem(const StemParams& p, hipStream_t stream);
 
 // patchembed.hip: exact-fp32 patch embedding of (frames, 128) images as an implicit GEMM over the tokens of all utterances (MAE-AST's
 // nn.Unfold((kt, kc), stride = kernel) + Linear + position row): token t * V + v of utterance b is the kt x kc patch at image row
@@ -656,6 +697,12 @@ struct MelspecParams {
     int fft;                   // 1 the FFT kernel, 0 the GEMM form (needs sig and spec)
     float* sig;                // GEMM form: melspec_sig_elems floats, 16-byte aligned
     float* spec;               // GEMM form: melspec_spec_elems floats
+    // BYOL-S's additions; all zero is the launch as it was
+    int win400;                // 1: MelSpectrogram(win_length = 400): a periodic hann(400) zero-padded to 1024 with 312 zeros in front
+                               // (torch.stft's centring of a short window), a second window table of the FFT kernel; the FFT form only,
+                               // and L only has to exceed 512 (the 8-frame rule is BYOL-A's network's)
+    const int* lead;           // device [nseg] or null: samples of segment i before lead[i] are zeros (a window that starts in front of
+                               // its utterance); ptrs[i] is then only ever read at offsets lead[i] .. valid[i] - 1
 };
 const char* melspec_refusal(const MelspecParams& p);  // null, or why launch_melspec would refuse
 hipError_t launch_melspec(const MelspecParams& p, hipStream_t st);

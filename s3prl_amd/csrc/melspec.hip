@@ -4,6 +4,8 @@
 //   count are zeros: the utterance's zero padding)  ->  1 + L / 160 frames of 1024 samples every 160  ->  periodic hann(1024)
 //   ->  |X|^2 over 513 one-sided bins, no normalisation  ->  64 HTK triangles in Hz between mel-spaced points (f_min 60, f_max 7800,
 //   norm = None, over linspace(0, 8000, 513))  ->  (log(mel + FLT_EPSILON) - mean) / std, written as (segment, frame, mel).
+// BYOL-S (upstream/byol_s/serab_byols/serab.py:136-144) runs the same front end with win_length = 400: torch.stft zero-pads the
+// periodic hann(400) to 1024 with 312 zeros on either side — a second window table of the FFT kernel (win400), nothing else.
 //
 // Two forms of the spectrum (tuning key melspec_fft):
 //   1  melspec_fft_kernel, one workgroup of 256 threads per frame: the windowed frame packed as 512 complex numbers z[n] = x[2n] +
@@ -29,10 +31,11 @@ namespace {
 constexpr int NFFT = 1024, NBIN = 513, HOP = 160, NMEL = 64, HALF = 512;
 
 // sample i of frame t of a segment: padded position n = 160 t + i - 512 reflected about 0 and about L - 1 (L > 512: one reflection)
-__device__ __forceinline__ float seg_sample(const float* src, int nv, int L, int n) {
+// (samples before `lo` are zeros too: a BYOL-S window that starts in front of its utterance)
+__device__ __forceinline__ float seg_sample(const float* src, int nv, int L, int n, int lo = 0) {
     if (n < 0) n = -n;
     if (n >= L) n = 2 * (L - 1) - n;
-    return n < nv ? src[n] : 0.f;
+    return n >= lo && n < nv ? src[n] : 0.f;
 }
 
 // band m's sum over its own bins, ascending, then log and the affine: shared by both forms
@@ -46,7 +49,7 @@ __device__ __forceinline__ float mel_value(const float* pw, const int* bands, co
 
 __global__ __launch_bounds__(256) void melspec_fft_kernel(const float* const* ptrs, const int* valid, int L, int T, const float2* tw,
                                                           const float* win, const int* bands, const float* wts, float mean, float std_,
-                                                          float* out, long o_bs, long o_row, float* power) {
+                                                          float* out, long o_bs, long o_row, float* power, const int* lead) {
     __shared__ float2 za[HALF], zb[HALF];
     __shared__ float pw[NBIN + 3];
     const int tid = threadIdx.x;
@@ -55,11 +58,12 @@ __global__ __launch_bounds__(256) void melspec_fft_kernel(const float* const* pt
     const float* src = ptrs[seg];
     int nv = valid[seg];
     nv = nv < 0 ? 0 : (nv > L ? L : nv);
+    const int lo = lead ? lead[seg] : 0;
     const int base = t * HOP - HALF;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int n = tid + 256 * h;
-        za[n] = make_float2(seg_sample(src, nv, L, base + 2 * n) * win[2 * n], seg_sample(src, nv, L, base + 2 * n + 1) * win[2 * n + 1]);
+        za[n] = make_float2(seg_sample(src, nv, L, base + 2 * n, lo) * win[2 * n], seg_sample(src, nv, L, base + 2 * n + 1, lo) * win[2 * n + 1]);
     }
     __syncthreads();
     float2 *in = za, *ot = zb;
@@ -122,6 +126,7 @@ __global__ __launch_bounds__(256) void melspec_mel_kernel(const float* spec, int
 struct MelspecPlan {
     float2* tw = nullptr;   // e^(-2 pi i m / 1024), m = 0..512
     float* win = nullptr;   // periodic hann(1024)
+    float* win400 = nullptr;  // periodic hann(400) behind 312 zeros and in front of 312 (MelSpectrogram(win_length = 400) at n_fft = 1024)
     int* bands = nullptr;   // [3][64]: first bin, bins, offset into wts
     float* wts = nullptr;   // the non-zero triangle weights, band by band
     float* dft = nullptr;   // the GEMM form's (2 * 513, 1024) matrix, built on first use
@@ -147,8 +152,11 @@ hipError_t build_plan(MelspecPlan& pl) {
     std::vector<int> bands;
     std::vector<float> wts;
     melspec_bank(bands, wts);
+    std::vector<float> win400(NFFT, 0.f);
+    for (int i = 0; i < 400; ++i) win400[(NFFT - 400) / 2 + i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / 400));
     hipError_t e = to_device(&pl.tw, tw);
     if (e == hipSuccess) e = to_device(&pl.win, win);
+    if (e == hipSuccess) e = to_device(&pl.win400, win400);
     if (e == hipSuccess) e = to_device(&pl.bands, bands);
     if (e == hipSuccess) e = to_device(&pl.wts, wts);
     return e;
@@ -205,7 +213,10 @@ const char* melspec_refusal(const MelspecParams& p) {
     if (!p.ptrs || !p.valid || !p.out) return "null operand";
     if (p.nseg < 1) return "no segments";
     if (p.L <= 512) return "a segment of at most 512 samples cannot be reflect-padded by 512 (n_fft / 2)";
-    if (p.L < 1120) return "a segment below 1120 samples has fewer than 8 frames: nothing survives three 2 x 2 pools";
+    if (p.win400 < 0 || p.win400 > 1) return "win400 must be 0 or 1";
+    if (!p.win400 && p.L < 1120) return "a segment below 1120 samples has fewer than 8 frames: nothing survives three 2 x 2 pools";
+    if (p.win400 && !p.fft) return "the 400-sample window is built for the FFT form only";
+    if (p.lead && !p.fft) return "leading zeros are built for the FFT form only";
     if (p.L > (1 << 24)) return "segment too long";
     const long T = melspec_num_frames(p.L);
     if ((long)p.nseg * T > 0x7fffffffL / (2 * NBIN) || p.nseg > 65535 * 16) return "too many frames";
@@ -230,8 +241,8 @@ hipError_t launch_melspec(const MelspecParams& p, hipStream_t st) {
     }
     const unsigned frames = (unsigned)(p.nseg * T);
     if (p.fft) {
-        hipLaunchKernelGGL(melspec_fft_kernel, dim3(frames), dim3(256), 0, st, p.ptrs, p.valid, p.L, (int)T, pl->tw, pl->win, pl->bands,
-                           pl->wts, p.mean, p.std_, p.out, p.o_bs, p.o_row, p.power);
+        hipLaunchKernelGGL(melspec_fft_kernel, dim3(frames), dim3(256), 0, st, p.ptrs, p.valid, p.L, (int)T, pl->tw,
+                           p.win400 ? pl->win400 : pl->win, pl->bands, pl->wts, p.mean, p.std_, p.out, p.o_bs, p.o_row, p.power, p.lead);
         return hipGetLastError();
     }
     const long Lp = (p.L + NFFT + 3) & ~3L;

@@ -29,6 +29,7 @@ int tuning_set(Tuning& t, const char* key, int value, const char** err) {
         {"rnn_split", &Tuning::rnn_split, -1, 8},           {"npc_skip_taps", &Tuning::npc_skip_taps, 0, 1},
         {"conv2d_n64", &Tuning::conv2d_n64, 0, 1},           {"melspec_fft", &Tuning::melspec_fft, 0, 1},
         {"patch_embed_fused", &Tuning::patch_embed_fused, 0, 1},
+        {"stem_fused", &Tuning::stem_fused, 0, 1},           {"byol_s_chunk", &Tuning::byol_s_chunk, 1, 4096},
         {"gemm32_tail", &Tuning::gemm32_tail, 0, 2},         {"gemm32_tail_units", &Tuning::gemm32_tail_units, 0, 1 << 20},
     };
     static thread_local char msg[160];
@@ -580,25 +581,28 @@ int s3enc_op_conv2d3x3_affine(const float* x, const float* w_host, const float* 
     return 0;
 }
 
-int s3enc_op_melspec1024(const float* segments, int32_t nseg, int32_t L, float* out, float* power, void* stream) {
-    if (!segments || !out) return fail("s3enc_op_melspec1024: null argument");
-    if (nseg <= 0 || nseg > 65535) return fail("s3enc_op_melspec1024: nseg must be 1..65535");
+// the two front-end entries: BYOL-A's (hann(1024), its precomputed statistics) and BYOL-S's (hann(400) in 1024, un-normalised)
+static int op_melspec(const std::string& who, int win400, float mean, float std_, const float* segments, int32_t nseg, int32_t L, float* out,
+                      float* power, void* stream) {
+    if (!segments || !out) return fail(who + ": null argument");
+    if (nseg <= 0 || nseg > 65535) return fail(who + ": nseg must be 1..65535");
     MelspecParams p{};
     p.nseg = nseg;
     p.L = L;
-    p.mean = -5.4919195f;
-    p.std_ = 5.0389895f;
+    p.mean = mean;
+    p.std_ = std_;
+    p.win400 = win400;
     p.out = out;
     p.o_row = 64;
     p.o_bs = melspec_num_frames(L > 0 ? L : 0) * 64;
     p.power = power;
-    p.fft = tuning().melspec_fft;
+    p.fft = win400 ? 1 : tuning().melspec_fft;
     static const float* const stand_in_ptr = nullptr;
     static const int stand_in_val = 0;
     p.ptrs = &stand_in_ptr;  // the checks that need no device memory first
     p.valid = &stand_in_val;
     p.sig = p.spec = out;
-    if (const char* why = melspec_refusal(p)) return fail(std::string("s3enc_op_melspec1024: ") + why);
+    if (const char* why = melspec_refusal(p)) return fail(who + ": " + why);
     std::vector<const float*> hp(nseg);
     std::vector<int> hv(nseg, L);
     for (int i = 0; i < nseg; ++i) hp[i] = segments + (size_t)i * L;
@@ -618,6 +622,91 @@ int s3enc_op_melspec1024(const float* segments, int32_t nseg, int32_t L, float* 
     }
     HIP_TRY(launch_melspec(p, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the tables and the scratch are freed on return
+    return 0;
+}
+
+int s3enc_op_melspec1024(const float* segments, int32_t nseg, int32_t L, float* out, float* power, void* stream) {
+    return op_melspec("s3enc_op_melspec1024", 0, -5.4919195f, 5.0389895f, segments, nseg, L, out, power, stream);
+}
+
+int s3enc_op_melspec400(const float* segments, int32_t nseg, int32_t L, float* out, float* power, void* stream) {
+    return op_melspec("s3enc_op_melspec400", 1, 0.f, 1.f, segments, nseg, L, out, power, stream);
+}
+
+int s3enc_op_conv2d_res(const float* x, const float* w_host, const float* bias, const float* scale, const float* shift, const float* res,
+                        int32_t B, int32_t H, int32_t W, int32_t C, int32_t N, int32_t k, int32_t stride, int32_t act, float* dst,
+                        int32_t dst_pad, int64_t ldo, void* stream) {
+    if (!x || !w_host || !dst) return fail("s3enc_op_conv2d_res: null argument");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0) return fail("s3enc_op_conv2d_res: bad shape");
+    if (H > 32768 || W > 32768 || B > (1 << 24)) return fail("s3enc_op_conv2d_res: bad shape");
+    Conv2dParams p{};
+    p.src = x;
+    p.src_bs = (long)(H + 2) * (W + 2) * C;
+    p.C = C;
+    p.bias = bias;
+    p.scale = scale;
+    p.shift = shift;
+    p.H = H;
+    p.W = W;
+    p.N = N;
+    p.B = B;
+    p.act = act;
+    p.n64 = 1;
+    p.gen = 1;
+    p.k = k;
+    p.stride = stride;
+    p.dst = dst;
+    p.dst_pad = dst_pad;
+    p.ld_dst = ldo;
+    alignas(16) static float stand_in[4];  // the checks that need no device memory first
+    p.Wt = stand_in;
+    if ((k == 1 || k == 3) && (stride == 1 || stride == 2)) {
+        const long Ho = conv2d_out(H, k, stride), Wo = conv2d_out(W, k, stride);
+        p.dst_bs = (Ho + 2 * (long)dst_pad) * (Wo + 2 * (long)dst_pad) * ldo;
+        p.res = res;  // a plain contiguous (B, Ho, Wo, N) tensor
+        p.res_bs = Ho * Wo * N;
+        p.ld_res = N;
+    }
+    if (const char* why = conv2d3x3_refusal(p)) return fail(std::string("s3enc_op_conv2d_res: ") + why);
+    std::vector<float> packed;
+    if (k == 3)
+        pack_conv2d3x3(w_host, N, C, packed);
+    else
+        packed.assign(w_host, w_host + (size_t)N * C);  // nn.Conv2d's (N, C, 1, 1) is the kernel's (N, C)
+    DevBuf dw;
+    HIP_TRY(upload_f32(dw, packed));
+    p.Wt = (const float*)dw.p;
+    HIP_TRY(launch_conv2d3x3(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
+    return 0;
+}
+
+int s3enc_op_stem7x7_pool(const float* x, const float* w_host, const float* scale, const float* shift, int32_t B, int32_t H, int32_t fused,
+                          float* dst, float* map, void* stream) {
+    if (!x || !w_host || !scale || !shift || !dst) return fail("s3enc_op_stem7x7_pool: null argument");
+    if (B <= 0 || H <= 0 || H > 32768 || B > (1 << 20)) return fail("s3enc_op_stem7x7_pool: bad shape");
+    StemParams p{};
+    p.src = x;
+    p.src_bs = (long)(H + 8) * 72;
+    p.H = H;
+    p.B = B;
+    p.scale = scale;
+    p.shift = shift;
+    p.dst = dst;
+    p.dst_bs = (long)((H - 1) / 2 + 3) * 34 * 64;
+    p.fused = fused;
+    p.map = map;
+    p.map_bs = (long)(H + 2) * 66 * 64;
+    alignas(16) static float stand_in[4];  // the checks that need no device memory first
+    p.Wt = stand_in;
+    if (const char* why = stem_refusal(p)) return fail(std::string("s3enc_op_stem7x7_pool: ") + why);
+    std::vector<float> packed;
+    pack_stem7x7(w_host, packed);
+    DevBuf dw;
+    HIP_TRY(upload_f32(dw, packed));
+    p.Wt = (const float*)dw.p;
+    HIP_TRY(launch_stem(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
     return 0;
 }
 

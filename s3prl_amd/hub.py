@@ -21,6 +21,7 @@ from .upstream.vq_apc.hubconf import *  # noqa: F401,F403
 from .upstream.npc.hubconf import *  # noqa: F401,F403
 from .upstream.vggish.hubconf import *  # noqa: F401,F403
 from .upstream.byol_a.hubconf import *  # noqa: F401,F403
+from .upstream.byol_s.hubconf import *  # noqa: F401,F403
 from .upstream.mae_ast.hubconf import *  # noqa: F401,F403
 from .upstream.decoar.hubconf import *  # noqa: F401,F403
 from .upstream.decoar_layers.hubconf import *  # noqa: F401,F403

@@ -76,12 +76,21 @@ def featurize_data_parallel(encode_fn: Callable[[List[torch.Tensor], int], torch
     return out[:B]
 
 
+def refuse_whole_batch_family(expert) -> None:
+    """BYOL-S normalises every window with the mean and std of ALL windows of the batch (byol_s/serab_byols/utils.py:31-48): a
+    shard would compute other statistics and every row of the state would change.  Refused by name."""
+    if getattr(expert, "family", None) == "byol_s":
+        raise ValueError("byol_s cannot be sharded over ranks: its log-mel statistics belong to the whole batch, and a shard would "
+                         "compute different ones")
+
+
 def featurized_data_parallel(expert, weights: Sequence[float], wavs: Sequence[torch.Tensor], normalize: bool = False,
                              group=None) -> torch.Tensor:
     """Data-parallel encode with the Featurizer's weighted sum computed INSIDE the encoder (``s3enc_forward_ex``
     featurize epilogue): every rank produces only its shard's (Bs, T, D) weighted sum and ONE all-gather
     reassembles the batch — the per-layer slab is neither written nor exchanged.  ``weights``: one float per layer
     (softmax already applied).  Returns (B, T, D) fp32, identical on every rank, input order."""
+    refuse_whole_batch_family(expert)
     return featurize_data_parallel(lambda mine, n_max: expert.encode_featurized(mine, weights, normalize, n_max=n_max),
                                    lambda feat: feat, wavs, group)
 
@@ -247,6 +256,7 @@ class DataParallelUpstream(torch.nn.Module):
 
     def __init__(self, expert, group=None, overlap: bool = True, algo: str = "ring"):
         super().__init__()
+        refuse_whole_batch_family(expert)
         self.expert = expert
         self.group = group
         self.overlap = overlap

@@ -36,6 +36,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _vggish_shapes(cfg)
     if cfg.family == "byol_a":
         return _byol_a_shapes(cfg)
+    if cfg.family == "byol_s":
+        return _byol_s_shapes(cfg)
     if cfg.family == "mae_ast":
         return _mae_ast_shapes(cfg)
     s: Dict[str, tuple] = {}
@@ -315,6 +317,36 @@ def mae_ast_sine_table(rows: int, D: int) -> np.ndarray:
     return pe
 
 
+def _byol_s_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """BYOL-S's networks under the reference's plain state_dict names.  ``default``: AudioNTT2020(n_mels=64, d=2048), BYOL-A's names
+    (upstream/byol_s/byol_a/models/audio_ntt.py).  ``resnetish``: ResNetish(BasicBlock, blocks) (models/resnetish.py:159-290): the
+    7 x 7 stem, and per block two bias-free 3 x 3 convolutions with their BatchNorms; the first block of layers 2-4 carries the 1 x 1
+    ``downsample``.  ``num_batches_tracked`` is training state and is not listed."""
+    if cfg.bs_network == "default":
+        return _byol_a_shapes(cfg)
+    s: Dict[str, tuple] = {"conv1.weight": (64, 1, 7, 7)}
+
+    def bn(name, c):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            s[f"{name}.{leaf}"] = (c,)
+
+    bn("bn1", 64)
+    cin = 64
+    for L, n_blocks in enumerate(cfg.bs_blocks):
+        planes = 64 << L
+        for b in range(n_blocks):
+            pre = f"layer{L + 1}.{b}"
+            s[f"{pre}.conv1.weight"] = (planes, cin, 3, 3)
+            bn(f"{pre}.bn1", planes)
+            s[f"{pre}.conv2.weight"] = (planes, planes, 3, 3)
+            bn(f"{pre}.bn2", planes)
+            if b == 0 and (L > 0 or cin != planes):
+                s[f"{pre}.downsample.0.weight"] = (planes, cin, 1, 1)
+                bn(f"{pre}.downsample.1", planes)
+            cin = planes
+    return s
+
+
 def _decoar_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
     """Decoar (upstream/decoar/decoar.py:21-39), the checkpoint's names: the projection and the two multi-layer nn.LSTM modules
     (decoar_layers/expert.py:35-47 renames them to its per-layer modules; both experts read this one file)."""
@@ -538,6 +570,17 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
                  "running_mean": lambda: 0.3 * rng.standard_normal(shape), "running_var": lambda: rng.uniform(0.5, 2.0, size=shape)}[leaf]()
         elif cfg.family == "byol_a" and leaf == "weight":
             w = rng.standard_normal(shape) * np.sqrt(2.0 / int(np.prod(shape[1:])))  # He scaling, as for VGGish
+        elif cfg.family == "byol_s" and cfg.bs_network == "default" and name.split(".")[1] in ("1", "5", "9") and name.startswith("features."):
+            w = {"weight": lambda: 1.0 + 0.2 * rng.standard_normal(shape), "bias": lambda: 0.2 * rng.standard_normal(shape),
+                 "running_mean": lambda: 0.3 * rng.standard_normal(shape), "running_var": lambda: rng.uniform(0.5, 2.0, size=shape)}[leaf]()
+        elif cfg.family == "byol_s" and len(shape) == 1 and cfg.bs_network == "resnetish":
+            # eval-mode BatchNorm statistics that do something, running variances well away from zero; the BatchNorm that closes a
+            # residual branch (bn2, downsample.1) at half gain, so that sixteen additions do not double the map sixteen times
+            gain = 0.5 if (".bn2." in name or ".downsample.1." in name) else 1.0
+            w = {"weight": lambda: gain * (1.0 + 0.2 * rng.standard_normal(shape)), "bias": lambda: 0.2 * rng.standard_normal(shape),
+                 "running_mean": lambda: 0.3 * rng.standard_normal(shape), "running_var": lambda: rng.uniform(0.5, 2.0, size=shape)}[leaf]()
+        elif cfg.family == "byol_s" and leaf == "weight":
+            w = rng.standard_normal(shape) * np.sqrt(2.0 / int(np.prod(shape[1:])))  # He scaling through every conv and Linear
         elif cfg.family == "vggish" and leaf == "weight":
             # He scaling, sqrt(2 / fan_in), through every conv and Linear: ReLU then keeps the second moment of the log-mel input
             # (RMS 3-4 for unit-variance PCM) up to the embedding, about half of whose elements are exact zeros
@@ -801,6 +844,19 @@ def named_config(name: str) -> EncoderConfig:
         from .config import mae_ast_config
 
         return mae_ast_config(**mae_ast[name])
+    # BYOL-S: centred windows, hann(400) log-mel, whole-batch statistics, AudioNTT2020 or a ResNet of BasicBlocks, mean + max
+    byol_s = {
+        "byol_s_default": dict(network="default"), "byol_s_resnetish34": dict(network="resnetish", blocks=(3, 4, 6, 3)),
+        "tiny_byol_s_default": dict(network="default", window_secs=0.25, hop_secs=0.1),
+        "tiny_byol_s_resnetish10": dict(network="resnetish", blocks=(1, 1, 1, 1)),
+        # 26 frames -> 13 -> 7 -> 4 -> 2: odd at two levels
+        "tiny_byol_s_resnetish10_win025": dict(network="resnetish", blocks=(1, 1, 1, 1), window_secs=0.25, hop_secs=0.1),
+        "tiny_byol_s_resnetish10_hop02": dict(network="resnetish", blocks=(1, 1, 1, 1), window_secs=0.5, hop_secs=0.2),
+    }
+    if name in byol_s:
+        from .config import byol_s_config
+
+        return byol_s_config(**byol_s[name])
     # Mockingjay / TERA / AudioALBERT: a log-mel (or kaldi fbank) front end into post-LN BERT layers, long inputs in chunks
     tiny_mj = dict(hidden=128, layers=2, heads=2, intermediate=256, input_dim=16, sequence_length=0)
     mj = {
@@ -823,7 +879,7 @@ def named_config(name: str) -> EncoderConfig:
 
         return mockingjay_config(**mj[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(byol_a) + list(mae_ast) + list(mj))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(byol_a) + list(byol_s) + list(mae_ast) + list(mj))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
