@@ -940,6 +940,20 @@ int s3enc_op_conv_taps(const float* x, const float* w_host, const float* bias, i
                        int32_t mask, int32_t act, const float* res, int64_t ld_res, float* dst, int32_t dst_pad, int64_t ldo,
                        float* state, float* sum, int32_t sum_init, int32_t dense, void* stream);
 
+/* nn.Conv1d(C, C, 3, stride = 2) without padding on channel-last rows, exact fp32, in the two-output form (convf22.hip; conv1-4 of
+ * the HuBERT / wav2vec 2.0 / WavLM / data2vec extractors in the S3ENC_F32 mode):
+ *   out[b][t][:] = act(W[:, :, 0] x[b][2t] + W[:, :, 1] x[b][2t + 1] + W[:, :, 2] x[b][2t + 2] + bias),  t in [0, M),
+ *   act 0 none / 1 GELU (the tuning key "gelu32" chooses its form, as everywhere in the fp32 mode).
+ * x: device fp32, utterance b's frames at x + b * x_bs; frames [0, 2M] are read and nothing behind frame 2M is.  w_host: HOST fp32
+ * (C, C, 3), nn.Conv1d's layout; packed tap-major, with the (C, C) sum of taps 0 and 2 beside it, by the code s3enc_create uses,
+ * and uploaded inside.  bias: device fp32 [C] or null.  row_limit: device int32 [B] or null: rows [row_limit[b], M) of utterance b
+ * are written as +0.0.  out: utterance b's rows at out + b * o_bs; rows [0, M) only are written.  There is no other kernel behind
+ * this entry; refused by message: the tuning key "conv_f22" = 0, C not a multiple of 32, x_bs < (2M + 1) C (frame 2M must exist),
+ * o_bs < M C, strides that are not multiples of 4 floats, pointers that are not 16-byte aligned, null x / w_host / out.  A row's
+ * bits depend on its three frames and the weights only: not on M, B, its utterance's place, or the grid.  Synchronises. */
+int s3enc_op_conv_k3s2(const float* x, int64_t x_bs, const float* w_host, const float* bias, const int32_t* row_limit, int32_t B,
+                       int32_t M, int32_t C, int32_t act, float* out, int64_t o_bs, void* stream);
+
 /* Stride-1 nn.Conv2d(C, N, 3, padding = 1) on channel-last images, exact fp32, with bias -> act -> optional nn.MaxPool2d(2, 2) in
  * one pass (conv2d.hip; VGGish's features stack):
  *   v[b][y][x][:] = act(sum_{ky, kx} W[:, :, ky, kx] img[b][y + ky][x + kx] + bias),  act 0 none / 1 ReLU;

@@ -218,6 +218,7 @@ _PROTOS = {
     "s3enc_pack_lstm_bidir_whh": (C.c_int, [_VP, _I32, _VP]),
     "s3enc_op_conv_taps": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _I64, _VP, _VP,
                                      _I32, _I32, _VP]),
+    "s3enc_op_conv_k3s2": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _I64, _VP]),
     "s3enc_op_conv2d3x3": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
     "s3enc_op_conv2d3x3_affine": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
     "s3enc_op_melspec1024": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),

@@ -265,24 +265,41 @@ __global__ __launch_bounds__(256, 2) void conv_f22_kernel(ConvF22Params p) {
     }
 }
 
-}  // namespace
-
-// Batch-independent by construction: it depends on C and the buffers only, never on B, M or a tile picker.
-bool conv_f22_eligible(const ConvF22Params& p) {
-    if (!tuning().conv_f22 || !p.x || !p.W || !p.WP || !p.out) return false;
-    if (p.C < 32 || (p.C & 31) || (p.x_bs & 3) || (p.o_bs & 3)) return false;
+// the part of the refusal that depends on C and the buffers only, never on B, M or a tile picker
+const char* ineligible(const ConvF22Params& p) {
+    if (!tuning().conv_f22) return "the tuning key conv_f22 is 0 (the two-output kernel is switched off)";
+    if (!p.x || !p.W || !p.WP || !p.out) return "null operand";
+    if (p.C < 32 || (p.C & 31)) return "C must be a multiple of 32 (each K phase is an even number of 64-byte steps)";
+    if ((p.x_bs & 3) || (p.o_bs & 3)) return "batch strides must be multiples of 4 floats (vector accesses)";
     const uintptr_t al = (uintptr_t)p.x | (uintptr_t)p.W | (uintptr_t)p.WP | (uintptr_t)p.out | (uintptr_t)p.bias;
-    if (al & 15) return false;
+    if (al & 15) return "operands must be 16-byte aligned";
     // 32-bit buffer offsets: frames up to 2M of an utterance, the whole (C, 3C) weight
     const unsigned long x_span = ((unsigned long)p.x_bs + (unsigned long)p.C) * 4ul;
     const unsigned long w_span = (unsigned long)p.C * 3ul * (unsigned long)p.C * 4ul;
-    return x_span < (1ul << 32) - 64 && w_span < (1ul << 32) - 64;
+    if (x_span >= (1ul << 32) - 64 || w_span >= (1ul << 32) - 64) return "an operand is not addressable with 32-bit offsets";
+    return nullptr;
+}
+
+}  // namespace
+
+// Batch-independent by construction: it depends on C and the buffers only, never on B, M or a tile picker.
+bool conv_f22_eligible(const ConvF22Params& p) { return !ineligible(p); }
+
+const char* conv_f22_refusal(const ConvF22Params& p) {
+    if (const char* why = ineligible(p)) return why;
+    if (p.M < 1 || p.batches < 1) return "bad shape";
+    if (p.act < 0 || p.act > 2) return "act must be 0 (none) or 1 (GELU)";
+    if ((2L * p.M + 1) * p.C > p.x_bs) return "x_bs is smaller than (2M + 1) C: frame 2M must exist";
+    if ((long)p.M * p.C > p.o_bs) return "o_bs is smaller than M C";
+    const long tiles = (long)p.batches * ((p.M + BM - 1) / BM) * ((p.C + BN - 1) / BN);
+    if (tiles > 0x7fffffffL) return "too many tiles";
+    return nullptr;
 }
 
 hipError_t launch_conv_f22(const ConvF22Params& p0, hipStream_t stream) {
     ConvF22Params p = p0;
     if (p.M <= 0 || p.batches <= 0) return hipSuccess;
-    if (!conv_f22_eligible(p) || (2L * p.M + 1) * p.C > p.x_bs) return hipErrorInvalidValue;  // frame 2M must exist
+    if (conv_f22_refusal(p)) return hipErrorInvalidValue;
     if (p.act == 1 && tuning().gelu32 == 1) p.act = 2;  // as launch_gemm: the one-transcendental GELU of the fp32 mode
     constexpr int lds = 2 * PLANE;
     hipError_t e = ensure_dynamic_lds<conv_f22_kernel>(lds);

@@ -57,6 +57,13 @@ void tap_major(const std::vector<float>& t, int cout, int cin, int k, std::vecto
             for (int j = 0; j < k; ++j) o[((long)co * k + j) * cin + ci] = t[((long)co * cin + ci) * k + j];
 }
 
+void pack_conv_f22(const std::vector<float>& t, int C, std::vector<float>& w, std::vector<float>& wp) {
+    tap_major(t, C, C, 3, w);
+    wp.resize((size_t)C * C);
+    for (int co = 0; co < C; ++co)
+        for (int ci = 0; ci < C; ++ci) wp[(size_t)co * C + ci] = w[(long)co * 3 * C + ci] + w[(long)co * 3 * C + 2 * C + ci];
+}
+
 int load_rnn_layer(const Ckpt& ck, const std::string& prefix, const std::string& suffix, int G, int H, int I, RnnW& w) {
     std::vector<float> t, t2;
     w.w_ih.emplace_back();
@@ -388,19 +395,17 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
         if (i == 0) {
             UP(upload_f32(e->conv[i].w, t));  // [C][k]
         } else {
-            tap_major(t, C, cin, k, t2);  // W'[co][j*Cin + ci], the K order of the channel-last implicit GEMM
+            const bool f22 = e->dtype == F32 && !e->x3 && k == 3 && c.conv_stride[i] == 2;  // convf22.hip's WP = fl(W0 + W2)
+            std::vector<float> wp;
+            if (f22) pack_conv_f22(t, C, t2, wp);  // (cin = C from conv1 on; t2 is tap_major's image)
+            else tap_major(t, C, cin, k, t2);  // W'[co][j*Cin + ci], the K order of the channel-last implicit GEMM
             if (e->x2_conv_f32_from && i >= e->x2_conv_f32_from) {
                 UP(upload_gemm_w(e->conv[i].w, t2, C, (long)k * cin, e->dtype, e->x2));  // (read only if the three-term path declines)
             } else {
                 UPW(e->conv[i].w, t2, C, (long)k * cin, 1);
             }
             if (e->x3 || (e->x2_conv_f32_from && i >= e->x2_conv_f32_from)) UP(upload_x3(e->conv[i].w3, t2, C, (long)k * cin));
-            if (e->dtype == F32 && !e->x3 && k == 3 && c.conv_stride[i] == 2) {  // convf22.hip's WP = fl(W0 + W2)
-                std::vector<float> wp((size_t)C * cin);
-                for (int co = 0; co < C; ++co)
-                    for (int ci = 0; ci < cin; ++ci) wp[(size_t)co * cin + ci] = t2[(long)co * 3 * cin + ci] + t2[(long)co * 3 * cin + 2 * cin + ci];
-                UP(upload_f32(e->conv[i].wp, wp));
-            }
+            if (f22) UP(upload_f32(e->conv[i].wp, wp));
         }
         if (c.conv_bias) {
             GET(p + ".0.bias", C, t);

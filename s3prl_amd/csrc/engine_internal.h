@@ -74,6 +74,9 @@ struct Ckpt {
     } while (0)
 // (Cout, Cin, k) as nn.Conv1d holds it -> tap-major [co][j * Cin + ci]: the K order of the channel-last implicit GEMM
 void tap_major(const std::vector<float>& t, int cout, int cin, int k, std::vector<float>& o);
+// convf22.hip's weights from nn.Conv1d's (C, C, 3): w = tap_major's (C, 3C) image, wp = (C, C) fl(W0 + W2).  s3enc_create and
+// s3enc_op_conv_k3s2 both pack through here
+void pack_conv_f22(const std::vector<float>& t, int C, std::vector<float>& w, std::vector<float>& wp);
 
 // ---- host-side dtype conversion -------------------------------------------------------------------------
 inline uint16_t h_bf16(float f) {

@@ -209,6 +209,7 @@ struct ConvF22Params {
     long o_bs;
 };
 bool conv_f22_eligible(const ConvF22Params& p);  // tuning().conv_f22, C a multiple of 32, alignment, 32-bit offsets
+const char* conv_f22_refusal(const ConvF22Params& p);  // null, or why launch_conv_f22 would refuse (eligibility, then M, B, x_bs, o_bs)
 hipError_t launch_conv_f22(const ConvF22Params& p, hipStream_t stream);
 // convtaps.hip: exact-fp32 stride-1 Conv1d on channel-last rows whose K walk is up to two tap runs (NPC's masked convolutions:
 // the masked taps in the middle are neither fetched nor multiplied), with a pre-activation residual and up to three destinations.

@@ -504,6 +504,38 @@ int s3enc_op_conv_taps(const float* x, const float* w_host, const float* bias, i
     return 0;
 }
 
+int s3enc_op_conv_k3s2(const float* x, int64_t x_bs, const float* w_host, const float* bias, const int32_t* row_limit, int32_t B, int32_t M,
+                       int32_t C, int32_t act, float* out, int64_t o_bs, void* stream) {
+    if (!x || !w_host || !out) return fail("s3enc_op_conv_k3s2: null argument");
+    if (B <= 0 || M <= 0 || C <= 0) return fail("s3enc_op_conv_k3s2: bad shape");
+    if (act < 0 || act > 1) return fail("s3enc_op_conv_k3s2: act must be 0 (none) or 1 (GELU)");
+    ConvF22Params p{};
+    p.x = x;
+    p.x_bs = x_bs;
+    p.bias = bias;
+    p.M = M;
+    p.C = C;
+    p.batches = B;
+    p.act = act;
+    p.row_limit = row_limit;
+    p.out = out;
+    p.o_bs = o_bs;
+    alignas(16) static float stand_in[4];  // the checks that need no device memory first
+    p.W = p.WP = stand_in;
+    if (const char* why = conv_f22_refusal(p)) return fail(std::string("s3enc_op_conv_k3s2: ") + why);
+    if (((uintptr_t)row_limit) & 3) return fail("s3enc_op_conv_k3s2: row_limit must be 4-byte aligned");
+    std::vector<float> w(w_host, w_host + (size_t)C * C * 3), packed, wp;
+    pack_conv_f22(w, C, packed, wp);
+    DevBuf dw, dwp;
+    HIP_TRY(upload_f32(dw, packed));
+    HIP_TRY(upload_f32(dwp, wp));
+    p.W = (const float*)dw.p;
+    p.WP = (const float*)dwp.p;
+    HIP_TRY(launch_conv_f22(p, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
+    return 0;
+}
+
 int s3enc_op_conv2d3x3(const float* x, const float* w_host, const float* bias, int32_t B, int32_t H, int32_t W, int32_t C, int32_t N,
                        int32_t act, int32_t pool, float* dst, int32_t dst_pad, int64_t ldo, void* stream) {
     if (!x || !w_host || !dst) return fail("s3enc_op_conv2d3x3: null argument");
