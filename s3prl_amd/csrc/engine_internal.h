@@ -443,7 +443,7 @@ struct VggishW {
     std::vector<DevBuf> cw, cb;
     DevBuf fw[3], fb[3];
     DevBuf pca, pca_mean;
-    DevBuf dft, melT;
+    DevBuf dft, bands, wts;  // the folded hann x DFT operand; the mel matrix band by band (spectral.h's sparsify)
 };
 
 // BYOL-A (byol_a.hip): per conv layer conv2d.hip's packed image (taps transposed: the image is time x mel) and the BatchNorm as the

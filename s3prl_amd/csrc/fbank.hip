@@ -7,36 +7,20 @@
 // spectrum of every frame is then a GEMM whose A rows OVERLAP in the raw waveform (row t starts at sample 160 t:
 // lda = 160 < K = 400) — the same implicit-GEMM addressing as the strided convs, served by gemm.hip's exact-fp32 MFMA
 // kernel straight from the caller's PCM.  Three small HBM-bound kernels finish the job:
-//   fbank_mel_kernel   |X|^2 -> 80 triangular mel filters -> log(max(., eps))          (one workgroup per frame)
+//   mel_rows_kernel    |X|^2 -> 80 triangular mel filters -> log(max(., eps))          (spectral.h, one workgroup per frame)
 //   fbank_delta_kernel delta and delta-delta with replicate padding                     (thread per (t, bin))
-//   fbank_cmvn_kernel  per-dimension mean / unbiased std over time, two-pass, in place  (workgroup per dimension)
+//   cmvn_kernel        per-dimension mean / unbiased std over time, two-pass, in place  (spectral.hip, workgroup per dimension)
 #include <cmath>
 #include <map>
 #include <mutex>
 #include <vector>
 
 #include "kernels.h"
+#include "spectral.h"
 
 namespace s3 {
 
 namespace {
-
-__global__ __launch_bounds__(128) void fbank_mel_kernel(const float* spec, int nbin, int ldspec, const float* banksT, int nmel,
-                                                        float eps, float* out, int ldo) {
-    extern __shared__ float pw[];
-    const long t = blockIdx.x;
-    const float* s = spec + t * ldspec;
-    for (int k = threadIdx.x; k < nbin; k += blockDim.x) {
-        const float re = s[k], im = s[nbin + k];
-        pw[k] = re * re + im * im;
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < nmel; b += blockDim.x) {
-        float acc = 0.f;
-        for (int k = 0; k < nbin; ++k) acc = fmaf(pw[k], banksT[k * nmel + b], acc);
-        out[t * ldo + b] = logf(fmaxf(acc, eps));
-    }
-}
 
 // out[t][nmel*(o+1) + b] = delta of order o+1; d[t] = sum_k k * x[clamp(t+k)] / denom  (replicate padding)
 __global__ void fbank_delta_kernel(float* out, long T, int nmel, int ldo, int order, int n, float inv_denom) {
@@ -59,33 +43,10 @@ __global__ void fbank_delta_kernel(float* out, long T, int nmel, int ldo, int or
     }
 }
 
-__global__ __launch_bounds__(256) void fbank_cmvn_kernel(float* x, long T, int ldo, float eps) {
-    __shared__ double red[4];
-    const int f = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    auto block_sum = [&](double v) {
-        v = wave_sum_d(v);
-        __syncthreads();
-        if (lane == 0) red[wave] = v;
-        __syncthreads();
-        return red[0] + red[1] + red[2] + red[3];
-    };
-    double s = 0.0;
-    for (long t = threadIdx.x; t < T; t += 256) s += x[t * ldo + f];
-    const double mean = block_sum(s) / (double)T;
-    double q = 0.0;
-    for (long t = threadIdx.x; t < T; t += 256) {
-        const double d = x[t * ldo + f] - mean;
-        q += d * d;
-    }
-    const double var = block_sum(q) / (double)(T - 1);  // unbiased (torch.std default); T == 1 -> nan like torch
-    const float inv = (float)(1.0 / ((double)eps + sqrt(var)));
-    for (long t = threadIdx.x; t < T; t += 256) x[t * ldo + f] = (float)((x[t * ldo + f] - mean)) * inv;
-}
-
 struct FbankPlan {
     int size, shift, padded, nbin, nmel;
     float* dft = nullptr;     // (2*nbin, size) fp32: rows 0..nbin-1 cos, nbin.. -sin, pre-processing folded in
-    float* banksT = nullptr;  // (nbin, nmel)
+    MelBank bank;             // the kaldi bank, band by band
 };
 // Scratch is per (device, STREAM): the plan's constants are shared, but two experts / two streams running the same
 // configuration concurrently must not share the spectrum workspace (re-use within one stream is stream-ordered).
@@ -118,45 +79,8 @@ hipError_t build_plan(FbankPlan& pl, int nmel, int size, int shift, double preem
         const int ip = i == 0 ? 0 : i - 1;
         for (int j = 0; j < N; ++j) D[(size_t)i * N + j] = w * (tmp[(size_t)i * N + j] - preemph * tmp[(size_t)ip * N + j]);
     }
-    std::vector<float> M((size_t)2 * nb * N);
-    std::vector<double> c(N), s(N);
-    for (int r = 0; r < nb; ++r) {
-        for (int i = 0; i < N; ++i) {
-            const double a = 2.0 * M_PI * (double)((long)r * i % pl.padded) / pl.padded;
-            c[i] = std::cos(a);
-            s[i] = -std::sin(a);
-        }
-        for (int j = 0; j < N; ++j) {
-            double re = 0.0, im = 0.0;
-            for (int i = 0; i < N; ++i) {
-                re += c[i] * D[(size_t)i * N + j];
-                im += s[i] * D[(size_t)i * N + j];
-            }
-            M[(size_t)r * N + j] = (float)re;
-            M[(size_t)(nb + r) * N + j] = (float)im;
-        }
-    }
-    // kaldi mel banks (no VTLN): low 20 Hz, high = Nyquist, triangles in mel space; Nyquist column zero
-    std::vector<float> bT((size_t)nb * nmel, 0.f);
-    auto mel = [](double f) { return 1127.0 * std::log(1.0 + f / 700.0); };
-    const double lo = mel(20.0), hi = mel(0.5 * sample_rate), delta = (hi - lo) / (nmel + 1);
-    const double width = (double)sample_rate / pl.padded;
-    for (int b = 0; b < nmel; ++b) {
-        const double left = lo + b * delta, center = left + delta, right = center + delta;
-        for (int k = 0; k < nb - 1; ++k) {
-            const double m = mel(width * k);
-            const double up = (m - left) / (center - left), down = (right - m) / (right - center);
-            const double v = std::fmax(0.0, std::fmin(up, down));
-            bT[(size_t)k * nmel + b] = (float)v;
-        }
-    }
-    hipError_t e = hipMalloc((void**)&pl.dft, M.size() * 4);
-    if (e != hipSuccess) return e;
-    e = hipMemcpy(pl.dft, M.data(), M.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return e;
-    e = hipMalloc((void**)&pl.banksT, bT.size() * 4);
-    if (e != hipSuccess) return e;
-    return hipMemcpy(pl.banksT, bT.data(), bT.size() * 4, hipMemcpyHostToDevice);
+    hipError_t e = to_device(&pl.dft, fold_dft_dense(D.data(), N, pl.padded));
+    return e != hipSuccess ? e : upload_bank(pl.bank, kaldi_bank(nb, nmel, sample_rate, pl.padded), nb, nmel);
 }
 
 }  // namespace
@@ -220,8 +144,8 @@ hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* o
     g.o_bs = 0;
     e = launch_gemm(F32, g, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fbank_mel_kernel, dim3((unsigned)T), dim3(128), pl.nbin * sizeof(float), st, sc.spec, pl.nbin, N2,
-                       pl.banksT, pl.nmel, 1.1920928955078125e-07f, out, ldo);
+    hipLaunchKernelGGL((mel_rows_kernel<POWER, LogFloor>), dim3((unsigned)T), dim3(128), pl.nbin * sizeof(float), st, sc.spec, pl.nbin,
+                       (int)T, pl.bank.bands, pl.bank.wts, pl.nmel, LogFloor{FLT_EPSILON}, out, 0L, (long)ldo, nullptr);
     if (c.delta_order > 0) {
         const int nw = (c.delta_win - 1) / 2;
         const float inv = 3.0f / (float)(nw * (nw + 1) * (2 * nw + 1));
@@ -230,7 +154,7 @@ hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* o
                            c.delta_order, nw, inv);
     }
     if (c.use_cmvn)
-        hipLaunchKernelGGL(fbank_cmvn_kernel, dim3(pl.nmel * (c.delta_order + 1)), dim3(256), 0, st, out, T, ldo, c.cmvn_eps);
+        launch_cmvn(out, nullptr, (int)T, pl.nmel * (c.delta_order + 1), 1, ldo, 0, c.cmvn_eps, st);
     return hipGetLastError();
 }
 

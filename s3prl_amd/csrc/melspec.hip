@@ -13,9 +13,9 @@
 //      order: a frame's bits depend on its 1024 samples only), the split X[k] = (Z[k] + Z*[512 - k]) / 2 + e^(-2 pi i k / 1024)
 //      (Z[k] - Z*[512 - k]) / 2i, the power, the sparse mel sum (band m walks its own bins in ascending order), log and the affine.
 //      Twiddles come from one float64-built table e^(-2 pi i m / 1024), m = 0..512.  About 50 kFLOP per frame; 10 KiB LDS, no scratch.
-//   0  fbank.hip's / logmel.hip's form at K = 1024: melspec_pad_kernel materialises every reflect-padded segment, the spectrum is an
+//   0  fbank.hip's / logmel.hip's form at K = 1024: spectral.h's reflect_pad_kernel materialises every reflect-padded segment, the spectrum is an
 //      overlapping-row GEMM (lda = 160) against hann x DFT folded in float64 into a (2 x 513) x 1024 matrix (2.1 MFLOP per frame), and
-//      melspec_mel_kernel is the same power -> mel -> log -> affine epilogue.  The yardstick and the fallback.
+//      mel_rows_kernel is the same power -> mel -> log -> affine epilogue.  The yardstick and the fallback.
 #include <cfloat>
 #include <cmath>
 #include <map>
@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "spectral.h"
 
 namespace s3 {
 
@@ -36,15 +37,6 @@ __device__ __forceinline__ float seg_sample(const float* src, int nv, int L, int
     if (n < 0) n = -n;
     if (n >= L) n = 2 * (L - 1) - n;
     return n >= lo && n < nv ? src[n] : 0.f;
-}
-
-// band m's sum over its own bins, ascending, then log and the affine: shared by both forms
-__device__ __forceinline__ float mel_value(const float* pw, const int* bands, const float* wts, int m, float mean, float std_) {
-    const int lo = bands[m], n = bands[NMEL + m];
-    const float* w = wts + bands[2 * NMEL + m];
-    float acc = 0.f;
-    for (int i = 0; i < n; ++i) acc = fmaf(pw[lo + i], w[i], acc);
-    return (logf(acc + FLT_EPSILON) - mean) / std_;
 }
 
 __global__ __launch_bounds__(256) void melspec_fft_kernel(const float* const* ptrs, const int* valid, int L, int T, const float2* tw,
@@ -94,52 +86,18 @@ __global__ __launch_bounds__(256) void melspec_fft_kernel(const float* const* pt
         if (prow) prow[k] = v;
     }
     __syncthreads();
-    if (tid < NMEL) out[seg * o_bs + t * o_row + tid] = mel_value(pw, bands, wts, tid, mean, std_);
-}
-
-__global__ __launch_bounds__(256) void melspec_pad_kernel(const float* const* ptrs, const int* valid, int L, long Lp, float* sig) {
-    const int seg = blockIdx.y;
-    const long j = (long)blockIdx.x * 256 + threadIdx.x;
-    if (j >= Lp) return;
-    int nv = valid[seg];
-    nv = nv < 0 ? 0 : (nv > L ? L : nv);
-    sig[(long)seg * Lp + j] = j < L + NFFT ? seg_sample(ptrs[seg], nv, L, (int)j - HALF) : 0.f;
-}
-
-// one workgroup per frame of the GEMM form: row r of `spec` is (re[513] | im[513])
-__global__ __launch_bounds__(256) void melspec_mel_kernel(const float* spec, int T, const int* bands, const float* wts, float mean,
-                                                          float std_, float* out, long o_bs, long o_row, float* power) {
-    __shared__ float pw[NBIN + 3];
-    const long r = blockIdx.x;
-    const int seg = (int)(r / T), t = (int)(r - (long)seg * T);
-    const float* s = spec + r * (2L * NBIN);
-    for (int k = threadIdx.x; k < NBIN; k += 256) {
-        const float re = s[k], im = s[NBIN + k];
-        const float v = re * re + im * im;
-        pw[k] = v;
-        if (power) power[r * NBIN + k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NMEL) out[seg * o_bs + t * o_row + threadIdx.x] = mel_value(pw, bands, wts, threadIdx.x, mean, std_);
+    if (tid < NMEL) out[seg * o_bs + t * o_row + tid] = LogAffine{mean, std_}(mel_band_sum(pw, bands, wts, NMEL, tid));
 }
 
 struct MelspecPlan {
     float2* tw = nullptr;   // e^(-2 pi i m / 1024), m = 0..512
     float* win = nullptr;   // periodic hann(1024)
     float* win400 = nullptr;  // periodic hann(400) behind 312 zeros and in front of 312 (MelSpectrogram(win_length = 400) at n_fft = 1024)
-    int* bands = nullptr;   // [3][64]: first bin, bins, offset into wts
-    float* wts = nullptr;   // the non-zero triangle weights, band by band
+    MelBank bank;           // the HTK bank, 64 bands over 513 bins, band by band
     float* dft = nullptr;   // the GEMM form's (2 * 513, 1024) matrix, built on first use
 };
 std::mutex g_mu;
 std::map<int, MelspecPlan> g_plans;
-
-template <class T>
-hipError_t to_device(T** dst, const std::vector<T>& v) {
-    hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T) + 16);
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
 
 hipError_t build_plan(MelspecPlan& pl) {
     std::vector<float2> tw(HALF + 1);
@@ -147,63 +105,20 @@ hipError_t build_plan(MelspecPlan& pl) {
         const double a = 2.0 * M_PI * m / NFFT;
         tw[m] = make_float2((float)std::cos(a), (float)-std::sin(a));
     }
-    std::vector<float> win(NFFT);
-    for (int i = 0; i < NFFT; ++i) win[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / NFFT));
-    std::vector<int> bands;
-    std::vector<float> wts;
-    melspec_bank(bands, wts);
-    std::vector<float> win400(NFFT, 0.f);
-    for (int i = 0; i < 400; ++i) win400[(NFFT - 400) / 2 + i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / 400));
+    const std::vector<double> h1024 = hann_periodic(NFFT), h400 = hann_periodic(400);
+    std::vector<float> win(h1024.begin(), h1024.end()), win400(NFFT, 0.f);
+    for (int i = 0; i < 400; ++i) win400[(NFFT - 400) / 2 + i] = (float)h400[i];
     hipError_t e = to_device(&pl.tw, tw);
     if (e == hipSuccess) e = to_device(&pl.win, win);
     if (e == hipSuccess) e = to_device(&pl.win400, win400);
-    if (e == hipSuccess) e = to_device(&pl.bands, bands);
-    if (e == hipSuccess) e = to_device(&pl.wts, wts);
+    if (e == hipSuccess) e = upload_bank(pl.bank, htk_bank(NBIN, 60.0, 7800.0, NMEL), NBIN, NMEL);
     return e;
-}
-
-hipError_t build_dft(MelspecPlan& pl) {
-    std::vector<float> M((size_t)2 * NBIN * NFFT);
-    for (int r = 0; r < NBIN; ++r)
-        for (int i = 0; i < NFFT; ++i) {
-            const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * i / NFFT);
-            const double a = 2.0 * M_PI * (double)((long)r * i % NFFT) / NFFT;
-            M[(size_t)r * NFFT + i] = (float)(w * std::cos(a));
-            M[(size_t)(NBIN + r) * NFFT + i] = (float)(-w * std::sin(a));
-        }
-    return to_device(&pl.dft, M);
 }
 
 }  // namespace
 
-// torchaudio.functional.melscale_fbanks(513, 60, 7800, 64, 16000, norm = None, "htk") in float64, stored band by band: only the
-// non-zero weights (a bin feeds at most two bands)
-void melspec_bank(std::vector<int>& bands, std::vector<float>& wts) {
-    auto hz2mel = [](double f) { return 2595.0 * std::log10(1.0 + f / 700.0); };
-    auto mel2hz = [](double m) { return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0); };
-    const double m_lo = hz2mel(60.0), m_hi = hz2mel(7800.0);
-    std::vector<double> fpt(NMEL + 2);
-    for (int i = 0; i < NMEL + 2; ++i) fpt[i] = mel2hz(m_lo + (m_hi - m_lo) * i / (NMEL + 1));
-    bands.assign(3 * NMEL, 0);
-    wts.clear();
-    for (int m = 0; m < NMEL; ++m) {
-        int lo = -1, hi = -1;
-        std::vector<float> w(NBIN);
-        for (int k = 0; k < NBIN; ++k) {
-            const double f = 8000.0 * k / (NBIN - 1);
-            const double down = (f - fpt[m]) / (fpt[m + 1] - fpt[m]), up = (fpt[m + 2] - f) / (fpt[m + 2] - fpt[m + 1]);
-            w[k] = (float)std::fmax(0.0, std::fmin(down, up));
-            if (w[k] != 0.f) {
-                if (lo < 0) lo = k;
-                hi = k;
-            }
-        }
-        bands[m] = lo < 0 ? 0 : lo;
-        bands[NMEL + m] = lo < 0 ? 0 : hi - lo + 1;
-        bands[2 * NMEL + m] = (int)wts.size();
-        for (int k = bands[m]; k < bands[m] + bands[NMEL + m]; ++k) wts.push_back(w[k]);
-    }
-}
+// torchaudio.functional.melscale_fbanks(513, 60, 7800, 64, 16000, norm = None, "htk") in float64, stored band by band
+void melspec_bank(std::vector<int>& bands, std::vector<float>& wts) { sparsify(htk_bank(NBIN, 60.0, 7800.0, NMEL), NBIN, NMEL, bands, wts); }
 
 long melspec_num_frames(long L) { return 1 + L / HOP; }
 size_t melspec_sig_elems(long nseg, long L) { return (size_t)nseg * (size_t)((L + NFFT + 3) & ~3L); }
@@ -237,16 +152,17 @@ hipError_t launch_melspec(const MelspecParams& p, hipStream_t st) {
         std::lock_guard<std::mutex> lock(g_mu);
         pl = &g_plans[dev];
         if (!pl->tw && (e = build_plan(*pl)) != hipSuccess) return e;
-        if (!p.fft && !pl->dft && (e = build_dft(*pl)) != hipSuccess) return e;
+        if (!p.fft && !pl->dft && (e = to_device(&pl->dft, fold_dft(hann_periodic(NFFT).data(), NFFT, NFFT))) != hipSuccess) return e;
     }
     const unsigned frames = (unsigned)(p.nseg * T);
     if (p.fft) {
         hipLaunchKernelGGL(melspec_fft_kernel, dim3(frames), dim3(256), 0, st, p.ptrs, p.valid, p.L, (int)T, pl->tw,
-                           p.win400 ? pl->win400 : pl->win, pl->bands, pl->wts, p.mean, p.std_, p.out, p.o_bs, p.o_row, p.power, p.lead);
+                           p.win400 ? pl->win400 : pl->win, pl->bank.bands, pl->bank.wts, p.mean, p.std_, p.out, p.o_bs, p.o_row, p.power, p.lead);
         return hipGetLastError();
     }
     const long Lp = (p.L + NFFT + 3) & ~3L;
-    hipLaunchKernelGGL(melspec_pad_kernel, dim3((unsigned)((Lp + 255) / 256), p.nseg), dim3(256), 0, st, p.ptrs, p.valid, p.L, Lp, p.sig);
+    hipLaunchKernelGGL(reflect_pad_kernel<int>, dim3((unsigned)((Lp + 255) / 256), p.nseg), dim3(256), 0, st, p.ptrs, p.valid,
+                       (const float*)nullptr, (long)p.L, HALF, Lp, p.sig);
     GemmParams g{};
     g.A = p.sig;
     g.lda = HOP;  // overlapping rows: frame t starts at padded sample 160 t
@@ -261,8 +177,8 @@ hipError_t launch_melspec(const MelspecParams& p, hipStream_t st) {
     g.o_bs = T * 2 * NBIN;
     e = launch_gemm(F32, g, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(melspec_mel_kernel, dim3(frames), dim3(256), 0, st, p.spec, (int)T, pl->bands, pl->wts, p.mean, p.std_, p.out, p.o_bs,
-                       p.o_row, p.power);
+    hipLaunchKernelGGL((mel_rows_kernel<POWER_FMA, LogAffine>), dim3(frames), dim3(128), NBIN * sizeof(float), st, p.spec, NBIN, (int)T,
+                       pl->bank.bands, pl->bank.wts, NMEL, LogAffine{p.mean, p.std_}, p.out, p.o_bs, p.o_row, p.power);
     return hipGetLastError();
 }
 

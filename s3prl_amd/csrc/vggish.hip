@@ -7,7 +7,7 @@
 //   front end: fbank.hip's fold — the periodic Hann window and the zero-padded n_fft-point real DFT as ONE (2 nbin) x window matrix,
 //              built in float64 at create — so the spectrum of an utterance's E_b * example_frames frames is a GEMM whose A rows
 //              overlap in the caller's PCM (lda = shift); frames of an incomplete last example are not computed;
-//              vggish_mel_kernel: |X| -> the mel matrix (float64 on the host, rounded once) -> log(. + offset), written into the
+//              spectral.h's mel_rows_kernel: |X| -> the mel matrix (float64 on the host, rounded once) -> log(. + offset), written into the
 //              first layer's operand, the BORDERED single-channel image (E, frames + 2, bands + 2) indexed by example, frame, band;
 //   layer 0:   conv2d.hip's VALU kernel (C = 1), layers 1..: its MFMA kernel; bias -> ReLU -> max-pool in the epilogue, each into
 //              the interior of the next layer's bordered (H + 2, W + 2, C) operand.  The last layer writes a plain contiguous
@@ -22,31 +22,11 @@
 #include <cmath>
 
 #include "engine_internal.h"
+#include "spectral.h"
 
 namespace s3e {
 
 namespace {
-
-// one workgroup per frame of a complete example: row r of `spec` is frame (r % frames) of example (r / frames)
-__global__ __launch_bounds__(128) void vggish_mel_kernel(const float* spec, int nbin, int ldspec, const float* melT, int nmel,
-                                                         float offset, int frames, float* img) {
-    extern __shared__ float mag[];
-    const long r = blockIdx.x;
-    const float* s = spec + r * ldspec;
-    for (int k = threadIdx.x; k < nbin; k += blockDim.x) {
-        const float re = s[k], im = s[nbin + k];
-        mag[k] = sqrtf(re * re + im * im);
-    }
-    __syncthreads();
-    const long ex = r / frames;
-    const int f = (int)(r - ex * frames);
-    float* row = img + (ex * (frames + 2) + f + 1) * (long)(nmel + 2) + 1;
-    for (int b = threadIdx.x; b < nmel; b += blockDim.x) {
-        float acc = 0.f;
-        for (int k = 1; k < nbin; ++k) acc = fmaf(mag[k], melT[k * nmel + b], acc);  // the DC row of the mel matrix is zero
-        row[b] = logf(acc + offset);
-    }
-}
 
 // one workgroup per (utterance, example slot) row of the (B, E_max, D) state; off[b] = the first example of utterance b in `emb`
 __global__ __launch_bounds__(256) void vggish_post_kernel(const float* emb, const int* off, const int* cnt, int E_max, int D,
@@ -175,29 +155,12 @@ static int vggish_create(s3enc_encoder* e, const Ckpt& ck) {
     }
     // the front end's constants, float64 on the host and rounded once
     const int N = x.window, nb = x.n_fft / 2 + 1, nmel = x.num_mel_bins;
-    std::vector<float> M((size_t)2 * nb * N);
-    for (int r = 0; r < nb; ++r)
-        for (int i = 0; i < N; ++i) {
-            const double hann = 0.5 - 0.5 * std::cos(2.0 * M_PI * i / N);  // periodic: a whole cycle of a period-N cosine
-            const double a = 2.0 * M_PI * (double)((long)r * i % x.n_fft) / x.n_fft;
-            M[(size_t)r * N + i] = (float)(hann * std::cos(a));
-            M[(size_t)(nb + r) * N + i] = (float)(-hann * std::sin(a));
-        }
-    UP(upload_f32(w.dft, M));
-    std::vector<float> mT((size_t)nb * nmel, 0.f);
-    auto mel = [](double f) { return 1127.0 * std::log(1.0 + f / 700.0); };
-    const double lo = mel(x.mel_min_hz), hi = mel(x.mel_max_hz);
-    for (int b = 0; b < nmel; ++b) {
-        // np.linspace(lo, hi, nmel + 2)[b : b + 3]
-        const double step = (hi - lo) / (nmel + 1);
-        const double left = lo + b * step, center = lo + (b + 1) * step, right = b + 2 == nmel + 1 ? hi : lo + (b + 2) * step;
-        for (int k = 1; k < nb; ++k) {  // row 0 (DC) stays zero
-            const double m = mel(8000.0 * k / (nb - 1));
-            const double up = (m - left) / (center - left), down = (right - m) / (right - center);
-            mT[(size_t)k * nmel + b] = (float)std::fmax(0.0, std::fmin(up, down));
-        }
-    }
-    UP(upload_f32(w.melT, mT));
+    UP(upload_f32(w.dft, s3::fold_dft(s3::hann_periodic(N).data(), N, x.n_fft)));
+    std::vector<int> bands;
+    s3::sparsify(s3::vggish_bank(nb, nmel, x.mel_min_hz, x.mel_max_hz), nb, nmel, bands, t);
+    UP(upload_f32(w.wts, t));
+    UP(w.bands.ensure(bands.size() * sizeof(int)));
+    UP(hipMemcpy(w.bands.p, bands.data(), bands.size() * sizeof(int), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -318,8 +281,10 @@ static int vggish_forward(s3enc_handle e, const float* const* wav_ptrs_host, con
             g.ldo = N2;
             HIP_TRY(launch_gemm(F32, g, st));
         }
-        hipLaunchKernelGGL(vggish_mel_kernel, dim3((unsigned)rows), dim3(128), nb * sizeof(float), st, spec, nb, N2,
-                           (const float*)w.melT.p, NM, x.log_offset, FR, img);
+        // row r of `spec` is frame r % FR of example r / FR: into the interior of the bordered image
+        hipLaunchKernelGGL((s3::mel_rows_kernel<s3::MAGNITUDE, s3::LogAdd>), dim3((unsigned)rows), dim3(128), nb * sizeof(float), st, spec, nb, FR,
+                           (const int*)w.bands.p, (const float*)w.wts.p, NM, s3::LogAdd{x.log_offset}, img + (NM + 2) + 1,
+                           (long)(FR + 2) * (NM + 2), (long)(NM + 2), (float*)nullptr);
         HIP_TRY(hipGetLastError());
     }
 
