@@ -866,7 +866,12 @@ int s3enc_op_layernorm(int32_t dtype, const float* x, const float* gamma, const 
  * pre-scaled by head_dim^-0.5 — for dtype S3ENC_BF16 / S3ENC_F16 by head_dim^-0.5 * log2(e): the 16-bit kernels
  * work on base-2 scores, the engine folds either factor into W_q at s3enc_create; optional WavLM gated relative-position bias: score += gate[b][h][i] * table[h][clamp(j-i, -R, R) + R]
  * with a (H, 2R+1) table (the bucket of wavlm/modules.py:418-446 is constant for |j-i| >= max_distance, so
- * R = max_distance serves every T). */
+ * R = max_distance serves every T).  table_R = 0 is accepted: a (H, 1) table adds one constant per query, which the softmax
+ * ignores — the result is the bias-free one to rounding.  Every query row of the T is computed, the padded ones (t >= valid[b])
+ * like the rest.  valid[b] must be at least 1: with valid[b] = 0 the key loop runs zero tiles and the utterance's rows are
+ * 0 * (1 / 0) = NaN (nothing is read or written out of bounds).  The engine never passes 0: every forward refuses an utterance
+ * without a valid frame before it launches anything ("too short to produce a valid frame"), the chunked Mockingjay path clamps a
+ * chunk's key count to 1, and s3enc_valid_frames, which does answer 0 for such an utterance, is a query and launches nothing. */
 int s3enc_op_attention(int32_t dtype, const void* qkv, void* out, const int32_t* valid, int32_t B, int32_t T,
                        int32_t H, const float* bias_table, int32_t table_R, const float* gate, void* stream);
 

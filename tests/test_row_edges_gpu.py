@@ -11,6 +11,7 @@ import zlib
 import numpy as np
 import pytest
 
+from attention_ref import ATT_TOL, assert_rows, row_errors  # noqa: F401  (the per-row score, shared with the attention row sweep)
 from oracle import encoder_oracle as O
 from test_ops_gpu import TOL, _attention_ref, _dev, _ptr, _round, _torch
 
@@ -20,29 +21,6 @@ GUARD = 32  # NaN rows behind the last row of every output buffer
 
 
 # ---- shared helpers ---------------------------------------------------------------------------------------------------------------
-def row_errors(got, ref, floor=1e-3):
-    """Per-row error ||got[m] - ref[m]|| / max(||ref[m]||, floor) of two (rows, cols) arrays."""
-    got = np.asarray(got, dtype=np.float64)
-    ref = np.asarray(ref, dtype=np.float64)
-    return np.linalg.norm(got - ref, axis=1) / np.maximum(np.linalg.norm(ref, axis=1), floor)
-
-
-def assert_rows(got, ref, bound, what, floor=1e-3):
-    """max over rows of row_errors < bound; a failure names the worst row and its residue mod 32."""
-    got = np.asarray(got, dtype=np.float64)
-    rows = len(ref)
-    bad = ~np.isfinite(got).all(axis=1)
-    if bad.any():
-        m = int(np.argmax(bad))
-        raise AssertionError(f"{what}: row {m} of {rows} (row % 32 = {m % 32}, rows % 32 = {rows % 32}) is not finite "
-                             f"({int(bad.sum())} such rows)")
-    e = row_errors(got, ref, floor)
-    m = int(np.argmax(e))
-    assert e[m] < bound, (f"{what}: worst row {m} of {rows} (row % 32 = {m % 32}, rows % 32 = {rows % 32}): "
-                          f"per-row error {e[m]:.3e} >= {bound:.1e}")
-    return float(e[m])
-
-
 def guarded(rows, cols, dtype, ldo=None):
     """A NaN-prefilled (rows + GUARD, ldo) device buffer and its (rows, cols) view (row stride ldo)."""
     torch = _torch()
@@ -377,9 +355,6 @@ def test_gemm_swish_is_refused_by_the_16bit_kernels(dtype):
 
 
 # ---- (f) attention row edges ---------------------------------------------------------------------------------------------------
-ATT_TOL = {"fp32": 2e-5, "bf16": 1.5e-2, "fp16": 2e-3, "fp32x3": 5e-5}  # test_attention's bands
-
-
 def _valid(T, r):
     """Ragged valid lengths whose residues mod 32 are 1, 17 or 31 (and the full T)."""
     return np.array([T, (33, 49, 63)[r % 3], (1, 17, 31)[(r + 1) % 3]], dtype=np.int32)
@@ -417,20 +392,21 @@ def test_attention_rows_at_every_residue(dtype):
         torch.cuda.synchronize()
         assert_guards(buf, B * T, D, what)
         got = out.float().cpu().numpy()
-        assert_rows(got, ref, 2 * ATT_TOL[dtype], what)
+        assert_rows(got, ref, 2 * ATT_TOL[dtype], what, T=T)
         assert O.rel_err(got, ref) < ATT_TOL[dtype], what
 
 
-@pytest.mark.parametrize("T", [64, 65, 81, 95, 96, 127, 128])
+@pytest.mark.parametrize("T", [64, 65, 81, 95, 96, 127, 128, 129, 160, 255, 256, 257])
 def test_relpos_attention_rows_at_row_edges(T):
     """s3enc_op_relpos_attention (Conformer rel_pos, fp32) with H = 16 at T = 0 and other residues mod 32, ragged valid: every query row
-    against float64 (conformer_ref.relpos_scores), guard rows after B*T."""
+    against float64 (conformer_ref.relpos_scores), guard rows after B*T.  T > 128 (H = 3): a second and a third 128-query block, whose
+    S_rel ring starts at a block-dependent window row, one utterance's valid inside the second block."""
     torch = _torch()
     import conformer_ref as R
     from s3prl_amd import _lib
 
     lib = _lib.load()
-    B, H = 3, 16
+    B, H = 3, 16 if T <= 128 else 3
     D = 64 * H
     rng = np.random.default_rng(900 + T)
     qkv = rng.standard_normal((B, T, 3 * D)).astype(np.float32)
@@ -438,6 +414,8 @@ def test_relpos_attention_rows_at_row_edges(T):
     P = (0.5 * rng.standard_normal((2 * T - 1, D))).astype(np.float32)
     qadd = (0.1 * rng.standard_normal((H, 64))).astype(np.float32)
     valid = _valid(T, T % 32)
+    if T > 128:
+        valid[1] = min(130, T - 1)
     buf, out = guarded(B * T, D, torch.float32)
     dvalid = torch.from_numpy(valid).cuda()
     dqkv, dP, dqadd = _dev(qkv), _dev(P), _dev(qadd)
@@ -451,5 +429,5 @@ def test_relpos_attention_rows_at_row_edges(T):
     s = R.relpos_scores(q, k, P.astype(np.float64).reshape(2 * T - 1, H, 64), qadd.astype(np.float64))
     ref = (R.softmax_masked(s, valid) @ v).transpose(0, 2, 1, 3).reshape(B * T, D)
     got = out.cpu().numpy()
-    assert_rows(got, ref, 4e-5, what)
+    assert_rows(got, ref, 4e-5, what, T=T)
     assert O.rel_err(got, ref) < 2e-5, what
