@@ -20,7 +20,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13, "byol_s": 14}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13, "byol_s": 14, "lighthubert": 15}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -229,6 +229,7 @@ _PROTOS = {
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
+    "s3enc_op_posconv_narrow": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "s3enc_weighted_sum": (C.c_int, [_VP, _I64, _I32, C.POINTER(C.c_float), _I32, _I64, _I32, _VP, _VP]),
     "s3enc_weighted_sum_backward_scratch": (_I64, [_I64, _I32]),
     "s3enc_weighted_sum_backward": (C.c_int, [_VP, _I64, _I32, _I32, _I64, _I32, _VP, _VP, _VP, _VP]),
@@ -308,6 +309,12 @@ def make_config(cfg, dtype: str) -> S3Config:
     if dtype not in DTYPES:
         raise S3EncError(f"unknown dtype {dtype!r}; use one of fp32 / bf16 / fp16")
     c.compute_dtype = DTYPES[dtype]
+    if DTYPES[dtype] != F32:  # s3enc_create refuses both with these messages too
+        if cfg.family == "lighthubert":
+            raise S3EncError(f"LightHuBERT is built for compute dtype fp32 only; {dtype} is not built")
+        if cfg.layer_type != "conformer" and cfg.encoder_embed_dim // cfg.conv_pos_groups in (24, 40):
+            raise S3EncError(f"the positional conv at group width {cfg.encoder_embed_dim // cfg.conv_pos_groups} is built for compute "
+                             f"dtype fp32 only; {dtype} is not built")
     c.no_feature_layer_norm = int(not cfg.feature_layer_norm)
     c.pos_conv_depth = int(cfg.pos_conv_depth)
     c.wav_norm_eps = float(cfg.wav_norm_eps)

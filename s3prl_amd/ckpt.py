@@ -5,6 +5,7 @@
 * WavLM / UniSpeech-SAT ``{"cfg", "model"}``                      (wavlm/expert.py:37-40, unispeech_sat/expert.py:36-39)
 * DistilHuBERT ``{"Config": {"distiller": {...}}, "Distiller": state_dict}``      (distiller/builder.py:41-58,119-122)
 * multires-HuBERT: the HuBERT layout with ``MultiresHubertConfig`` in ``model_cfg``  (multires_hubert/convert.py:21-62)
+* LightHuBERT ``{"cfg": {"model": {...}}, "model": supernet state_dict}``         (lighthubert/expert.py:17-47): cut to its subnet here
 
 plus the fairseq layout ``{"cfg": {"task", "model"}, "model"}`` that ``hubert_custom(fairseq=True)`` /
 ``wav2vec2_custom(fairseq=True)`` convert first (hubert/convert.py:22-40, wav2vec2/convert.py:14-24).
@@ -19,8 +20,8 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, byol_a_config, byol_s_config, config_from_mae_ast, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
-from .synth import param_shapes
+from .config import EncoderConfig, LIGHTHUBERT_SUPERNET, config_from_lighthubert, byol_a_config, byol_s_config, config_from_mae_ast, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .synth import lighthubert_supernet_config, param_shapes
 
 _REQUIRED = {
     "hubert": ["task_cfg", "model_cfg", "model_weight", "dictionaries_symbols"],
@@ -387,6 +388,100 @@ def mockingjay_upstream_config(cfg: EncoderConfig) -> Dict:
     return dict(transformer=t, task=dict(sequence_length=cfg.mj_sequence_length), audio=audio)
 
 
+def _split_rows(full: int, block: int, take: int, total: int) -> np.ndarray:
+    """Indices an ``SLinear`` with splits keeps along its split axis (lighthubert/modules/scaling_linear.py:71-121): the axis of
+    ``full`` entries is ``full // block`` equal blocks; a subnet of ``total`` entries takes the leading ``take`` of every block
+    (the last block what is left of ``total``).  The whole axis when nothing is cut."""
+    if total == full:
+        return np.arange(full)
+    idx, i = [], 0
+    while len(idx) < total:
+        n = min(take, total - i * take)
+        idx.extend(range(i * block, i * block + n))
+        i += 1
+    assert i * block <= full
+    return np.asarray(idx)
+
+
+def lighthubert_slice(cfg: EncoderConfig, sd, what: str = "the LightHuBERT weights") -> Dict[str, np.ndarray]:
+    """The supernet state dict cut to the subnet ``cfg`` describes — the tensors the handle reads, under HuBERT's names.
+
+    ``SLayerNorm`` / ``SLinear`` / q, k, v, out_proj keep leading rows and columns; fc1 keeps the leading ``embed`` rows of each of its
+    four 768-row blocks and fc2 the same columns (their ``out_splits`` / ``in_splits``); the positional ``SConv1d`` keeps
+    ``weight[:embed, :embed // groups, :]`` with ``groups`` unchanged — new group g owns supernet filters [g dg, (g + 1) dg) and reads
+    the first dg input columns of each — AFTER ``weight_norm`` has been resolved on the unsliced tensor (``weight_v`` (768, 48, K),
+    ``weight_g`` (1, 1, K): the per-tap norm runs over all 768 x 48 entries), so the fold happens here, in float64, and the result
+    travels as ``encoder.pos_conv.0.weight``.  ``mask_emb``, ``layer_pred_heads.*`` and label tensors are never read."""
+    S = LIGHTHUBERT_SUPERNET
+    E, F, C = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.conv_dim
+    SE, SF = S["embed_dim"], S["ffn_embed"]
+
+    def get(name, shape):
+        if name not in sd:
+            raise ValueError(f"{what}: missing parameter {name}")
+        w = sd[name]
+        w = w.detach().cpu().float().numpy() if hasattr(w, "detach") else np.asarray(w, dtype=np.float32)
+        if tuple(w.shape) != tuple(shape):
+            raise ValueError(f"{what}: parameter {name} has shape {tuple(w.shape)}, expected {tuple(shape)}")
+        return w
+
+    out: Dict[str, np.ndarray] = {}
+    for name, shape in param_shapes(lighthubert_supernet_config(cfg)).items():  # the extractor is not cut
+        if name.startswith(("feature_extractor.", "layer_norm.")):
+            out[name] = get(name, shape)
+    out["post_extract_proj.weight"] = get("post_extract_proj.weight", (SE, C))[:E]
+    out["post_extract_proj.bias"] = get("post_extract_proj.bias", (SE,))[:E]
+    K, G = cfg.conv_pos, cfg.conv_pos_groups
+    v = get("encoder.pos_conv.0.weight_v", (SE, SE // G, K)).astype(np.float64)
+    g = get("encoder.pos_conv.0.weight_g", (1, 1, K)).astype(np.float64)
+    w = v * (g / np.sqrt((v * v).sum(axis=(0, 1), keepdims=True)))
+    out["encoder.pos_conv.0.weight"] = w[:E, :E // G, :].astype(np.float32)
+    out["encoder.pos_conv.0.bias"] = get("encoder.pos_conv.0.bias", (SE,))[:E]
+    for leaf in ("weight", "bias"):
+        out[f"encoder.layer_norm.{leaf}"] = get(f"encoder.layer_norm.{leaf}", (SE,))[:E]
+    ffn = _split_rows(SF, SE, E, F)
+    for l in range(cfg.encoder_layers):
+        p = f"encoder.layers.{l}"
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            out[f"{p}.self_attn.{n}.weight"] = get(f"{p}.self_attn.{n}.weight", (SE, SE))[:E, :E]
+            out[f"{p}.self_attn.{n}.bias"] = get(f"{p}.self_attn.{n}.bias", (SE,))[:E]
+        for n in ("self_attn_layer_norm", "final_layer_norm"):
+            for leaf in ("weight", "bias"):
+                out[f"{p}.{n}.{leaf}"] = get(f"{p}.{n}.{leaf}", (SE,))[:E]
+        out[f"{p}.fc1.weight"] = get(f"{p}.fc1.weight", (SF, SE))[ffn][:, :E]
+        out[f"{p}.fc1.bias"] = get(f"{p}.fc1.bias", (SF,))[ffn]
+        out[f"{p}.fc2.weight"] = get(f"{p}.fc2.weight", (SE, SF))[:E][:, ffn]
+        out[f"{p}.fc2.bias"] = get(f"{p}.fc2.bias", (SE,))[:E]
+    return {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in out.items()}
+
+
+def lighthubert_model_cfg(cfg: EncoderConfig) -> Dict:
+    """``checkpoint["cfg"]["model"]`` for a LightHuBERT configuration, as the released files spell it."""
+    d = dict(_name=cfg.lh_model, extractor_mode=cfg.extractor_mode, conv_bias=cfg.conv_bias, encoder_layers=12, encoder_embed_dim=768,
+             encoder_ffn_embed_dim=3072, encoder_attention_heads=12, layer_norm_first=cfg.layer_norm_first, conv_pos=cfg.conv_pos,
+             conv_pos_groups=cfg.conv_pos_groups, activation_fn="gelu", layer_type="transformer", pos_conv_depth=cfg.pos_conv_depth,
+             conv_feature_layers=str([tuple(t) for t in cfg.conv_layers]))
+    if cfg.lh_model == "hubert_pruner":
+        d["pruner_supernet"] = f"lighthubert_{cfg.lh_supernet}.yaml"
+    else:
+        d["supernet_type"] = cfg.lh_supernet
+    return d
+
+
+def load_lighthubert_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"cfg": {"model": {...}}, "model": state_dict}`` (upstream/lighthubert/expert.py:17-47): the subnet is resolved as the
+    expert does and only the sliced tensors are returned (what reaches the device)."""
+    import torch
+
+    state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    for key in ("cfg", "model"):
+        if key not in state:
+            raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: {key} is missing")
+    model_cfg = _plain(_plain(state["cfg"])["model"])
+    cfg = config_from_lighthubert(model_cfg)
+    return cfg, lighthubert_slice(cfg, state["model"], ckpt)
+
+
 def _hot_path_weights(ckpt: str, cfg: EncoderConfig, sd) -> Dict[str, np.ndarray]:
     weights = {}
     for name, shape in param_shapes(cfg).items():
@@ -421,6 +516,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_byol_s_checkpoint(ckpt)
     if family == "mae_ast":
         return load_mae_ast_checkpoint(ckpt)
+    if family == "lighthubert":
+        return load_lighthubert_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -479,6 +576,9 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
         if "batch_norm.num_batches_tracked" in sd:
             sd["batch_norm.num_batches_tracked"] = sd["batch_norm.num_batches_tracked"].to(torch.int64).reshape(())
         torch.save({"cfg": mae_ast_cfg_blocks(cfg), "model": sd}, path)
+        return
+    if cfg.family == "lighthubert":  # upstream/lighthubert/expert.py:17-21: the SUPERNET state dict beside cfg.model
+        torch.save({"cfg": {"model": lighthubert_model_cfg(cfg)}, "model": sd}, path)
         return
     if cfg.family in ("byol_a", "byol_s"):  # upstream/byol_a/byol_a.py:58-80, byol_s/serab_byols/serab.py:100-102: a plain state dict
         torch.save(sd, path)

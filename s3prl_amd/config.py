@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast", "byol_s")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast", "byol_s", "lighthubert")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -83,6 +83,11 @@ class EncoderConfig:
     # data2vec-audio (upstream/data2vec, wav2vec2_model.py:2995-3023): pos_conv_depth > 1 replaces the weight-normed
     # positional conv by that many {Conv1d(k = max(3, conv_pos // depth), groups) -> LayerNorm(no affine) -> GELU} blocks
     pos_conv_depth: int = 1
+    # LightHuBERT (family "lighthubert", upstream/lighthubert): the encoder_* fields describe the SUBNET that runs; the checkpoint
+    # holds the 768-wide supernet it is cut from.  ``lh_model`` is the checkpoint's ``cfg.model._name`` ("hubert_pruner": the
+    # released subnet of ``lh_supernet``; "student_hubert": the supernet's largest subnet), ``lh_supernet`` "base" | "small"
+    lh_model: str = ""
+    lh_supernet: str = ""
     # eps of the per-utterance waveform normalisation: F.layer_norm's 1e-5 in the fairseq experts (hubert/expert.py:57-58),
     # 1e-7 in Hugging Face's Wav2Vec2FeatureExtractor (hf_hubert / hf_wav2vec2 upstreams)
     wav_norm_eps: float = 1e-5
@@ -439,6 +444,16 @@ class EncoderConfig:
             return self._validate_byol_s()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
+        if self.family == "lighthubert":
+            if self.lh_model not in ("hubert_pruner", "student_hubert") or self.lh_supernet not in ("base", "small"):
+                raise ValueError("lighthubert: lh_model must be 'hubert_pruner' or 'student_hubert' and lh_supernet 'base' or "
+                                 f"'small', got {self.lh_model!r} / {self.lh_supernet!r} (config_from_lighthubert sets them)")
+            if self.layer_norm_first:
+                raise ValueError("lighthubert with layer_norm_first=True is not built (the released checkpoints are post-LN)")
+            if self.pos_conv_depth > 1:
+                raise ValueError("lighthubert with pos_conv_depth > 1 is not built (the released checkpoints have one positional conv)")
+            if self.layer_type != "transformer":
+                raise ValueError("lighthubert: only layer_type='transformer' exists in the reference")
         if self.layer_type == "conformer":
             if self.family != "wav2vec2" or self.pos_conv_depth > 1:
                 raise ValueError("conformer layers are a wav2vec2-family encoder")
@@ -462,11 +477,12 @@ class EncoderConfig:
             raise ValueError("the HIP attention kernel is specialised for head_dim == 64")
         if self.encoder_embed_dim % self.conv_pos_groups:
             raise ValueError("embed_dim must be divisible by conv_pos_groups")
-        if self.encoder_embed_dim // self.conv_pos_groups not in (32, 48, 64):
+        if self.encoder_embed_dim // self.conv_pos_groups not in (24, 32, 40, 48, 64):
             # the positional-conv kernels are built for these group widths (s3enc_create repeats it); a Conformer never runs
-            # its positional conv, but its checkpoint carries one and the handle packs it
-            raise ValueError("embed_dim / conv_pos_groups (the positional conv's group width) must be 32, 48 or 64, got "
-                             f"{self.encoder_embed_dim} / {self.conv_pos_groups}")
+            # its positional conv, but its checkpoint carries one and the handle packs it.  24 and 40 (the LightHuBERT subnets)
+            # exist in exact fp32 only: make_config / s3enc_create refuse the other operand modes there
+            raise ValueError("embed_dim / conv_pos_groups (the positional conv's group width) must be 32, 48 or 64 (fp32: also 24 or "
+                             f"40), got {self.encoder_embed_dim} / {self.conv_pos_groups}")
         if not 1 <= self.conv_pos <= 256:
             raise ValueError(f"conv_pos (the positional conv's kernel) must be 1..256, got {self.conv_pos}")
 
@@ -802,6 +818,70 @@ _MODEL_KEYS = (
     "encoder_attention_heads", "layer_norm_first", "conv_pos", "conv_pos_groups",
 )
 _WAVLM_KEYS = ("relative_position_embedding", "num_buckets", "max_distance", "gru_rel_pos", "normalize")
+
+
+LIGHTHUBERT_SUPERNET = dict(embed_dim=768, ffn_embed=3072, heads_num=12, layer_num=12)  # the checkpoint's own width, hard-coded by the reference
+
+
+def lighthubert_subnet(model_name: str, supernet_type: str) -> Dict:
+    """The subnet the reference's expert runs (lighthubert/expert.py:38-42, lighthubert.py:199-272): for ``hubert_pruner`` the
+    released subnet of the supernet type, for ``student_hubert`` the largest subnet of its search space."""
+    if supernet_type not in ("base", "small"):
+        raise ValueError(f"lighthubert: unknown supernet type {supernet_type!r}")
+    if model_name == "hubert_pruner":
+        embed = 640 if supernet_type == "base" else 384
+    elif model_name == "student_hubert":
+        embed = 768 if supernet_type == "base" else 512
+    else:
+        raise ValueError(f"lighthubert: cfg.model._name must be 'hubert_pruner' or 'student_hubert', got {model_name!r}")
+    heads = embed // 64
+    return dict(atten_dim=[embed] * 12, embed_dim=embed, ffn_embed=[4 * embed] * 12, heads_num=[heads] * 12, layer_num=12,
+                slide_wsz=["global"] * 12)
+
+
+def check_lighthubert_subnet(subnet: Dict) -> None:
+    """What the HIP path builds of a subnet description; the rest is refused by name."""
+    n = int(subnet["layer_num"])
+    if n != 12:
+        raise ValueError(f"lighthubert: a subnet of {n} layers is not built (the 10- and 11-layer depth maps drop supernet layers)")
+    for key in ("atten_dim", "ffn_embed", "heads_num"):
+        if len(set(subnet[key])) != 1 or len(subnet[key]) != n:
+            raise ValueError(f"lighthubert: a subnet with non-uniform {key} is not built, got {list(subnet[key])}")
+    if subnet["atten_dim"][0] != subnet["embed_dim"]:
+        raise ValueError(f"lighthubert: a subnet with atten_dim != embed_dim is not built, got {subnet['atten_dim'][0]} / "
+                         f"{subnet['embed_dim']}")
+    if any(w != "global" for w in subnet.get("slide_wsz", ["global"])):
+        raise ValueError("lighthubert: sliding-window attention (slide_wsz) is not built")
+
+
+def config_from_lighthubert(model_cfg: Dict, subnet: Dict | None = None) -> EncoderConfig:
+    """``checkpoint["cfg"]["model"]`` of a LightHuBERT file -> the configuration of the subnet its expert runs
+    (lighthubert/expert.py:17-47; LightHuBERTConfig.update keeps only the keys it knows, lighthubert.py:341-428)."""
+    name = model_cfg.get("_name")
+    stype = str(model_cfg.get("supernet_type", "base")).lower()
+    if name == "hubert_pruner":  # expert.py:24-36: the yaml's name decides, else the configured / default type stays
+        yaml = str(model_cfg.get("pruner_supernet", "")).lower()
+        stype = "small" if yaml.endswith("small.yaml") else "base" if yaml.endswith("base.yaml") else stype
+    subnet = subnet or lighthubert_subnet(name, stype)
+    check_lighthubert_subnet(subnet)
+    for key, want in (("encoder_layers", 12), ("encoder_embed_dim", 768), ("encoder_ffn_embed_dim", 3072), ("encoder_attention_heads", 12)):
+        if int(model_cfg.get(key, want)) != want:
+            raise ValueError(f"lighthubert: the supernet is {want} for {key} (hard-coded by the reference), got {model_cfg[key]}")
+    if str(model_cfg.get("layer_type", "transformer")) != "transformer":
+        raise ValueError("lighthubert: only layer_type='transformer' exists in the reference")
+    act = str(getattr(model_cfg.get("activation_fn", "gelu"), "name", model_cfg.get("activation_fn", "gelu")))
+    if act != "gelu":
+        raise ValueError(f"only activation_fn='gelu' is on the hot path, got {act!r}")
+    cfg = EncoderConfig(
+        family="lighthubert", lh_model=str(name), lh_supernet=stype, normalize=True,  # expert.py:56: F.layer_norm on every waveform
+        extractor_mode=str(model_cfg.get("extractor_mode", "layer_norm")), conv_bias=bool(model_cfg.get("conv_bias", False)),
+        conv_layers=parse_conv_layers(model_cfg.get("conv_feature_layers", DEFAULT_CONV_LAYERS)),
+        encoder_layers=12, encoder_embed_dim=int(subnet["embed_dim"]), encoder_ffn_embed_dim=int(subnet["ffn_embed"][0]),
+        encoder_attention_heads=int(subnet["heads_num"][0]), layer_norm_first=bool(model_cfg.get("layer_norm_first", False)),
+        conv_pos=int(model_cfg.get("conv_pos", 128)), conv_pos_groups=int(model_cfg.get("conv_pos_groups", 16)),
+        pos_conv_depth=int(model_cfg.get("pos_conv_depth", 1) or 1))
+    cfg.validate()
+    return cfg
 
 
 def config_from_dicts(family: str, model_cfg: Dict, task_cfg: Dict | None = None) -> EncoderConfig:

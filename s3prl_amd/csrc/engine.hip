@@ -172,7 +172,7 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > 14) return fail("config: unknown family");
+    if (c.family < 0 || c.family > S3ENC_LIGHTHUBERT) return fail("config: unknown family");
     if (family_ops(c.family)) return 0;  // its record's own check runs on both configuration blocks (create_impl)
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
@@ -201,9 +201,21 @@ int check_config(const s3enc_config& c) {
     if (c.ffn_dim % 8) return fail("config: ffn_dim must be a multiple of 8");
     if (c.conv_pos_groups <= 0 || c.embed_dim % c.conv_pos_groups) return fail("config: embed_dim % conv_pos_groups != 0");
     const int dg = c.embed_dim / c.conv_pos_groups;
-    if (dg != 32 && dg != 48 && dg != 64) return fail("config: embed_dim/conv_pos_groups must be 32, 48 or 64");
+    if (dg != 24 && dg != 32 && dg != 40 && dg != 48 && dg != 64) return fail("config: embed_dim/conv_pos_groups must be 32, 48 or 64 (fp32: also 24 or 40)");
     if (c.conv_pos < 1 || c.conv_pos > 256) return fail("config: conv_pos out of range");
     if (c.compute_dtype < 0 || c.compute_dtype > 4) return fail("config: unknown compute_dtype");
+    static const char* const kModes[] = {"fp32", "bf16", "fp16", "fp32x3", "fp16x2"};
+    if ((dg == 24 || dg == 40) && c.compute_dtype != S3ENC_F32)
+        return fail(std::string("config: the positional conv at group width ") + std::to_string(dg) + " is built for compute dtype fp32 only; " +
+                    kModes[c.compute_dtype] + " is not built");
+    if (c.family == S3ENC_LIGHTHUBERT) {
+        if (c.compute_dtype != S3ENC_F32)
+            return fail(std::string("config: LightHuBERT is built for compute dtype fp32 only; ") + kModes[c.compute_dtype] + " is not built");
+        if (c.layer_norm_first) return fail("config: LightHuBERT with layer_norm_first is not built");
+        if (c.pos_conv_depth > 1) return fail("config: LightHuBERT with pos_conv_depth > 1 is not built");
+        if (c.layer_type || c.rel_pos || c.pred_heads || c.no_feature_layer_norm)
+            return fail("config: LightHuBERT takes none of the Conformer / WavLM / DistilHuBERT options");
+    }
     if (c.encoder_layers < 1) return fail("config: encoder_layers < 1");
     if (c.rel_pos && c.family != S3ENC_WAVLM) return fail("config: rel_pos is a WavLM feature");
     if (c.rel_pos && (c.num_buckets < 4 || c.max_distance <= c.num_buckets / 4))
@@ -474,14 +486,20 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
     } else {
         const int K = c.conv_pos, G = c.conv_pos_groups, Dg = D / G;
         std::vector<float> g, v;
-        GET(enc0 + ".pos_conv.0.weight_g", K, g);
-        GET(enc0 + ".pos_conv.0.weight_v", (long)D * Dg * K, v);
-        std::vector<double> nrm(K, 0.0);
-        for (long i = 0; i < (long)D * Dg; ++i)
-            for (int k = 0; k < K; ++k) nrm[k] += (double)v[i * K + k] * v[i * K + k];
-        for (int k = 0; k < K; ++k) nrm[k] = (double)g[k] / std::sqrt(nrm[k]);
-        for (long i = 0; i < (long)D * Dg; ++i)
-            for (int k = 0; k < K; ++k) v[i * K + k] = (float)(v[i * K + k] * nrm[k]);
+        if (c.family == S3ENC_LIGHTHUBERT) {
+            // the weight-norm runs over the UNSLICED supernet tensor (768 x 48 entries per tap), so only the binder can fold it:
+            // the sliced, folded filters arrive as a plain conv weight (s3enc.h: S3ENC_LIGHTHUBERT)
+            GET(enc0 + ".pos_conv.0.weight", (long)D * Dg * K, v);
+        } else {
+            GET(enc0 + ".pos_conv.0.weight_g", K, g);
+            GET(enc0 + ".pos_conv.0.weight_v", (long)D * Dg * K, v);
+            std::vector<double> nrm(K, 0.0);
+            for (long i = 0; i < (long)D * Dg; ++i)
+                for (int k = 0; k < K; ++k) nrm[k] += (double)v[i * K + k] * v[i * K + k];
+            for (int k = 0; k < K; ++k) nrm[k] = (double)g[k] / std::sqrt(nrm[k]);
+            for (long i = 0; i < (long)D * Dg; ++i)
+                for (int k = 0; k < K; ++k) v[i * K + k] = (float)(v[i * K + k] * nrm[k]);
+        }
         // the 16-bit / split-precision implicit GEMM wants an even tap count with K * Dg a multiple of 128: append zero
         // taps (the real kernel keeps its K / 2 left padding), as for the data2vec stack above
         int kp = K;
@@ -1071,6 +1089,9 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     if (fo.selection < 0 || fo.selection > 2) return fail("s3enc_forward: unknown selection");
     if ((dist || mr) && fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: DistilHuBERT / multires-HuBERT have one selection (their hidden_states list)");
+    const bool lhb = c.family == S3ENC_LIGHTHUBERT;  // hidden_states[0] = post_extract_proj's output, then the layer outputs
+    if (lhb && fo.selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_forward: feature_selection is not defined for LightHuBERT (its expert returns one hidden_states list)");
     const bool conf = c.layer_type == 1;
     if (conf && fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: feature_selection is not defined for a Conformer encoder (the reference's ConformerEncoder records "
@@ -1192,7 +1213,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     // state index of each tensor of the forward under this selection (-1: not a state)
     const bool hid = fo.selection == S3ENC_SEL_HIDDEN && !dist;
     const bool lay = fo.selection == S3ENC_SEL_LAYER_OUT;
-    auto si_hidden = [&](int l) { return hid ? l : -1; };                             // input of layer l / encoder output
+    auto si_hidden = [&](int l) { return hid && !(lhb && l == 0) ? l : -1; };         // input of layer l / encoder output
     auto si_layer_out = [&](int l) { return lay ? l : (dist ? 1 + l : -1); };         // output of layer l
     auto si_stream = [&](int l) {  // the tensor "residual stream after layer l" as the next layer's input
         const int a = (l + 1 < NL || !prel) ? si_hidden(l + 1) : -1;  // pre-LN: the encoder output is the normed stream
@@ -1349,8 +1370,8 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         if (dbg_stop == 20) return 0;
     }
     // DistilHuBERT: hidden_states[0] = feat_final, padded frames zeroed in place; a pre-LN Conformer's hidden_states[0] is the same
-    // tensor (ConformerEncoder has no positional conv and zeroes the padded frames, wav2vec2_model.py:3170-3175)
-    const int si_proj = (dist || (conf && c.layer_norm_first)) ? 0 : -1;
+    // tensor (ConformerEncoder has no positional conv and zeroes the padded frames, wav2vec2_model.py:3170-3175); LightHuBERT's too
+    const int si_proj = (dist || lhb || (conf && c.layer_norm_first)) ? 0 : -1;
     float* xproj = sink.slot32(si_proj) ? sink.slot32(si_proj) : (float*)x32;
     {
         GemmParams g{};
@@ -1798,6 +1819,8 @@ int s3enc_forward_status(s3enc_handle h, int32_t wait, int32_t* status) {
 int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
     if (!h || !n) return fail("s3enc_num_states: null argument");
     if (selection < 0 || selection > 2) return fail("s3enc_num_states: unknown selection");
+    if (h->cfg.family == S3ENC_LIGHTHUBERT && selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_num_states: feature_selection is not defined for LightHuBERT (its expert returns one hidden_states list)");
     if ((h->cfg.family == S3ENC_DISTILLER || h->cfg.family == S3ENC_MULTIRES) && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: DistilHuBERT / multires-HuBERT have one selection (their hidden_states list)");
     if (h->cfg.layer_type == 1 && selection != S3ENC_SEL_HIDDEN)

@@ -216,17 +216,21 @@ inline hipError_t upload_cvt(DevBuf& d, const std::vector<float>& v, int dtype) 
 //   fp32   [G][K][Dg/16][Dg(co)][16]         (posconv_kernel: tap-major 16-deep input-channel chunks; inside a row of 16 the
 //                                             four 16-byte slots are stored at slot ^ pc_w_swizzle(co): the kernel's
 //                                             ds_read_b128 of a (16 co) x (16 ci) fragment block is then bank-conflict free)
+//          Dg = 24, 40: per tap the Dg/16 full chunks as above, then the last 8 input channels as [Dg(co)][8] with the
+//                                             four 8-byte slots of a row swizzled the same way — Dg * Dg floats per tap, no padding
 //   16-bit [G][Dg(co)][k = tap*Dg + ci]       (posconv16_kernel: the W operand of the implicit GEMM)
 inline void pack_posconv(const std::vector<float>& w, int D, int G, int K, int dtype, std::vector<float>& out) {
-    const int Dg = D / G;
+    const int Dg = D / G, full = Dg & ~15;  // input channels in 16-deep chunks; Dg = 24, 40: the last 8 follow as [Dg(co)][8]
     out.assign((size_t)G * K * Dg * Dg, 0.f);
     for (int gi = 0; gi < G; ++gi)
         for (int n = 0; n < Dg; ++n)
             for (int ci = 0; ci < Dg; ++ci)
                 for (int k = 0; k < K; ++k) {
                     const float x = w[((long)(gi * Dg + n) * Dg + ci) * K + k];
-                    if (dtype == F32)
-                        out[((((long)gi * K + k) * (Dg / 16) + ci / 16) * Dg + n) * 16 + ((((ci % 16) >> 2) ^ pc_w_swizzle(n)) << 2) + (ci & 3)] = x;
+                    if (dtype == F32 && ci < full)
+                        out[((long)gi * K + k) * Dg * Dg + ((long)(ci / 16) * Dg + n) * 16 + ((((ci % 16) >> 2) ^ pc_w_swizzle(n)) << 2) + (ci & 3)] = x;
+                    else if (dtype == F32)
+                        out[((long)gi * K + k) * Dg * Dg + (long)full * Dg + n * 8 + ((((ci - full) >> 1) ^ pc_w_swizzle(n)) << 1) + (ci & 1)] = x;
                     else
                         out[(((long)gi * Dg + n) * K + k) * Dg + ci] = x;
                 }

@@ -427,7 +427,7 @@ hipError_t launch_rope(const float* x, const float* table, long rows, int T, int
 // ---- posconv.hip --------------------------------------------------------------------------------------------
 struct PosConvParams {
     const float* x;     // (B, T, D) fp32, padded frames already zero
-    const void* w;      // fp32 mode: packed [G][K][Dg/16][Dg(n)][16]; 16-bit modes: see launch_posconv16
+    const void* w;      // fp32 mode: packed [G][K][Dg/16][Dg(n)][16] (+ [Dg(n)][8] at Dg = 24, 40: pack_posconv); 16-bit modes: see launch_posconv16
     const float* bias;  // [D]
     float* out;         // (B, T, D) fp32 = x + gelu(conv(x) + bias)
     int B, T, D, G, K;

@@ -873,11 +873,21 @@ int s3enc_op_wavlm_gate(const float* x, const float* grep_w, const float* grep_b
     return 0;
 }
 
-int s3enc_op_posconv(int32_t dtype, const float* x, const float* w_host, const float* bias, int32_t B, int32_t T, int32_t D,
-                     int32_t G, int32_t K, float* out, void* stream) {
-    if (!x || !w_host || !bias || !out) return fail("s3enc_op_posconv: null argument");
-    if (G <= 0 || D % G) return fail("s3enc_op_posconv: D must be a multiple of groups");
+}  // extern "C"
+
+// the body of both positional-conv entries; `narrow`: the entry of the group widths 24 and 40 (s3enc_op_posconv_narrow)
+static int op_posconv(const char* entry, bool narrow, int32_t dtype, const float* x, const float* w_host, const float* bias, int32_t B,
+                      int32_t T, int32_t D, int32_t G, int32_t K, float* out, void* stream) {
+    const std::string who = std::string(entry) + ": ";
+    if (!x || !w_host || !bias || !out) return fail(who + "null argument");
+    if (G <= 0 || D % G) return fail(who + "D must be a multiple of groups");
     const int Dg = D / G;
+    if (narrow) {
+        if (Dg != 24 && Dg != 40) return fail(who + "D / groups must be 24 or 40 (s3enc_op_posconv runs 32, 48 and 64)");
+        if (dtype != F32) return fail(who + "group width " + std::to_string(Dg) + " is built for fp32 only (the 16-bit and fp32x3 kernel is not built at 24 and 40)");
+    } else if (Dg != 32 && Dg != 48 && Dg != 64) {
+        return fail(who + "D / groups must be 32, 48 or 64 (24 and 40, fp32 only: s3enc_op_posconv_narrow)");
+    }
     std::vector<float> w(w_host, w_host + (size_t)D * Dg * K), packed;
     DevBuf dw;
     if (dtype == 3) {
@@ -899,6 +909,18 @@ int s3enc_op_posconv(int32_t dtype, const float* x, const float* w_host, const f
     HIP_TRY(dtype == F32 ? launch_posconv(p, (hipStream_t)stream) : launch_posconv16(dtype, p, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the packed weights are freed on return
     return 0;
+}
+
+extern "C" {
+
+int s3enc_op_posconv(int32_t dtype, const float* x, const float* w_host, const float* bias, int32_t B, int32_t T, int32_t D,
+                     int32_t G, int32_t K, float* out, void* stream) {
+    return op_posconv("s3enc_op_posconv", false, dtype, x, w_host, bias, B, T, D, G, K, out, stream);
+}
+
+int s3enc_op_posconv_narrow(int32_t dtype, const float* x, const float* w_host, const float* bias, int32_t B, int32_t T, int32_t D,
+                            int32_t G, int32_t K, float* out, void* stream) {
+    return op_posconv("s3enc_op_posconv_narrow", true, dtype, x, w_host, bias, B, T, D, G, K, out, stream);
 }
 
 int s3enc_weighted_sum(const float* hs, int64_t layer_stride, int32_t L, const float* w, int32_t normalize, int64_t rows, int32_t D,

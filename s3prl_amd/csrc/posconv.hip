@@ -50,11 +50,18 @@ __device__ __forceinline__ PcWork pc_work(const PosConvParams& p, int ntiles) {
     return w;
 }
 
+// DG = 24 and 40 (the LightHuBERT subnets: 384 / 640 channels in 16 groups) are no multiple of the 16-wide tiles.  Along the
+// contraction nothing is padded: the MFMA takes four input channels at a time, so behind the DG/16 full chunks comes one HALF
+// chunk of 8 channels — two MFMAs fed by 8-byte reads (lane group kk holds channels 2kk, 2kk+1 of the chunk).  Along the output
+// channels the last 16-wide tile has 8 real columns: its lanes 8..15 re-read the rows of lanes 0..7 (same address: an LDS
+// broadcast, no zero rows in the weight stream or in LDS) and their results are never stored.  x is read in place from the
+// (B, T, D) rows (g*DG*4 bytes is a multiple of 16 for both widths) and only the DG real channels of a group are written.
 template <int DG>
 __global__ __launch_bounds__(256) void posconv_kernel(PosConvParams p) {
-    constexpr int NT = DG / 16;       // 16-wide output-channel tiles
-    constexpr int NCC = DG / 16;      // 16-deep input-channel chunks
-    constexpr int RS = DG + 8;        // LDS row stride of the x window (floats): +8 makes the float4 A reads conflict-free (+4: 2-way)
+    constexpr bool HALF = DG % 16 == 8;   // a trailing 8-wide half tile / half chunk (DG = 24, 40)
+    constexpr int NT = (DG + 15) / 16;    // 16-wide output-channel tiles (HALF: the last one has 8 real columns)
+    constexpr int NCC = DG / 16;          // 16-deep input-channel chunks (HALF: + one 8-deep chunk)
+    constexpr int RS = DG + (HALF ? 16 : 8);  // LDS row stride of the x window (floats): = 8 (mod 16) makes the float4 A reads conflict-free (+4: 2-way)
     constexpr int WSZ = DG * DG;      // floats per tap
     constexpr int NWV = (WSZ / 4 + 255) / 256;  // float4 per thread per tap
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -106,9 +113,12 @@ __global__ __launch_bounds__(256) void posconv_kernel(PosConvParams p) {
         for (int n = 0; n < NT; ++n) acc[f][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     const float* xrow = xs + (wave * (16 * PC_FT) + l15) * RS + 4 * kk;  // frame tile f: + 16 f rows
+    // weight row of this lane inside a 16-wide tile; HALF: the tile's lanes 8..15 of the LAST tile mirror rows 0..7
+    const int l7 = l15 & 7;
     for (int j = 0; j < K; ++j) {
         if (j + 1 < K) wload(j + 1);
-        const float* wb = wl + (j & 1) * WSZ + l15 * 16 + 4 * (kk ^ pc_w_swizzle(l15));  // (the pack stored slot kk there)
+        const float* wt = wl + (j & 1) * WSZ;
+        const float* wb = wt + l15 * 16 + 4 * (kk ^ pc_w_swizzle(l15));  // (the pack stored slot kk there)
         const float* xa = xrow + j * RS;
 #pragma unroll
         for (int cc = 0; cc < NCC; ++cc) {
@@ -117,7 +127,8 @@ __global__ __launch_bounds__(256) void posconv_kernel(PosConvParams p) {
             for (int f = 0; f < PC_FT; ++f) a[f] = *(const float4*)(xa + f * 16 * RS + 16 * cc);
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-                const float4 w = *(const float4*)(wb + (cc * DG + n * 16) * 16);
+                const float4 w = (HALF && n == NT - 1) ? *(const float4*)(wt + ((cc * DG + n * 16) + l7) * 16 + 4 * kk)
+                                                       : *(const float4*)(wb + (cc * DG + n * 16) * 16);
                 // per accumulator the k order is x, y, z, w of chunk cc, chunks and taps ascending — as before: a frame's
                 // result does not depend on the frame tile it sits in
 #pragma unroll
@@ -126,6 +137,22 @@ __global__ __launch_bounds__(256) void posconv_kernel(PosConvParams p) {
                     acc[f][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[f].y, w.y, acc[f][n], 0, 0, 0);
                     acc[f][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[f].z, w.z, acc[f][n], 0, 0, 0);
                     acc[f][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[f].w, w.w, acc[f][n], 0, 0, 0);
+                }
+            }
+        }
+        if constexpr (HALF) {  // the 8-deep chunk behind the full ones: [DG co][8], 8-byte slot kk at kk ^ pc_w_swizzle(co)
+            const float* wh = wt + NCC * DG * 16;
+            float2 a[PC_FT];
+#pragma unroll
+            for (int f = 0; f < PC_FT; ++f) a[f] = *(const float2*)(xa + f * 16 * RS + 16 * NCC - 2 * kk);  // (xa holds + 4 kk: here + 2 kk)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                const float2 w = n == NT - 1 ? *(const float2*)(wh + (n * 16 + l7) * 8 + 2 * kk)
+                                             : *(const float2*)(wh + (n * 16 + l15) * 8 + 2 * (kk ^ pc_w_swizzle(l15)));
+#pragma unroll
+                for (int f = 0; f < PC_FT; ++f) {
+                    acc[f][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[f].x, w.x, acc[f][n], 0, 0, 0);
+                    acc[f][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[f].y, w.y, acc[f][n], 0, 0, 0);
                 }
             }
         }
@@ -138,6 +165,7 @@ __global__ __launch_bounds__(256) void posconv_kernel(PosConvParams p) {
     for (int f = 0; f < PC_FT; ++f)
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
+            if (HALF && n == NT - 1 && l15 >= 8) continue;  // the half tile's mirror lanes
             const int c = g * DG + n * 16 + l15;
             const float bias = p.bias[c];
 #pragma unroll
@@ -154,7 +182,7 @@ __global__ __launch_bounds__(256) void posconv_kernel(PosConvParams p) {
 template <int DG>
 hipError_t pc_launch(const PosConvParams& p, hipStream_t s) {
     const int rows = PC_TM + p.K - 1;
-    const size_t lds = (size_t)(((rows * (DG + 8) + 3) & ~3) + 2 * DG * DG) * sizeof(float);
+    const size_t lds = (size_t)(((rows * (DG + (DG % 16 ? 16 : 8)) + 3) & ~3) + 2 * DG * DG) * sizeof(float);
     hipError_t e = ensure_dynamic_lds<posconv_kernel<DG>>((int)lds);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((p.T + PC_TM - 1) / PC_TM) * p.G * p.B));  // 1-D: pc_work maps it XCD-aware (G % 8 == 0: same count)
@@ -359,11 +387,13 @@ hipError_t launch_posconv(const PosConvParams& p, hipStream_t s) {
     const int dg = p.D / p.G;
     if (dg * p.G != p.D) return hipErrorInvalidValue;
     switch (dg) {
+        case 24: return pc_launch<24>(p, s);
         case 32: return pc_launch<32>(p, s);
+        case 40: return pc_launch<40>(p, s);
         case 48: return pc_launch<48>(p, s);
         case 64: return pc_launch<64>(p, s);
     }
-    return hipErrorInvalidValue;  // D/groups must be 32, 48 or 64 (tiny / base / large)
+    return hipErrorInvalidValue;  // D/groups must be 24, 32, 40, 48 or 64
 }
 
 }  // namespace s3

@@ -35,6 +35,10 @@ class HipEncoder:
             from .ckpt import mae_ast_hot_path
 
             weights = mae_ast_hot_path("the MAE-AST weights", cfg, weights)
+        if cfg.family == "lighthubert" and "encoder.pos_conv.0.weight_v" in weights:  # the supernet's state dict: cut to the subnet
+            from .ckpt import lighthubert_slice
+
+            weights = lighthubert_slice(cfg, weights)
         self.cfg = cfg
         self.dtype = dtype
         self.check = check or os.environ.get("S3PRL_AMD_CHECK", "deferred")

@@ -40,6 +40,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _byol_s_shapes(cfg)
     if cfg.family == "mae_ast":
         return _mae_ast_shapes(cfg)
+    if cfg.family == "lighthubert":
+        return _lighthubert_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     for i, (dim, k, _) in enumerate(cfg.conv_layers):
@@ -92,6 +94,22 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         s["output_layer.0.bias"] = (D * N,)
         s["output_layer.2.weight"] = (N, D, D)
         s["output_layer.2.bias"] = (1, 1, N, D)
+    return s
+
+
+def lighthubert_supernet_config(cfg: EncoderConfig) -> EncoderConfig:
+    """The HuBERT-base shaped network a LightHuBERT checkpoint stores: 768 wide whatever subnet ``cfg`` runs (the reference
+    hard-codes it), with ``cfg``'s extractor."""
+    return EncoderConfig(family="hubert", conv_layers=cfg.conv_layers, extractor_mode=cfg.extractor_mode, conv_bias=cfg.conv_bias,
+                         conv_pos=cfg.conv_pos, conv_pos_groups=cfg.conv_pos_groups, normalize=True)
+
+
+def _lighthubert_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """The SUPERNET state dict of a LightHuBERT checkpoint (``s3prl_amd.ckpt.lighthubert_slice`` cuts it to ``cfg``'s subnet), with
+    the two tensors the forward never reads, so that a written file is one the reference's ``load_state_dict`` takes."""
+    s = param_shapes(lighthubert_supernet_config(cfg))
+    s["mask_emb"] = (768,)
+    s["layer_pred_heads.11.weight"] = (768, 768)
     return s
 
 
@@ -421,6 +439,8 @@ def synth_weights(cfg: EncoderConfig, seed: int = 0, profile: str = "synthetic")
     if profile not in PROFILES:
         raise ValueError(f"profile must be one of {PROFILES}, got {profile!r}")
     out = _synthetic(cfg, seed)
+    if cfg.family == "lighthubert":  # the statistics profile is the supernet's: a HuBERT-base shaped network
+        return _pretrained_like(lighthubert_supernet_config(cfg), out, seed) if profile == "pretrained_like" else out
     return _pretrained_like(cfg, out, seed) if profile == "pretrained_like" else out
 
 
@@ -689,6 +709,14 @@ def named_config(name: str) -> EncoderConfig:
         "tiny_data2vec": dict(family="wav2vec2", **{**tiny, "extractor_mode": "layer_norm", "conv_pos": 15,
                                                    "pos_conv_depth": 3, "normalize": True}),
         "tiny_hubert": dict(family="hubert", **tiny),
+        # LightHuBERT (upstream/lighthubert): the subnets its three released checkpoints run.  The reference hard-codes the 768-wide
+        # 12-layer supernet and the subnet shapes, so there is no tiny variant: synth_weights draws the supernet at its real width
+        "lighthubert_base": dict(family="lighthubert", lh_model="hubert_pruner", lh_supernet="base", extractor_mode="layer_norm",
+                                 normalize=True, encoder_embed_dim=640, encoder_ffn_embed_dim=2560, encoder_attention_heads=10),
+        "lighthubert_small": dict(family="lighthubert", lh_model="hubert_pruner", lh_supernet="small", extractor_mode="layer_norm",
+                                  normalize=True, encoder_embed_dim=384, encoder_ffn_embed_dim=1536, encoder_attention_heads=6),
+        "lighthubert_stage1": dict(family="lighthubert", lh_model="student_hubert", lh_supernet="base", extractor_mode="layer_norm",
+                                   normalize=True),
         # multires-HuBERT (mrhubert_mono_base: 20 ms -> 40 ms -> 20 ms, 4 layers each; the hyper-parameters are those of
         # the released checkpoint's config as far as the reference tree shows them: hubert_model.py:97-330 defaults)
         "multires_hubert_base": dict(family="multires_hubert", label_rate_ratios=[1, 2], block_layers=[4, 4, 4]),
