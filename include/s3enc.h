@@ -1132,6 +1132,58 @@ int s3enc_op_layernorm_eps(const float* x, const float* gamma, const float* beta
 int s3enc_op_input_repr(const float* feat, const float* w, const float* bias, const float* pos_host, int32_t Tc, const float* gamma,
                         const float* beta, float eps, int64_t rows, int32_t F, int32_t D, float* out, void* stream);
 
+/* ---- the plain signal features: `spectrogram`, `mfcc`, `mel`, `linear` (upstream/baseline) and `stft_mag` (upstream/log_stft) ----
+ * Exact fp32 at 16 kHz.  kind:
+ *   S3ENC_SPECTRAL_SPECTROGRAM  torchaudio.compliance.kaldi.spectrogram (snip_edges, mean removal, pre-emphasis, povey window,
+ *       zero-padded to the next power of two): log(max(|X|^2, eps32)) over bins 0 .. n/2, bin 0 replaced by the frame's raw log
+ *       energy floored at log(1) = 0 -> deltas -> CMVN                                               (extracter.py:32-90)
+ *   S3ENC_SPECTRAL_MFCC         kaldi.mfcc: the fbank log-mel at num_mel_bins (23), the orthonormal DCT-II's first num_ceps
+ *       columns (column 0 sqrt(1 / num_mel_bins)), the lifter 1 + 0.5 Q sin(pi i / Q) -> deltas -> CMVN
+ *   S3ENC_SPECTRAL_LINEAR / _MEL  the OnlinePreprocessor without a level normalisation (preprocessor.py:150-223, expert.py:55-67):
+ *       T = 1 + max length / 160 centred reflect hann frames (400 / 160) of the zero-PADDED batch rows, log(|X|^2 + 1e-10) of the
+ *       201 bins or of num_mel_bins HTK triangles.  With CMVN: over round(L' / (max length / T)) frames, L' = 1 + the index of the
+ *       utterance's last NON-ZERO sample (an all-zero one: max length), zeros behind, and the batch cut to the largest such count,
+ *       R (the reference's re-padding to max L' slices the channel axis and changes nothing); without: R = T.  Then
+ *       min(round(length * (R / lengths[0])), R) rows are kept (Python's rounding both times)
+ *   S3ENC_SPECTRAL_STFT_MAG     per utterance torch.stft(n_fft, hop, win, periodic hann, center, reflect): |X| (not the power),
+ *       with log: log(max(|X|, 1e-8)); 1 + n / hop frames; an utterance of n_fft / 2 samples or fewer is refused
+ * Fields a kind does not read are ignored.  CMVN: per column over time, unbiased std, cmvn_eps added to the std. */
+#define S3ENC_SPECTRAL_SPECTROGRAM 0
+#define S3ENC_SPECTRAL_MFCC 1
+#define S3ENC_SPECTRAL_LINEAR 2
+#define S3ENC_SPECTRAL_MEL 3
+#define S3ENC_SPECTRAL_STFT_MAG 4
+typedef struct s3enc_spectral_config {
+    int32_t kind;
+    int32_t sample_rate;      /* 16000 */
+    float frame_length_ms;    /* kaldi kinds: 25 */
+    float frame_shift_ms;     /* kaldi kinds: 10 */
+    float preemphasis;        /* kaldi kinds: 0.97 */
+    int32_t num_mel_bins;     /* mfcc: 23 (kaldi bank); mel: 80 (HTK bank) */
+    int32_t num_ceps;         /* mfcc: 13, <= num_mel_bins */
+    float cepstral_lifter;    /* mfcc: 22; 0 = none */
+    int32_t delta_order;      /* kaldi kinds: 0..2 (spectrogram.yaml 0, mfcc.yaml 2) */
+    int32_t delta_win_length; /* 5 */
+    int32_t use_cmvn;
+    float cmvn_eps;           /* 1e-10 */
+    int32_t log;              /* stft_mag: 0 / 1; linear and mel: 1 */
+    int32_t n_fft;            /* stft_mag: 512 (a multiple of 4); linear and mel: 400 */
+    int32_t hop;              /* stft_mag: 320 (a multiple of 4); linear and mel: 160 */
+    int32_t win;              /* stft_mag: 512 (<= n_fft, centred in it); linear and mel: 400 */
+} s3enc_spectral_config;
+/* frames[b] (HOST, B values) = the rows utterance b occupies in the output of the forward below; the output needs T_max >= the
+ * largest.  The kaldi kinds and stft_mag read the lengths only (wavs may be null, no device is touched) and return 0 frames for
+ * an utterance under one window (stft_mag: n_fft / 2 samples or fewer); linear and mel run the last-non-zero reduction over the
+ * device waveforms on `stream` and synchronise it. */
+int s3enc_spectral_num_frames(const s3enc_spectral_config* cfg, const float* const* wavs, const int64_t* lengths, int32_t B,
+                              int32_t* frames, int32_t device, void* stream);
+/* wavs: host array of B device pointers (borrowed, 4-byte alignment suffices); out: device fp32 (B, T_max, F), zero behind each
+ * utterance's rows; F = (padded window / 2 + 1) x (delta_order + 1), num_ceps x (delta_order + 1), 201, num_mel_bins, n_fft / 2 + 1.
+ * One frame under CMVN is NaN, as in the reference.  The kaldi kinds and stft_mag are asynchronous on `stream`; linear and mel
+ * synchronise it (the frame count depends on the samples). */
+int s3enc_spectral_forward(const s3enc_spectral_config* cfg, const float* const* wavs, const int64_t* lengths, int32_t B, float* out,
+                           int64_t T_max, int32_t device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

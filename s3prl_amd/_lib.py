@@ -161,6 +161,16 @@ class S3FbankConfig(C.Structure):
                 ("delta_win_length", C.c_int32), ("use_cmvn", C.c_int32), ("cmvn_eps", C.c_float)]
 
 
+SPECTRAL_KINDS = {"spectrogram": 0, "mfcc": 1, "linear": 2, "mel": 3, "stft_mag": 4}  # S3ENC_SPECTRAL_*
+
+
+class S3SpectralConfig(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("sample_rate", C.c_int32), ("frame_length_ms", C.c_float), ("frame_shift_ms", C.c_float),
+                ("preemphasis", C.c_float), ("num_mel_bins", C.c_int32), ("num_ceps", C.c_int32), ("cepstral_lifter", C.c_float),
+                ("delta_order", C.c_int32), ("delta_win_length", C.c_int32), ("use_cmvn", C.c_int32), ("cmvn_eps", C.c_float),
+                ("log", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("win", C.c_int32)]
+
+
 # every symbol include/s3enc.h declares: (restype, argtypes)
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 _PROTOS = {
@@ -236,6 +246,8 @@ _PROTOS = {
     "s3enc_fbank_num_frames": (C.c_int, [C.POINTER(S3FbankConfig), _I64, C.POINTER(_I32)]),
     "s3enc_fbank_forward": (C.c_int, [C.POINTER(S3FbankConfig), _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
     "s3enc_fbank_forward_ex": (C.c_int, [C.POINTER(S3FbankConfig), _I32, _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
+    "s3enc_spectral_num_frames": (C.c_int, [C.POINTER(S3SpectralConfig), _VP, C.POINTER(_I64), _I32, C.POINTER(_I32), _I32, _VP]),
+    "s3enc_spectral_forward": (C.c_int, [C.POINTER(S3SpectralConfig), _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
     "s3enc_logmel_frame_counts": (C.c_int, [C.POINTER(_I64), _I32, _I64, C.POINTER(_I32)]),
     "s3enc_logmel_forward": (C.c_int, [_VP, C.POINTER(_I64), _I32, _I64, _I32, C.c_float, _I32, C.POINTER(_I32), _VP, _I32, _VP]),
     "s3enc_op_layernorm_eps": (C.c_int, [_VP, _VP, _VP, C.c_float, _I64, _I32, _VP, _VP]),

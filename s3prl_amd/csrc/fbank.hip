@@ -83,7 +83,37 @@ hipError_t build_plan(FbankPlan& pl, int nmel, int size, int shift, double preem
     return e != hipSuccess ? e : upload_bank(pl.bank, kaldi_bank(nb, nmel, sample_rate, pl.padded), nb, nmel);
 }
 
+// under g_mu
+hipError_t plan_for(const FbankParams& c, int dev, int size, int shift, FbankPlan** out) {
+    const std::vector<long> key{dev, c.num_mel_bins, size, shift, (long)std::lround(c.preemph * 1e6), c.sample_rate, c.window};
+    FbankPlan& pl = g_plans[key];
+    *out = &pl;
+    return pl.dft ? hipSuccess : build_plan(pl, c.num_mel_bins, size, shift, c.preemph, c.sample_rate, c.window);
+}
+
 }  // namespace
+
+hipError_t fbank_operand(const FbankParams& c, FbankOperand* op) {
+    const int size = (int)(c.sample_rate * c.frame_length_ms * 0.001), shift = (int)(c.sample_rate * c.frame_shift_ms * 0.001);
+    if (size <= 0 || shift <= 0 || (size & 3) || (shift & 3) || c.num_mel_bins <= 0 || c.window < 0 || c.window > 1)
+        return hipErrorInvalidValue;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(g_mu);
+    FbankPlan* pl = nullptr;
+    e = plan_for(c, dev, size, shift, &pl);
+    if (e != hipSuccess) return e;
+    *op = FbankOperand{pl->dft, pl->bank, pl->size, pl->shift, pl->nbin};
+    return hipSuccess;
+}
+
+void launch_fbank_delta(float* out, long T, int nmel, int ldo, int order, int delta_win, hipStream_t st) {
+    const int nw = (delta_win - 1) / 2;
+    const float inv = 3.0f / (float)(nw * (nw + 1) * (2 * nw + 1));
+    const long tot = T * nmel;
+    hipLaunchKernelGGL(fbank_delta_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, out, T, nmel, ldo, order, nw, inv);
+}
 
 long fbank_num_frames(long n, const FbankParams& c) {
     const int size = (int)(c.sample_rate * c.frame_length_ms * 0.001), shift = (int)(c.sample_rate * c.frame_shift_ms * 0.001);
@@ -102,12 +132,10 @@ hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* o
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lock(g_mu);
-    const std::vector<long> key{dev, c.num_mel_bins, size, shift, (long)std::lround(c.preemph * 1e6), c.sample_rate, c.window};
-    FbankPlan& pl = g_plans[key];
-    if (!pl.dft) {
-        e = build_plan(pl, c.num_mel_bins, size, shift, c.preemph, c.sample_rate, c.window);
-        if (e != hipSuccess) return e;
-    }
+    FbankPlan* plan = nullptr;
+    e = plan_for(c, dev, size, shift, &plan);
+    if (e != hipSuccess) return e;
+    FbankPlan& pl = *plan;
     const int N2 = 2 * pl.nbin;
     FbankScratch& sc = g_scratch[std::make_pair(dev, (uintptr_t)st)];
     if ((size_t)T * N2 > sc.spec_elems) {
@@ -146,13 +174,7 @@ hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* o
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((mel_rows_kernel<POWER, LogFloor>), dim3((unsigned)T), dim3(128), pl.nbin * sizeof(float), st, sc.spec, pl.nbin,
                        (int)T, pl.bank.bands, pl.bank.wts, pl.nmel, LogFloor{FLT_EPSILON}, out, 0L, (long)ldo, nullptr);
-    if (c.delta_order > 0) {
-        const int nw = (c.delta_win - 1) / 2;
-        const float inv = 3.0f / (float)(nw * (nw + 1) * (2 * nw + 1));
-        const long tot = T * pl.nmel;
-        hipLaunchKernelGGL(fbank_delta_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, out, T, pl.nmel, ldo,
-                           c.delta_order, nw, inv);
-    }
+    if (c.delta_order > 0) launch_fbank_delta(out, T, pl.nmel, ldo, c.delta_order, c.delta_win, st);
     if (c.use_cmvn)
         launch_cmvn(out, nullptr, (int)T, pl.nmel * (c.delta_order + 1), 1, ldo, 0, c.cmvn_eps, st);
     return hipGetLastError();

@@ -678,6 +678,8 @@ struct LogmelParams {
     float* spec;               // scratch, logmel_spec_elems floats
     float* out;                // row (b, t) at out + b * o_bs + t * n_mels, t < logmel_num_frames(max_len)
     long o_bs;
+    int no_level;              // 1: no level scaling in front (the `mel` / `linear` baselines); 0 is Mockingjay's call, bit for bit
+    int linear;                // 1: log(|X|^2 + 1e-10) of the 201 bins themselves, rows of 201 floats (n_mels is not read)
 };
 hipError_t launch_logmel(const LogmelParams& p, hipStream_t st);
 

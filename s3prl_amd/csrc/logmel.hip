@@ -73,25 +73,27 @@ size_t logmel_sig_elems(int B, long max_len) { return (size_t)B * (size_t)((max_
 size_t logmel_spec_elems(int B, long max_len) { return (size_t)B * (size_t)logmel_num_frames(max_len) * 402; }
 
 hipError_t launch_logmel(const LogmelParams& p, hipStream_t st) {
-    if (p.B <= 0 || p.max_len <= 200 || p.n_mels < 1 || p.n_mels > 256) return hipErrorInvalidValue;
+    const int F = p.linear ? 201 : p.n_mels;
+    if (p.B <= 0 || p.max_len <= 200 || F < 1 || F > 256) return hipErrorInvalidValue;
     const long T = logmel_num_frames(p.max_len), Lp = (p.max_len + 400 + 3) & ~3L;
-    if ((long)p.B * T > 0x7fffffffL / 402 || p.B > 65535 || p.o_bs < T * p.n_mels) return hipErrorInvalidValue;
+    if ((long)p.B * T > 0x7fffffffL / 402 || p.B > 65535 || p.o_bs < T * F) return hipErrorInvalidValue;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     LogmelPlan* pl;
     {
         std::lock_guard<std::mutex> lock(g_mu);
-        pl = &g_plans[std::make_pair(dev, p.n_mels)];
+        pl = &g_plans[std::make_pair(dev, p.linear ? 1 : p.n_mels)];  // linear reads the operand only
         if (!pl->dft) {
-            e = build_plan(*pl, p.n_mels);
+            e = build_plan(*pl, p.linear ? 1 : p.n_mels);
             if (e != hipSuccess) return e;
         }
     }
-    hipLaunchKernelGGL(logmel_rms_kernel, dim3(p.B), dim3(1024), 0, st, p.wavs, p.lens, std::pow(10.0, (double)p.target_level / 20.0),
-                       p.scale);
+    if (!p.no_level)
+        hipLaunchKernelGGL(logmel_rms_kernel, dim3(p.B), dim3(1024), 0, st, p.wavs, p.lens, std::pow(10.0, (double)p.target_level / 20.0),
+                           p.scale);
     hipLaunchKernelGGL(reflect_pad_kernel<long>, dim3((unsigned)((Lp + 255) / 256), p.B), dim3(256), 0, st, p.wavs, p.lens,
-                       (const float*)p.scale, p.max_len, 200, Lp, p.sig);
+                       p.no_level ? (const float*)nullptr : (const float*)p.scale, p.max_len, 200, Lp, p.sig);
     GemmParams g{};
     g.A = p.sig;
     g.lda = 160;  // overlapping rows: frame t starts at padded sample 160 t
@@ -106,9 +108,12 @@ hipError_t launch_logmel(const LogmelParams& p, hipStream_t st) {
     g.o_bs = T * 402;
     e = launch_gemm(F32, g, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((mel_rows_kernel<POWER, LogAdd>), dim3((unsigned)(p.B * T)), dim3(128), 201 * sizeof(float), st, p.spec, 201, (int)T,
-                       pl->bank.bands, pl->bank.wts, p.n_mels, LogAdd{1e-10f}, p.out, p.o_bs, (long)p.n_mels, nullptr);
-    if (p.cmvn) launch_cmvn(p.out, p.counts, (int)T, p.n_mels, p.B, p.n_mels, p.o_bs, 1e-10f, st);
+    if (p.linear)
+        launch_spectrum_rows<POWER>(p.spec, 201, T, p.B, LogAdd{1e-10f}, nullptr, p.out, 201L, p.o_bs, st);
+    else
+        hipLaunchKernelGGL((mel_rows_kernel<POWER, LogAdd>), dim3((unsigned)(p.B * T)), dim3(128), 201 * sizeof(float), st, p.spec, 201,
+                           (int)T, pl->bank.bands, pl->bank.wts, p.n_mels, LogAdd{1e-10f}, p.out, p.o_bs, (long)p.n_mels, nullptr);
+    if (p.cmvn) launch_cmvn(p.out, p.counts, (int)T, F, p.B, F, p.o_bs, 1e-10f, st);
     return hipGetLastError();
 }
 

@@ -43,6 +43,61 @@ __global__ __launch_bounds__(256) void cmvn_kernel(float* x, const int* cnt, int
     for (int t = threadIdx.x; t < T; t += 256) xb[t * pitch] = t < L ? (float)(xb[t * pitch] - mean) * inv : 0.f;
 }
 
+// one wave per frame: the mean, then the squared deviations of the samples held in registers (never sum x^2 - (sum x)^2 / N),
+// max(log(max(e, eps)), log_floor)
+__global__ __launch_bounds__(256) void frame_energy_kernel(const float* x, long T, int size, int shift, float eps, float log_floor,
+                                                           float* energy) {
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (t >= T) return;
+    const float* f = x + t * shift;
+    float v[16], s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int i = lane + 64 * j;
+        v[j] = i < size ? f[i] : 0.f;
+        s += v[j];
+    }
+    const float mean = wave_sum(s) / (float)size;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const float d = lane + 64 * j < size ? v[j] - mean : 0.f;
+        q = fmaf(d, d, q);
+    }
+    q = wave_sum(q);
+    if (lane == 0) energy[t] = fmaxf(logf(fmaxf(q, eps)), log_floor);
+}
+
+// one workgroup per utterance: last[b] = 1 + the index of the last non-zero sample of x[b][0 .. n[b]), or `none` if all are zero
+__global__ __launch_bounds__(1024) void last_nonzero_kernel(const float* const* x, const long* n, long none, long* last) {
+    __shared__ long red[16];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long hi = 0;
+    for (long i = threadIdx.x; i < n[b]; i += 1024)
+        if (x[b][i] != 0.f) hi = i + 1;  // ascending i: the thread's last hit is its largest
+    for (int o = 32; o; o >>= 1) {
+        const long other = __shfl_xor(hi, o);
+        hi = other > hi ? other : hi;
+    }
+    if (lane == 0) red[wave] = hi;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 16; ++w) hi = red[w] > hi ? red[w] : hi;
+        last[b] = hi ? hi : none;
+    }
+}
+
+// one utterance: sig[j], j < Lp = x reflect-padded by `half` about 0 and about L - 1 (L > half), zeros behind L + 2 half
+__global__ __launch_bounds__(256) void reflect_pad_one_kernel(const float* x, long L, int half, long Lp, float* sig) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= Lp) return;
+    long p = j - half;
+    if (p < 0) p = -p;
+    if (p >= L) p = 2 * (L - 1) - p;
+    sig[j] = j < L + 2 * half && p >= 0 && p < L ? x[p] : 0.f;
+}
+
 }  // namespace
 
 std::vector<float> fold_dft(const double* win, int N, int nfft) {
@@ -157,6 +212,36 @@ hipError_t upload_bank(MelBank& b, const std::vector<float>& dense, int nbin, in
     sparsify(dense, nbin, nmel, bands, wts);
     const hipError_t e = to_device(&b.bands, bands);
     return e != hipSuccess ? e : to_device(&b.wts, wts);
+}
+
+std::vector<float> dct_lifter(int nceps, int nmel, double Q) {
+    std::vector<float> D((size_t)nceps * nmel);
+    for (int c = 0; c < nceps; ++c) {
+        const double lift = Q > 0.0 ? 1.0 + 0.5 * Q * std::sin(M_PI * c / Q) : 1.0;
+        for (int n = 0; n < nmel; ++n) {
+            const double m = c == 0 ? std::sqrt(1.0 / nmel) : std::cos(M_PI / nmel * (n + 0.5) * c) * std::sqrt(2.0 / nmel);
+            D[(size_t)c * nmel + n] = (float)(lift * m);
+        }
+    }
+    return D;
+}
+
+long preproc_rows_kept(long length, long first, long T) {
+    const double ratio = (double)T / (double)first;
+    const long v = (long)std::nearbyint((double)length * ratio);  // Python's round(): half to even, the default rounding mode
+    return v < 0 ? 0 : (v > T ? T : v);
+}
+
+void launch_frame_energy(const float* x, long T, int size, int shift, float eps, float log_floor, float* energy, hipStream_t st) {
+    hipLaunchKernelGGL(frame_energy_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, x, T, size, shift, eps, log_floor, energy);
+}
+
+void launch_last_nonzero(const float* const* x, const long* n, int B, long none, long* last, hipStream_t st) {
+    hipLaunchKernelGGL(last_nonzero_kernel, dim3(B), dim3(1024), 0, st, x, n, none, last);
+}
+
+void launch_reflect_pad_one(const float* x, long L, int half, long Lp, float* sig, hipStream_t st) {
+    hipLaunchKernelGGL(reflect_pad_one_kernel, dim3((unsigned)((Lp + 255) / 256)), dim3(256), 0, st, x, L, half, Lp, sig);
 }
 
 void launch_cmvn(float* x, const int* cnt, int T, int cols, int B, long pitch, long x_bs, float eps, hipStream_t st) {
