@@ -120,7 +120,22 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * reference's in-place index_put aliases it), followed by the encoder_layers layer OUTPUTS; the layer-0 input (behind the
         * positional conv and encoder.layer_norm), HuBERT's element 0, is not a state.  One selection (S3ENC_SEL_HIDDEN).
         * compute_dtype S3ENC_F32 only, layer_norm_first = 0, pos_conv_depth <= 1 (s3enc_create refuses the rest by name). */
-       S3ENC_LIGHTHUBERT = 15 };
+       S3ENC_LIGHTHUBERT = 15,
+       /* DeCoAR 2.0 (upstream/decoar2/{audio,decoar2,expert}.py; decoar2, decoar2_custom, decoar2_local, decoar2_url): HuBERT-base's
+        * post-LN encoder behind DeCoAR's kaldi front end instead of a conv extractor.  Through s3enc_create / s3enc_create_ex, no second
+        * block: s3enc_config carries the frame geometry as a one-layer "conv stack", n_conv = 1, conv_kernel[0] / conv_stride[0] = 400 /
+        * 160, conv_dim = 80 mel bins (the family's constants: every other value is refused), extractor_layer_norm = 0, conv_bias = 0,
+        * normalize = 0.  Front end: torchaudio.compliance.kaldi.fbank(80 bins, hamming) at 16 kHz -> CMVN over the utterance's own F
+        * frames (unbiased std, eps 1e-10 added to it) -> every second frame: T = ceil(F / 2), F = 1 + (n - 400) / 160; one batch-wide
+        * pass (fbank.hip: launch_fbank_batch).  post_extract_proj Linear(80, embed_dim) reads every second row and zeroes rows at and
+        * after T_b; from there HuBERT's path: positional conv, encoder.layer_norm, the layers with key padding.  The front end and the
+        * projection are exact fp32 in every compute_dtype.  encoder_layers + 1 states for S3ENC_SEL_HIDDEN — the layer inputs, then the
+        * encoder output; the other selections are refused (the expert has one list).  Padded rows: HuBERT's rule, the reference's values.
+        * s3enc_num_frames / s3enc_valid_frames are ceil(F / 2), s3enc_downsample_rate 320.  Checkpoint tensors: post_extract_proj.{weight
+        * (embed_dim, 80), bias}, encoder.pos_conv.0.{weight_g,weight_v,bias}, encoder.layer_norm.*, encoder.layers.N.*.  Refused by name:
+        * layer_norm_first, pos_conv_depth > 1, the Conformer / WavLM / DistilHuBERT options, and by the forward an utterance with F < 2
+        * (the reference's std over one frame is NaN). */
+       S3ENC_DECOAR2 = 16 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -319,8 +334,8 @@ typedef struct s3enc_mockingjay_config {
  * 2 hidden (the width of a state), encoder_layers = the number of states - 1 (0, or num_layers - 1 with per_layer_states).
  * Front end: torchaudio.compliance.kaldi.fbank(num_mel_bins, window_type = hamming) at 16 kHz -> CMVN over time (unbiased std, eps
  * 1e-10 added to the std), then every `subsample`-th frame: f fbank frames give ceil(f / subsample) model frames.  The reference's
- * decoar / decoar_layers front end keeps every frame (subsample 1); 2 is the front end of DeCoAR 2.0 (decoar2/audio.py:84) and
- * costs nothing here: the projection reads its rows at twice the stride.  Model: post_extract_proj (Linear), then per layer and
+ * decoar / decoar_layers front end keeps every frame (subsample 1); 2 is the front end of DeCoAR 2.0 (decoar2/audio.py:84; served
+ * by S3ENC_DECOAR2 on the batch-wide pass) and costs nothing here: the projection reads its rows at twice the stride.  Model: post_extract_proj (Linear), then per layer and
  * direction an nn.LSTM layer on packed sequences — the backward stack on every utterance's own rows in reverse — and the two
  * outputs side by side.  Checkpoint tensors, reference state_dict names: post_extract_proj.{weight,bias},
  * {forward,backward}_lstm.{weight_ih,weight_hh,bias_ih,bias_hh}_lN, every one of them required.  Refused by name: every compute
@@ -1111,6 +1126,16 @@ int s3enc_fbank_forward(const s3enc_fbank_config* cfg, const float* const* wavs,
  * 0.54 - 0.46 cos(2 pi i / (N - 1)) (APC's front end, apc/audio.py:22,82-88).  s3enc_fbank_config is unchanged. */
 int s3enc_fbank_forward_ex(const s3enc_fbank_config* cfg, int32_t window, const float* const* wavs, const int64_t* lengths,
                            int32_t B, float* out, int64_t T_max, int32_t device, void* stream);
+/* The batch-wide pass of the same front end (fbank.hip: launch_fbank_batch; what S3ENC_DECOAR2 runs): ONE overlapping-row GEMM over
+ * the padded batch, one power -> mel -> log launch, one CMVN launch with per-utterance counts.  cfg: delta_order 0 and use_cmvn 1 (the
+ * rest is refused by name).  pcm: DEVICE (B, row_stride) fp32, 16-byte aligned, row_stride a multiple of 4 and >= n_max; whatever stands
+ * behind an utterance's own samples is never part of a valid row.  lengths: HOST [B] samples, each at least one analysis window;
+ * n_max: the batch's padded length (0: the longest utterance).  out: DEVICE (B, Fmax, num_mel_bins), Fmax =
+ * s3enc_fbank_num_frames(n_max): rows [0, F_b) of utterance b are bit for bit what s3enc_fbank_forward_ex gives for it alone, rows
+ * [F_b, Fmax) are exactly 0 (written by the last kernel, no memset in front).  spec_cap_bytes: the cap on the spectrum workspace (2 x 257
+ * floats per frame); 0: the default 128 MiB.  A batch above it is walked in chunks of whole utterances.  Synchronises. */
+int s3enc_op_fbank_batch(const s3enc_fbank_config* cfg, int32_t window, const float* pcm, int64_t row_stride, const int64_t* lengths,
+                         int32_t B, int64_t n_max, float* out, int64_t spec_cap_bytes, int32_t device, void* stream);
 
 
 /* ---- the OnlinePreprocessor log-mel front end (Mockingjay / TERA / AudioALBERT, upstream/baseline/preprocessor.py) ----

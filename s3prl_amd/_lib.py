@@ -20,7 +20,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13, "byol_s": 14, "lighthubert": 15}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13, "byol_s": 14, "lighthubert": 15, "decoar2": 16}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -246,6 +246,7 @@ _PROTOS = {
     "s3enc_fbank_num_frames": (C.c_int, [C.POINTER(S3FbankConfig), _I64, C.POINTER(_I32)]),
     "s3enc_fbank_forward": (C.c_int, [C.POINTER(S3FbankConfig), _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
     "s3enc_fbank_forward_ex": (C.c_int, [C.POINTER(S3FbankConfig), _I32, _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
+    "s3enc_op_fbank_batch": (C.c_int, [C.POINTER(S3FbankConfig), _I32, _VP, _I64, C.POINTER(_I64), _I32, _I64, _VP, _I64, _I32, _VP]),
     "s3enc_spectral_num_frames": (C.c_int, [C.POINTER(S3SpectralConfig), _VP, C.POINTER(_I64), _I32, C.POINTER(_I32), _I32, _VP]),
     "s3enc_spectral_forward": (C.c_int, [C.POINTER(S3SpectralConfig), _VP, C.POINTER(_I64), _I32, _VP, _I64, _I32, _VP]),
     "s3enc_logmel_frame_counts": (C.c_int, [C.POINTER(_I64), _I32, _I64, C.POINTER(_I32)]),

@@ -6,6 +6,7 @@
 * DistilHuBERT ``{"Config": {"distiller": {...}}, "Distiller": state_dict}``      (distiller/builder.py:41-58,119-122)
 * multires-HuBERT: the HuBERT layout with ``MultiresHubertConfig`` in ``model_cfg``  (multires_hubert/convert.py:21-62)
 * LightHuBERT ``{"cfg": {"model": {...}}, "model": supernet state_dict}``         (lighthubert/expert.py:17-47): cut to its subnet here
+* DeCoAR 2.0 ``{"model": state_dict}``, no configuration: the widths come from the tensors' shapes  (decoar2/expert.py:20-26)
 
 plus the fairseq layout ``{"cfg": {"task", "model"}, "model"}`` that ``hubert_custom(fairseq=True)`` /
 ``wav2vec2_custom(fairseq=True)`` convert first (hubert/convert.py:22-40, wav2vec2/convert.py:14-24).
@@ -20,7 +21,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import EncoderConfig, LIGHTHUBERT_SUPERNET, config_from_lighthubert, byol_a_config, byol_s_config, config_from_mae_ast, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
+from .config import EncoderConfig, LIGHTHUBERT_SUPERNET, config_from_decoar2, config_from_lighthubert, byol_a_config, byol_s_config, config_from_mae_ast, decoar_config, vggish_config, config_from_apc, config_from_npc, config_from_cpc, config_from_mockingjay, config_from_dicts, config_from_distiller, config_from_multires, config_from_wav2vec
 from .synth import lighthubert_supernet_config, param_shapes
 
 _REQUIRED = {
@@ -325,6 +326,25 @@ def load_decoar_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarr
     return cfg, _hot_path_weights(ckpt, cfg, sd)
 
 
+def load_decoar2_checkpoint(ckpt: str) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """``{"model": state_dict}`` (upstream/decoar2/expert.py:20-26).  The file carries no configuration — the reference's
+    ``Decoar2()`` hard-codes 80 / 768 / 12 / 3072 — so the widths, the depth and the positional conv's kernel and groups are read off
+    the tensors; heads are D / 64.  The reference loads with ``strict=False``: the tensors of the pre-training model that the encoder
+    does not own are ignored here too, but a missing tensor that it does own would silently keep its random initialisation there, so
+    every tensor the forward reads is required here, by name."""
+    import torch
+
+    state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    if "model" not in state:
+        raise ValueError(f"{ckpt} is not a valid checkpoint since the required key: model is missing")
+    sd = state["model"]
+    try:
+        cfg = config_from_decoar2(sd)
+    except ValueError as err:
+        raise ValueError(f"{ckpt}: {err}") from None
+    return cfg, _hot_path_weights(ckpt, cfg, sd)
+
+
 def mockingjay_state_dict(sd) -> Dict:
     """The legacy LayerNorm names of a ``Transformer`` state_dict, renamed as ``TransformerBuilder.load_model`` does
     (mockingjay/builder.py:136-150): ``gamma`` -> ``weight``, ``beta`` -> ``bias``."""
@@ -518,6 +538,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_mae_ast_checkpoint(ckpt)
     if family == "lighthubert":
         return load_lighthubert_checkpoint(ckpt)
+    if family == "decoar2":
+        return load_decoar2_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -569,7 +591,7 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
         # new-style files keep the runner's config under "Config" and the reference's builder reads that key first
         torch.save({"Transformer": sd, "Upstream_Config": mockingjay_upstream_config(cfg), "Config": {"runner": {}}}, path)
         return
-    if cfg.family == "decoar":  # upstream/decoar/expert.py:30-36
+    if cfg.family in ("decoar", "decoar2"):  # upstream/decoar/expert.py:30-36, upstream/decoar2/expert.py:20-26
         torch.save({"model": sd}, path)
         return
     if cfg.family == "mae_ast":  # upstream/mae_ast/expert.py:28-38

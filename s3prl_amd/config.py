@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast", "byol_s", "lighthubert")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast", "byol_s", "lighthubert", "decoar2")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -280,7 +280,7 @@ class EncoderConfig:
         r = 1
         for _, _, s in self.conv_layers:
             r *= s
-        return r
+        return 2 * r if self.family == "decoar2" else r  # decoar2/expert.py:65-66: 320, every second 10 ms frame
 
     def conv_lengths(self, n: int) -> List[int]:
         """floor((L-k)/s)+1 per layer (wav2vec2_model.py:2615-2616); modified CPC: floor((L + 2 pad - k)/s)+1."""
@@ -296,6 +296,8 @@ class EncoderConfig:
             return 1 + n // 160 if n > 200 else 0
         if self.family == "decoar":  # ceil(fbank frames / subsample)
             return -(-self.conv_lengths(n)[-1] // self.decoar_subsample)
+        if self.family == "decoar2":  # y[::2] of the fbank frames (decoar2/audio.py:84)
+            return -(-self.conv_lengths(n)[-1] // 2)
         if self.family == "mae_ast":  # time steps of kt frames; the frames behind the last whole step are dropped by nn.Unfold
             return self.conv_lengths(n)[-1] // self.ma_kt
         if self.family == "byol_s":  # windows: frame_audio's loop (byol_s/serab_byols/utils.py:79-96)
@@ -325,7 +327,7 @@ class EncoderConfig:
             return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
         if self.family == "mockingjay":
             return min(T, max(self.num_frames(length), 0))
-        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "npc", "vggish", "byol_a", "byol_s"):  # byol_s: the utterance's own windows (the rows behind them are the reference's values, not zeros); byol_a: the utterance's own segments (the rows behind them are the reference's values, not zeros); vggish: the utterance's own examples, exact zeros behind them; distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
+        if self.family in ("wav2vec2", "distiller", "wav2vec", "cpc", "apc", "decoar", "decoar2", "npc", "vggish", "byol_a", "byol_s"):  # decoar2: the utterance's own frames (decoar2/expert.py:86-94); byol_s: the utterance's own windows (the rows behind them are the reference's values, not zeros); byol_a: the utterance's own segments (the rows behind them are the reference's values, not zeros); vggish: the utterance's own examples, exact zeros behind them; distiller: cal_pad_mask, distiller/model.py:271-285; wav2vec, cpc: no mask; apc: the packed length; npc: the utterance's own frames (the rows behind them are the reference's values, not zeros)
             return min(T, max(self.num_frames(length), 0))
         chunk = n_max // T
         return min(T, -(-length // chunk))
@@ -454,6 +456,24 @@ class EncoderConfig:
                 raise ValueError("lighthubert with pos_conv_depth > 1 is not built (the released checkpoints have one positional conv)")
             if self.layer_type != "transformer":
                 raise ValueError("lighthubert: only layer_type='transformer' exists in the reference")
+        if self.family == "decoar2":
+            if list(map(tuple, self.conv_layers)) != [DECOAR2_FRONT_END]:
+                raise ValueError("decoar2: conv_layers carries the front end's constants as one (80 mel bins, 400, 160 samples) entry "
+                                 f"(decoar2_config sets it), got {self.conv_layers}")
+            if self.layer_norm_first:
+                raise ValueError("decoar2 with layer_norm_first=True is not built (the reference hard-codes a post-LN encoder)")
+            if self.pos_conv_depth > 1:
+                raise ValueError("decoar2 with pos_conv_depth > 1 is not built (the reference has one positional conv)")
+            if self.layer_type != "transformer":
+                raise ValueError("decoar2: only layer_type='transformer' exists in the reference")
+            if self.relative_position_embedding or self.pred_heads or not self.feature_layer_norm:
+                raise ValueError("decoar2 takes none of the WavLM / DistilHuBERT options")
+            if self.normalize or self.conv_bias or self.extractor_mode != "default":
+                raise ValueError("decoar2 has no conv extractor and no waveform normalisation: normalize and conv_bias must be False and "
+                                 "extractor_mode 'default'")
+            if self.encoder_embed_dim % 64 or self.encoder_attention_heads != self.encoder_embed_dim // 64:
+                raise ValueError("decoar2: embed_dim must be a multiple of 64 and heads embed_dim / 64 (768 / 12 in the reference, which "
+                                 f"hard-codes its widths), got {self.encoder_embed_dim} / {self.encoder_attention_heads}")
         if self.layer_type == "conformer":
             if self.family != "wav2vec2" or self.pos_conv_depth > 1:
                 raise ValueError("conformer layers are a wav2vec2-family encoder")
@@ -818,6 +838,49 @@ _MODEL_KEYS = (
     "encoder_attention_heads", "layer_norm_first", "conv_pos", "conv_pos_groups",
 )
 _WAVLM_KEYS = ("relative_position_embedding", "num_buckets", "max_distance", "gru_rel_pos", "normalize")
+
+
+# DeCoAR 2.0's front end as a one-layer "conv stack": (mel bins, analysis window, frame shift in samples) — the family's own constants
+# (decoar2/audio.py: kaldi.fbank's 80 bins, 25 ms / 10 ms at 16 kHz, hamming; CMVN eps 1e-10; every second frame)
+DECOAR2_FRONT_END = (80, 400, 160)
+
+
+def decoar2_config(embed_dim: int = 768, ffn_dim: int = 3072, layers: int = 12, conv_pos: int = 128, conv_pos_groups: int = 16) -> "EncoderConfig":
+    """An :class:`EncoderConfig` of family "decoar2" (decoar2/decoar2.py:9-24 hard-codes 768 / 3072 / 12 / 128 / 16).  Heads are
+    embed_dim / 64: the head count cannot be read from a tensor and the released shape is 768 / 12."""
+    D = int(embed_dim)
+    if D % 64:
+        raise ValueError(f"decoar2: embed_dim must be a multiple of 64 (heads are embed_dim / 64), got {D}")
+    if int(conv_pos_groups) < 1 or D % int(conv_pos_groups) or D // int(conv_pos_groups) not in (24, 32, 40, 48, 64):
+        raise ValueError("decoar2: embed_dim / conv_pos_groups (the positional conv's group width) must be 32, 48 or 64 (fp32: also 24 "
+                         f"or 40), got {D} / {conv_pos_groups}")
+    cfg = EncoderConfig(family="decoar2", conv_layers=[DECOAR2_FRONT_END], extractor_mode="default", conv_bias=False, normalize=False,
+                        encoder_layers=int(layers), encoder_embed_dim=D, encoder_ffn_embed_dim=int(ffn_dim),
+                        encoder_attention_heads=D // 64, layer_norm_first=False, conv_pos=int(conv_pos),
+                        conv_pos_groups=int(conv_pos_groups))
+    cfg.validate()
+    return cfg
+
+
+def config_from_decoar2(sd) -> "EncoderConfig":
+    """The configuration a DeCoAR 2.0 state dict implies: D, FFN, layers and the positional conv's K and G from the tensors' shapes."""
+    def shape(name):
+        if name not in sd:
+            raise ValueError(f"decoar2: missing parameter {name}")
+        return tuple(sd[name].shape)
+
+    D, feat = shape("post_extract_proj.weight")
+    if feat != DECOAR2_FRONT_END[0]:
+        raise ValueError(f"decoar2: post_extract_proj reads {feat} features, the front end gives {DECOAR2_FRONT_END[0]} mel bins")
+    v = shape("encoder.pos_conv.0.weight_v")
+    if len(v) != 3 or v[0] != D or v[1] < 1 or D % v[1]:
+        raise ValueError(f"decoar2: encoder.pos_conv.0.weight_v has shape {v}, expected ({D}, {D} / groups, kernel)")
+    layers = 0
+    while f"encoder.layers.{layers}.fc1.weight" in sd:
+        layers += 1
+    if layers < 1:
+        raise ValueError("decoar2: missing parameter encoder.layers.0.fc1.weight")
+    return decoar2_config(D, shape("encoder.layers.0.fc1.weight")[0], layers, v[2], D // v[1])
 
 
 LIGHTHUBERT_SUPERNET = dict(embed_dim=768, ffn_embed=3072, heads_num=12, layer_num=12)  # the checkpoint's own width, hard-coded by the reference

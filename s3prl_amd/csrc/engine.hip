@@ -7,6 +7,7 @@
 //   fc2(+residual), LN }  with every hidden-state tap written straight into the caller's (NL+1, B, T, D) slab.
 //   (multires-HuBERT continues in multires.hip after post_extract_proj; the single-kernel entry points are in ops.hip)
 #include "engine_internal.h"
+#include "spectral.h"
 
 namespace s3e {
 
@@ -14,6 +15,7 @@ thread_local std::string g_err;
 
 long conv_len(const s3enc_config& c, long n, int upto /*exclusive*/) {
     for (int i = 0; i < upto; ++i) n = n >= c.conv_kernel[i] ? (n - c.conv_kernel[i]) / c.conv_stride[i] + 1 : 0;
+    if (c.family == S3ENC_DECOAR2 && upto >= c.n_conv) n = (n + 1) / 2;  // y[::2] behind the fbank frames (decoar2/audio.py:84)
     return n;
 }
 
@@ -21,9 +23,10 @@ int valid_frames(const s3enc_config& c, long length, long n_max) {
     const long T = conv_len(c, n_max, c.n_conv);
     if (T <= 0) return 0;
     long v;
-    if (c.family == S3ENC_WAV2VEC2 || c.family == S3ENC_DISTILLER || c.family == S3ENC_WAV2VEC || c.family == S3ENC_APC || c.family == S3ENC_NPC) {
+    if (c.family == S3ENC_WAV2VEC2 || c.family == S3ENC_DISTILLER || c.family == S3ENC_WAV2VEC || c.family == S3ENC_APC || c.family == S3ENC_NPC ||
+        c.family == S3ENC_DECOAR2) {
         // wav2vec2_model.py:2652-2669; distiller/model.py:271-285; wav2vec has no mask: the frames an utterance's own samples reach;
-        // APC: the utterance's own whole analysis windows (its packed length)
+        // APC: the utterance's own whole analysis windows (its packed length); DeCoAR 2.0: every second one of them (decoar2/expert.py:86-94)
         v = conv_len(c, length, c.n_conv);
     } else {
         const long chunk = n_max / T;  // hubert_model.py:454-464
@@ -141,6 +144,21 @@ namespace {
 // the one list of them the engine has.
 const FamilyOps* const kFamilies[] = {&kWav2vecFamily, &kCpcFamily,    &kApcFamily,   &kMockingjayFamily, &kDecoarFamily,
                                       &kNpcFamily,     &kVggishFamily, &kByolAFamily, &kMaeAstFamily,     &kByolSFamily};
+// DeCoAR 2.0's front end, the family's own constants (decoar2/audio.py:8-9,70-76, kaldi.fbank's defaults; CMVN eps :16)
+s3::FbankParams decoar2_fbank_params() {
+    s3::FbankParams f;
+    f.sample_rate = 16000;
+    f.num_mel_bins = 80;
+    f.frame_length_ms = 25.f;
+    f.frame_shift_ms = 10.f;
+    f.preemph = 0.97f;
+    f.delta_order = 0;
+    f.use_cmvn = 1;
+    f.cmvn_eps = 1e-10f;
+    f.window = 1;  // hamming: the reference's WINDOW_TYPE
+    return f;
+}
+
 const FamilyOps* family_ops(int family) {  // null: a Transformer family
     for (const FamilyOps* f : kFamilies)
         if (f->family == family) return f;
@@ -172,7 +190,7 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > S3ENC_LIGHTHUBERT) return fail("config: unknown family");
+    if (c.family < 0 || c.family > S3ENC_DECOAR2) return fail("config: unknown family");
     if (family_ops(c.family)) return 0;  // its record's own check runs on both configuration blocks (create_impl)
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
@@ -194,9 +212,20 @@ int check_config(const s3enc_config& c) {
     }
     if (c.pred_heads < 0 || c.pred_heads > 16) return fail("config: pred_heads out of range");
     if (c.pred_heads && c.family != S3ENC_DISTILLER) return fail("config: pred_heads is a DistilHuBERT feature");
-    if (c.n_conv < 2 || c.n_conv > S3ENC_MAX_CONV) return fail("config: n_conv out of range");
-    if (c.conv_kernel[0] != 10) return fail("config: the conv0 kernel is specialised for kernel width 10");
-    if (c.conv_dim % 32 || c.conv_dim > 1024) return fail("config: conv_dim must be a multiple of 32, <= 1024");
+    const bool d2 = c.family == S3ENC_DECOAR2;  // no conv extractor: the kaldi front end's constants in the conv fields
+    if (d2) {
+        if (c.n_conv != 1 || c.conv_kernel[0] != 400 || c.conv_stride[0] != 160 || c.conv_dim != 80)
+            return fail("config: DeCoAR 2.0 carries its front end as n_conv = 1, conv_kernel[0] / conv_stride[0] = 400 / 160 samples and conv_dim = 80 mel bins");
+        if (c.layer_norm_first) return fail("config: DeCoAR 2.0 with layer_norm_first is not built");
+        if (c.pos_conv_depth > 1) return fail("config: DeCoAR 2.0 with pos_conv_depth > 1 is not built");
+        if (c.layer_type || c.rel_pos || c.pred_heads || c.no_feature_layer_norm)
+            return fail("config: DeCoAR 2.0 takes none of the Conformer / WavLM / DistilHuBERT options");
+        if (c.extractor_layer_norm || c.conv_bias || c.normalize)
+            return fail("config: DeCoAR 2.0 has no conv extractor and no waveform normalisation (extractor_layer_norm, conv_bias and normalize must be 0)");
+    }
+    if (!d2 && (c.n_conv < 2 || c.n_conv > S3ENC_MAX_CONV)) return fail("config: n_conv out of range");
+    if (!d2 && c.conv_kernel[0] != 10) return fail("config: the conv0 kernel is specialised for kernel width 10");
+    if (!d2 && (c.conv_dim % 32 || c.conv_dim > 1024)) return fail("config: conv_dim must be a multiple of 32, <= 1024");
     if (c.heads <= 0 || c.embed_dim != c.heads * 64) return fail("config: head_dim must be 64");
     if (c.ffn_dim % 8) return fail("config: ffn_dim must be a multiple of 8");
     if (c.conv_pos_groups <= 0 || c.embed_dim % c.conv_pos_groups) return fail("config: embed_dim % conv_pos_groups != 0");
@@ -399,8 +428,9 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
         // profiles/r06_parity_seeds.md); it costs conv1 at the three-term rate on fp32 rows — opt-in, the default stays inside 1e-3.
         if (ok && tuning().fp16x2_conv1_f32 && x3_shape_ok(C, (long)c.conv_kernel[1] * C, (long)c.conv_stride[1] * C)) e->x2_conv_f32_from = 1;
     }
+    const bool d2 = c.family == S3ENC_DECOAR2;  // the kaldi front end has no weights
     e->conv.resize(c.n_conv);
-    for (int i = 0; i < c.n_conv; ++i) {
+    for (int i = 0; i < c.n_conv && !d2; ++i) {
         const std::string p = "feature_extractor.conv_layers." + std::to_string(i);
         const int cin = i == 0 ? 1 : C, k = c.conv_kernel[i];
         GET(p + ".0.weight", (long)C * cin * k, t);
@@ -436,16 +466,20 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
             UP(upload_f32(e->gn_b, t));
         }
     }
-    if (!c.no_feature_layer_norm) {
+    if (!c.no_feature_layer_norm && !d2) {
         GET("layer_norm.weight", C, t);
         UP(upload_f32(e->fln_g, t));
         GET("layer_norm.bias", C, t);
         UP(upload_f32(e->fln_b, t));
     }
     GET("post_extract_proj.weight", (long)D * C, t);
-    UP(upload_gemm_w(e->proj_w, t, D, C, e->dtype, e->x2));
-    e->x2_proj_f32 = e->x2 && !c.no_feature_layer_norm && c.family != S3ENC_DISTILLER && x3_shape_ok(D, C, C);
-    if (e->x3 || e->x2_proj_f32) UP(upload_x3(e->proj_w3, t, D, C));
+    if (d2) {  // K = 80 on the CMVN's output, the model's input: exact fp32 in every operand mode
+        UP(upload_f32(e->proj_w, t));
+    } else {
+        UP(upload_gemm_w(e->proj_w, t, D, C, e->dtype, e->x2));
+        e->x2_proj_f32 = e->x2 && !c.no_feature_layer_norm && c.family != S3ENC_DISTILLER && x3_shape_ok(D, C, C);
+        if (e->x3 || e->x2_proj_f32) UP(upload_x3(e->proj_w3, t, D, C));
+    }
     GET("post_extract_proj.bias", D, t);
     UP(upload_f32(e->proj_b, t));
 
@@ -799,6 +833,7 @@ int s3enc_downsample_rate(s3enc_handle h, int32_t* rate) {
     if (!h || !rate) return fail("s3enc_downsample_rate: null argument");
     int r = 1;
     for (int i = 0; i < h->cfg.n_conv; ++i) r *= h->cfg.conv_stride[i];
+    if (h->cfg.family == S3ENC_DECOAR2) r *= 2;  // every second frame: 320, what the reference's get_downsample_rates returns
     *rate = h->ops && h->ops->rate ? h->ops->rate(h) : r;
     return 0;
 }
@@ -1092,6 +1127,9 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     const bool lhb = c.family == S3ENC_LIGHTHUBERT;  // hidden_states[0] = post_extract_proj's output, then the layer outputs
     if (lhb && fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: feature_selection is not defined for LightHuBERT (its expert returns one hidden_states list)");
+    const bool d2 = c.family == S3ENC_DECOAR2;  // the batch-wide kaldi front end in place of the conv extractor
+    if (d2 && fo.selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_forward: feature_selection is not defined for DeCoAR 2.0 (its expert returns one hidden_states list)");
     const bool conf = c.layer_type == 1;
     if (conf && fo.selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_forward: feature_selection is not defined for a Conformer encoder (the reference's ConformerEncoder records "
@@ -1102,10 +1140,20 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         return fail("s3enc_forward: out_dtype must be S3ENC_F32 or the handle's own 16-bit compute dtype");
     long n_max;
     if (batch_n_max(wav_ptrs_host, lengths, B, n_max_in, n_max)) return 1;
-    std::vector<long> L(c.n_conv);
+    std::vector<long> L(std::max(c.n_conv, 2), 0L);
     for (int i = 0; i < c.n_conv; ++i) L[i] = conv_len(c, n_max, i + 1);
     const long T = L[c.n_conv - 1];
     if (T < 1) return fail("s3enc_forward: input shorter than the receptive field of the conv stack");
+    // DeCoAR 2.0: the fbank frames of the padded batch and of every utterance; L[0] = T = ceil(d2_F / 2)
+    const long d2_F = d2 ? s3::fbank_num_frames(n_max, decoar2_fbank_params()) : 0;
+    const long d2_stride = (n_max + 3) & ~3L;  // row pitch of the staged PCM
+    std::vector<int> d2_frames(d2 ? B : 0);
+    for (int b = 0; d2 && b < B; ++b) {
+        d2_frames[b] = (int)s3::fbank_num_frames(lengths[b], decoar2_fbank_params());
+        if (d2_frames[b] < 2)
+            return fail("s3enc_forward: an utterance has fewer than 2 analysis windows (DeCoAR 2.0's front end normalises by the standard deviation over time: one frame has none)");
+    }
+    if (d2 && d2_F > 0x7fffffffL / 1024) return fail("s3enc_forward: batch too large");
     const long M = (long)B * T;
     MrPlan plan;  // multires-HuBERT: the frame geometry of the U-net; the states are (B, plan.T_out, D)
     if (mr) mr_plan(c, T, plan);
@@ -1141,7 +1189,7 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     if (!dg.ok) return fail("s3enc_forward: hipSetDevice failed");
 
     // ---- small device state: tables + stats ----
-    const size_t tbl_bytes = (size_t)B * (8 + 8 + 4) + valid_blk.size() * 4;
+    const size_t tbl_bytes = (size_t)B * (8 + 8 + 4) + (valid_blk.size() + d2_frames.size()) * 4;  // (never both: one tail)
     const size_t part_elems = stats_partial_elems(B, n_max);
     {
         Bump sb(nullptr);
@@ -1166,18 +1214,27 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     for (int b = 0; b < B; ++b) ((long*)(hp + (size_t)B * 8))[b] = (long)lengths[b];
     memcpy(hp + (size_t)B * 16, valid.data(), (size_t)B * 4);
     if (!valid_blk.empty()) memcpy(hp + (size_t)B * 20, valid_blk.data(), valid_blk.size() * 4);
+    if (d2) memcpy(hp + (size_t)B * 20, d2_frames.data(), (size_t)B * 4);
+    const int* d_frames = (const int*)(d_tbl + (size_t)B * 20);  // DeCoAR 2.0: every utterance's fbank frames
     if (stage_commit(e, hp, d_tbl, tbl_bytes, st)) return 1;
 
     // ---- workspace ----
     const bool lnmode = c.extractor_layer_norm != 0;
     const bool prel = c.layer_norm_first != 0;
     const bool gated = c.rel_pos && c.gru_rel_pos;
-    const bool featln = !c.no_feature_layer_norm;
+    const bool featln = !c.no_feature_layer_norm && !d2;
     const bool ffn_tap = fo.selection == S3ENC_SEL_FFN_OUT;
     const long HW = std::max<long>(F, (long)NH * D);  // widest row of the FFN / prediction-head intermediate
     void *actA, *actB, *tmp32, *feat32, *featT, *x32, *xpc, *xT, *qkv, *attn, *tmp1, *tmp2, *hbuf, *gate, *ffnbuf, *lnst, *cbuf, *pbuf;
+    float *d2_pcm = nullptr, *d2_feat = nullptr, *d2_spec = nullptr;  // DeCoAR 2.0: staged PCM rows, (B, d2_F, 80) log-mels, spectra
+    const size_t d2_spec_bytes = d2 ? s3::fbank_batch_workspace(decoar2_fbank_params(), B, d2_F, 0) : 0;
     for (int pass = 0; pass < 2; ++pass) {
         Bump wb(pass ? e->ws.p : nullptr);
+        if (d2) {
+            d2_pcm = (float*)wb.take((size_t)B * d2_stride * 4);
+            d2_feat = (float*)wb.take((size_t)B * d2_F * C * 4);
+            d2_spec = (float*)wb.take(d2_spec_bytes);
+        }
         // conv0's output in the compute dtype; in the fp16x2 hybrid conv2, conv4, ... write fp32 rows back here: L[2] <= L[0] / 2
         // only when conv1 * conv2 stride >= 2, which no config validation promises
         actA = wb.take(std::max((size_t)B * L[0] * C * (e->x2_conv_f32_from == 1 ? 4 : es),
@@ -1246,16 +1303,27 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         e->taps[name] = {kp, elems, tdt};
         return hipSuccess;
     };
-    {
+    if (d2) {
+        // every utterance's samples into one (B, d2_stride) slab, zeros behind them: the batched GEMM wants one row pitch
+        {
+            Prof pr(e, st, "decoar2_stage", 0, 8.0 * B * n_max);
+            hipLaunchKernelGGL((s3::reflect_pad_kernel<long>), dim3((unsigned)((d2_stride + 255) / 256), B), dim3(256), 0, st, d_ptrs, d_lens,
+                               (const float*)nullptr, n_max, 0, d2_stride, d2_pcm);
+        }
+        Prof pr(e, st, "decoar2_fbank", 2.0 * B * d2_F * 514 * 400, 4.0 * ((double)B * n_max + (double)B * d2_F * (2 * 514 + 2 * C)));
+        HIP_TRY(s3::launch_fbank_batch(decoar2_fbank_params(), d2_pcm, d2_stride, d_frames, B, d2_F, d2_feat, C, d2_spec, d2_spec_bytes, 0, st));
+        e->taps["fbank"] = {d2_feat, (long)B * d2_F * C, F32};
+    }
+    if (!d2) {
         Prof pr(e, st, "wav_stats", 0, 4.0 * B * n_max);
         HIP_TRY(launch_wav_norm_stats(wt, c.normalize, d_part, d_norm, st, c.wav_norm_eps));
     }
-    if (!lnmode) {
+    if (!lnmode && !d2) {
         Prof pr(e, st, "gn_stats", 0, 4.0 * B * n_max);
         HIP_TRY(launch_gn_stats(wt, d_norm, (const float*)e->conv[0].w.p, (const float*)e->gn_g.p, (const float*)e->gn_b.p, C,
                                 c.conv_kernel[0], c.conv_stride[0], L[0], d_part, nullptr, d_gn, st));
     }
-    {
+    if (!d2) {
         Conv0Params p{};
         p.wav = wt;
         p.norm = d_norm;
@@ -1375,9 +1443,9 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
     float* xproj = sink.slot32(si_proj) ? sink.slot32(si_proj) : (float*)x32;
     {
         GemmParams g{};
-        g.A = featT;
-        g.lda = C;
-        g.a_bs = T * C;
+        g.A = d2 ? (const void*)d2_feat : featT;
+        g.lda = d2 ? 2L * C : C;  // DeCoAR 2.0: every second fbank row costs nothing, the rows are read at twice the pitch
+        g.a_bs = d2 ? d2_F * C : T * C;
         g.W = e->proj_w.p;
         g.W_x3 = e->proj_w3.p;
         g.bias = (const float*)e->proj_b.p;
@@ -1392,7 +1460,9 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         g.o_bs = T * D;
         {
             Prof pr(e, st, "gemm:proj", 2.0 * M * D * C, ((double)M * C + (double)D * C) * es + (double)M * D * 4);
-            if (proj32 && dt != F32) {
+            if (d2) {  // fp32 operands in every mode (e->proj_w is an fp32 image, W_x3 is null)
+                HIP_TRY(launch_gemm(F32, g, st));
+            } else if (proj32 && dt != F32) {
                 if (!gemm_x3_eligible(g)) return fail("post_extract_proj is not a shape of the three-term GEMM (internal)");
                 HIP_TRY(launch_gemm(F32, g, st));
             } else {
@@ -1821,6 +1891,8 @@ int s3enc_num_states(s3enc_handle h, int32_t selection, int32_t* n) {
     if (selection < 0 || selection > 2) return fail("s3enc_num_states: unknown selection");
     if (h->cfg.family == S3ENC_LIGHTHUBERT && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: feature_selection is not defined for LightHuBERT (its expert returns one hidden_states list)");
+    if (h->cfg.family == S3ENC_DECOAR2 && selection != S3ENC_SEL_HIDDEN)
+        return fail("s3enc_num_states: feature_selection is not defined for DeCoAR 2.0 (its expert returns one hidden_states list)");
     if ((h->cfg.family == S3ENC_DISTILLER || h->cfg.family == S3ENC_MULTIRES) && selection != S3ENC_SEL_HIDDEN)
         return fail("s3enc_num_states: DistilHuBERT / multires-HuBERT have one selection (their hidden_states list)");
     if (h->cfg.layer_type == 1 && selection != S3ENC_SEL_HIDDEN)

@@ -180,4 +180,73 @@ hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* o
     return hipGetLastError();
 }
 
+// ---- the batch-wide pass ------------------------------------------------------------------------------------------------------------
+// The spectrum of a frame is 2 * nbin floats (2 * 257 at the kaldi geometry: 66 MB at 32 x 10 s).  A batch whose spectra outgrow the cap
+// is walked in chunks of whole utterances; one utterance above the cap is a chunk of its own.
+size_t fbank_batch_spec_cap() { return (size_t)128 << 20; }
+
+int fbank_batch_chunk(int B, long Fmax, int nbin, size_t cap_bytes) {
+    const size_t per = (size_t)(Fmax > 0 ? Fmax : 1) * 2 * (size_t)nbin * sizeof(float);
+    const size_t fit = (cap_bytes ? cap_bytes : fbank_batch_spec_cap()) / per;
+    return fit < 1 ? 1 : (fit > (size_t)B ? B : (int)fit);
+}
+
+size_t fbank_batch_workspace(const FbankParams& c, int B, long Fmax, size_t cap_bytes) {
+    const int size = (int)(c.sample_rate * c.frame_length_ms * 0.001);
+    int padded = 1;
+    while (padded < size) padded <<= 1;
+    const int nbin = padded / 2 + 1;
+    return (size_t)fbank_batch_chunk(B, Fmax, nbin, cap_bytes) * (size_t)Fmax * 2 * nbin * sizeof(float);
+}
+
+// pcm: (B, row_stride) with row b's samples from pcm + b * row_stride (16-byte aligned, row_stride a multiple of 4, at least
+// size + (Fmax - 1) * shift); frames: device [B], the utterance's own frame count F_b <= Fmax.  out: (B, Fmax, ldo), columns [0, nmel):
+// rows [0, F_b) the log-mels with the CMVN over those F_b rows, rows [F_b, Fmax) zeros — written by the CMVN kernel, the last one to
+// touch them, whatever the samples behind the utterance held.  A frame's arithmetic is launch_fbank's: the same operand, the same K
+// order in the GEMM, the same band sums, the same reduction order over an utterance's own rows.
+hipError_t launch_fbank_batch(const FbankParams& c, const float* pcm, long row_stride, const int* frames, int B, long Fmax, float* out,
+                              int ldo, float* spec, size_t spec_bytes, size_t cap_bytes, hipStream_t st) {
+    const int size = (int)(c.sample_rate * c.frame_length_ms * 0.001), shift = (int)(c.sample_rate * c.frame_shift_ms * 0.001);
+    if (B <= 0 || Fmax <= 0) return hipSuccess;
+    if (size <= 0 || shift <= 0 || (size & 3) || (shift & 3) || c.num_mel_bins <= 0 || c.delta_order != 0 || !c.use_cmvn || c.window < 0 ||
+        c.window > 1 || (((uintptr_t)pcm) & 15) || (row_stride & 3) || row_stride < size + (Fmax - 1) * shift || Fmax > 0x7fffffffL ||
+        ldo < c.num_mel_bins)
+        return hipErrorInvalidValue;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    FbankPlan* plan = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        e = plan_for(c, dev, size, shift, &plan);
+        if (e != hipSuccess) return e;
+    }
+    const FbankPlan& pl = *plan;  // (a plan is never rebuilt or freed: the pointer outlives the lock)
+    const int N2 = 2 * pl.nbin;
+    const int chunk = fbank_batch_chunk(B, Fmax, pl.nbin, cap_bytes);
+    if (!spec || spec_bytes < (size_t)chunk * Fmax * N2 * sizeof(float)) return hipErrorInvalidValue;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = B - b0 < chunk ? B - b0 : chunk;
+        GemmParams g{};
+        g.A = pcm + (long)b0 * row_stride;
+        g.lda = shift;  // overlapping rows: frame t of utterance b starts at sample b * row_stride + t * shift
+        g.a_bs = row_stride;
+        g.W = pl.dft;
+        g.M = (int)Fmax;
+        g.N = N2;
+        g.K = size;
+        g.batches = nb;
+        g.out32 = spec;
+        g.ldo = N2;
+        g.o_bs = Fmax * N2;
+        e = launch_gemm(F32, g, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((mel_rows_kernel<POWER, LogFloor>), dim3((unsigned)((long)nb * Fmax)), dim3(128), pl.nbin * sizeof(float), st, spec,
+                           pl.nbin, (int)Fmax, pl.bank.bands, pl.bank.wts, pl.nmel, LogFloor{FLT_EPSILON}, out + (long)b0 * Fmax * ldo,
+                           Fmax * (long)ldo, (long)ldo, nullptr);
+    }
+    launch_cmvn(out, frames, (int)Fmax, pl.nmel, B, ldo, Fmax * (long)ldo, c.cmvn_eps, st);
+    return hipGetLastError();
+}
+
 }  // namespace s3

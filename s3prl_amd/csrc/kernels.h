@@ -658,6 +658,16 @@ struct FbankParams {
 long fbank_num_frames(long n_samples, const FbankParams& c);
 // one utterance: wav (device) -> out (device, frames x ldo), columns [0, num_mel_bins * (delta_order + 1))
 hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* out, int ldo, hipStream_t st);
+// The batch-wide pass (delta_order 0, use_cmvn 1): one overlapping-row GEMM over the batch, one mel_rows launch, one CMVN launch with
+// counts.  pcm: (B, row_stride) device rows, 16-byte aligned, row_stride a multiple of 4; frames: device [B] frame counts; out: (B, Fmax,
+// ldo) with zeros behind an utterance's own frames and every valid row bit-equal to launch_fbank on that utterance alone.  spec: the
+// caller's workspace of fbank_batch_workspace bytes; cap_bytes: the spectrum cap (0: fbank_batch_spec_cap, 128 MiB), above which the
+// batch is walked fbank_batch_chunk whole utterances at a time
+size_t fbank_batch_spec_cap();
+int fbank_batch_chunk(int B, long Fmax, int nbin, size_t cap_bytes);
+size_t fbank_batch_workspace(const FbankParams& c, int B, long Fmax, size_t cap_bytes);
+hipError_t launch_fbank_batch(const FbankParams& c, const float* pcm, long row_stride, const int* frames, int B, long Fmax, float* out,
+                              int ldo, float* spec, size_t spec_bytes, size_t cap_bytes, hipStream_t st);
 
 // ---- logmel.hip (OnlinePreprocessor: decibel scale, centred hann STFT on the padded batch, HTK mel, log, CMVN) --------
 long logmel_num_frames(long max_len);               // 1 + max_len / 160

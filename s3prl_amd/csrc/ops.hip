@@ -994,6 +994,52 @@ int s3enc_fbank_forward_ex(const s3enc_fbank_config* cfg, int32_t window, const 
     return 0;
 }
 
+int s3enc_op_fbank_batch(const s3enc_fbank_config* cfg, int32_t window, const float* pcm, int64_t row_stride, const int64_t* lengths,
+                         int32_t B, int64_t n_max, float* out, int64_t spec_cap_bytes, int32_t device, void* stream) {
+    if (!cfg || !pcm || !lengths || !out) return fail("s3enc_op_fbank_batch: null argument");
+    if (B <= 0) return fail("s3enc_op_fbank_batch: empty batch");
+    if (window < 0 || window > 1) return fail("s3enc_op_fbank_batch: window must be 0 (povey) or 1 (hamming)");
+    FbankParams f = fbank_params(cfg);
+    f.window = window;
+    if (f.delta_order != 0) return fail("s3enc_op_fbank_batch: the batch-wide pass has no deltas (delta_order must be 0)");
+    if (!f.use_cmvn) return fail("s3enc_op_fbank_batch: the batch-wide pass ends in the CMVN, which writes the rows behind an utterance (use_cmvn must be 1)");
+    if (spec_cap_bytes < 0) return fail("s3enc_op_fbank_batch: spec_cap_bytes must not be negative");
+    if (((uintptr_t)pcm & 15) || (row_stride & 3)) return fail("s3enc_op_fbank_batch: pcm must be 16-byte aligned and row_stride a multiple of 4");
+    long mx = 0;
+    std::vector<int> frames(B);
+    for (int b = 0; b < B; ++b) {
+        const long T = fbank_num_frames(lengths[b], f);
+        if (T <= 0) return fail("s3enc_op_fbank_batch: an utterance is shorter than one analysis window");
+        frames[b] = (int)T;
+        mx = std::max(mx, (long)lengths[b]);
+    }
+    if (n_max > 0) {
+        if (n_max < mx) return fail("s3enc_op_fbank_batch: n_max is smaller than the longest utterance");
+        mx = n_max;
+    }
+    if (mx > row_stride) return fail("s3enc_op_fbank_batch: n_max exceeds row_stride");
+    const long Fmax = fbank_num_frames(mx, f);
+    if (Fmax > 0x7fffffffL / 1024) return fail("s3enc_op_fbank_batch: batch too long");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("s3enc_op_fbank_batch: no HIP device (there is no CPU fallback)");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ws = fbank_batch_workspace(f, B, Fmax, (size_t)spec_cap_bytes);
+    // the workspace and the counts stay with the device between calls (a call that timed its own hipMalloc of 66 MB would measure
+    // the allocator); one call at a time uses them: the lock is held until the stream has drained
+    static std::mutex mu;
+    static std::map<int, std::pair<DevBuf, DevBuf>> scratch;
+    std::lock_guard<std::mutex> lock(mu);
+    DevBuf& spec = scratch[device].first;
+    DevBuf& cnt = scratch[device].second;
+    HIP_TRY(spec.ensure(ws));
+    HIP_TRY(cnt.ensure((size_t)B * sizeof(int)));
+    HIP_TRY(hipMemcpyAsync(cnt.p, frames.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_fbank_batch(f, pcm, row_stride, (const int*)cnt.p, B, Fmax, out, f.num_mel_bins, (float*)spec.p, ws, (size_t)spec_cap_bytes, st));
+    HIP_TRY(hipStreamSynchronize(st));  // `frames` leaves with this scope
+    return 0;
+}
+
 int s3enc_logmel_frame_counts(const int64_t* lengths, int32_t B, int64_t n_max, int32_t* counts) {
     if (!lengths || !counts) return fail("s3enc_logmel_frame_counts: null argument");
     if (B <= 0) return fail("s3enc_logmel_frame_counts: empty batch");

@@ -191,6 +191,9 @@ class HipEncoder:
             if min(self.cfg.conv_lengths(n)[-1] for n in lengths) < 2:
                 raise ValueError(f"an utterance of {min(lengths)} samples has fewer than 2 analysis windows (DeCoAR's front end "
                                  "normalises by the standard deviation over time: one frame has none)")
+        if self.cfg.family == "decoar2" and min(self.cfg.conv_lengths(n)[-1] for n in lengths) < 2:
+            raise ValueError(f"an utterance of {min(lengths)} samples has fewer than 2 analysis windows (DeCoAR 2.0's front end "
+                             "normalises by the standard deviation over time: one frame has none)")
         if self.cfg.family == "mae_ast":
             for i, n in enumerate(lengths):
                 if n < 400:

@@ -44,7 +44,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _lighthubert_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
-    for i, (dim, k, _) in enumerate(cfg.conv_layers):
+    d2 = cfg.family == "decoar2"  # its "conv stack" is the kaldi front end's geometry: no weights, no feature LayerNorm
+    for i, (dim, k, _) in enumerate([] if d2 else cfg.conv_layers):
         p = f"feature_extractor.conv_layers.{i}"
         s[f"{p}.0.weight"] = (dim, cin, k)
         if cfg.conv_bias:
@@ -57,7 +58,7 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
             s[f"{p}.2.bias"] = (dim,)
         cin = dim
     C, D, F, H = cfg.conv_dim, cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.encoder_attention_heads
-    if cfg.feature_layer_norm:
+    if cfg.feature_layer_norm and not d2:
         s["layer_norm.weight"] = (C,)
         s["layer_norm.bias"] = (C,)
     s["post_extract_proj.weight"] = (D, C)
@@ -709,6 +710,14 @@ def named_config(name: str) -> EncoderConfig:
         "tiny_data2vec": dict(family="wav2vec2", **{**tiny, "extractor_mode": "layer_norm", "conv_pos": 15,
                                                    "pos_conv_depth": 3, "normalize": True}),
         "tiny_hubert": dict(family="hubert", **tiny),
+        # DeCoAR 2.0 (upstream/decoar2): HuBERT-base's post-LN encoder behind the kaldi front end; the released shape, which the
+        # reference hard-codes (decoar2/decoar2.py:9-24), and a narrow one
+        "decoar2": dict(family="decoar2", conv_layers=[(80, 400, 160)], conv_bias=False),
+        "tiny_decoar2": dict(family="decoar2", conv_layers=[(80, 400, 160)], conv_bias=False, encoder_layers=2, encoder_embed_dim=128,
+                             encoder_ffn_embed_dim=256, encoder_attention_heads=2, conv_pos=16, conv_pos_groups=4),
+        "tiny_decoar2_d192": dict(family="decoar2", conv_layers=[(80, 400, 160)], conv_bias=False, encoder_layers=2,
+                                  encoder_embed_dim=192, encoder_ffn_embed_dim=384, encoder_attention_heads=3, conv_pos=16,
+                                  conv_pos_groups=4),  # group width 48, the released one
         # LightHuBERT (upstream/lighthubert): the subnets its three released checkpoints run.  The reference hard-codes the 768-wide
         # 12-layer supernet and the subnet shapes, so there is no tiny variant: synth_weights draws the supernet at its real width
         "lighthubert_base": dict(family="lighthubert", lh_model="hubert_pruner", lh_supernet="base", extractor_mode="layer_norm",
