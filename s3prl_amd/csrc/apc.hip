@@ -132,21 +132,7 @@ static int apc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const 
     int I = F;
     for (int l = 0; l < NL; ++l) {
         const int si = l < 2 ? l : (l == NL - 1 ? 2 : -1);  // the hooks: inputs of rnn_layers[1] and [2], the model's output
-        GemmParams g{};
-        g.A = xin;
-        g.lda = I;
-        g.W = w.w_ih[l].p;
-        g.bias = (const float*)w.b_pre[l].p;
-        g.M = (int)M;
-        g.N = 3 * H;
-        g.K = I;
-        g.batches = 1;
-        g.out32 = pre;
-        g.ldo = 3L * H;
-        {
-            Prof pr(e, st, "gemm:apc_in", 2.0 * M * 3 * H * I, 4.0 * ((double)M * I + 3.0 * H * I + (double)M * 3 * H));
-            HIP_TRY(launch_gemm(F32, g, st));
-        }
+        HIP_TRY(linear_f32(e, st, {"gemm:apc_in", xin, w.w_ih[l].p, w.b_pre[l].p, M, 3 * H, I, 0, nullptr, pre}));
         float* hout = sink.slot32(si) ? sink.slot32(si) : hb[l];
         RnnLenParams r{};
         r.cell = 1;

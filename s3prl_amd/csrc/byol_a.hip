@@ -208,23 +208,8 @@ int byol_a_net_run(s3enc_encoder* e, const ByolAW& w, int D, const float* img, l
 
     // ---- fc.0 + ReLU, fc.3 (its ReLU is the tail kernel's) ----
     for (int i = 0; i < 2; ++i) {
-        const long K = i == 0 ? 512 : D;
-        GemmParams g{};
-        g.A = i == 0 ? act[2] : fcb[0];
-        g.lda = K;
-        g.W = w.fw[i].p;
-        g.bias = (const float*)w.fb[i].p;
-        g.M = (int)rows;
-        g.N = D;
-        g.K = (int)K;
-        g.batches = 1;
-        g.out32 = fcb[i];
-        g.ldo = D;
-        {
-            const std::string kind = "gemm:byol_a_fc" + std::to_string(i);
-            Prof pr(e, st, kind.c_str(), 2.0 * rows * D * K, 4.0 * ((double)rows * K + (double)D * K + (double)rows * D));
-            HIP_TRY(launch_gemm(F32, g, st));
-        }
+        const std::string kind = "gemm:byol_a_fc" + std::to_string(i);
+        HIP_TRY(linear_f32(e, st, {kind.c_str(), i == 0 ? act[2] : fcb[0], w.fw[i].p, w.fb[i].p, rows, D, i == 0 ? 512 : D, 0, nullptr, fcb[i]}));
         if (i == 0) {
             Prof pr(e, st, "relu", 0, 8.0 * rows * D);
             HIP_TRY(launch_relu(fcb[0], rows * D, st));

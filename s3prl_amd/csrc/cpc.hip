@@ -388,21 +388,7 @@ static int cpc_forward(s3enc_handle e, const float* const* wav_ptrs_host, const 
     const float* xin = state0;
     for (int l = 0; l < NL; ++l) {
         const bool last = l == NL - 1;
-        GemmParams g{};
-        g.A = xin;
-        g.lda = H;
-        g.W = w.w_ih[l].p;
-        g.bias = (const float*)w.b_pre[l].p;
-        g.M = (int)M;
-        g.N = G * H;
-        g.K = H;
-        g.batches = 1;
-        g.out32 = pre;
-        g.ldo = (long)G * H;
-        {
-            Prof pr(e, st, "gemm:cpc_ar_in", 2.0 * M * G * H * H, 4.0 * ((double)M * H + (double)G * H * H + (double)M * G * H));
-            HIP_TRY(launch_gemm(F32, g, st));
-        }
+        HIP_TRY(linear_f32(e, st, {"gemm:cpc_ar_in", xin, w.w_ih[l].p, w.b_pre[l].p, M, G * H, H, 0, nullptr, pre}));
         float* hout = (last && sink.slot32(1)) ? sink.slot32(1) : ((l & 1) ? hB : hA);
         RnnParams r{};
         r.cell = x.ar_mode;

@@ -167,21 +167,7 @@ static int decoar_forward(s3enc_handle e, const float* const* wav_ptrs_host, con
     }
 
     // ---- post_extract_proj on every sub-th frame ----
-    {
-        GemmParams g{};
-        g.A = feat;
-        g.lda = (long)sub * F;
-        g.W = w.proj_w.p;
-        g.bias = (const float*)w.proj_b.p;
-        g.M = (int)M;
-        g.N = H;
-        g.K = F;
-        g.batches = 1;
-        g.out32 = xp;
-        g.ldo = H;
-        Prof pr(e, st, "gemm:decoar_proj", 2.0 * M * H * F, 4.0 * ((double)M * F + (double)H * F + (double)M * H));
-        HIP_TRY(launch_gemm(F32, g, st));
-    }
+    HIP_TRY(linear_f32(e, st, {"gemm:decoar_proj", feat, w.proj_w.p, w.proj_b.p, M, H, F, 0, nullptr, xp, nullptr, (long)sub * F}));
 
     // ---- the two LSTM stacks on packed sequences ----
     const int max_len = *std::max_element(frames.begin(), frames.end());
@@ -189,19 +175,11 @@ static int decoar_forward(s3enc_handle e, const float* const* wav_ptrs_host, con
     for (int l = 0; l < NL; ++l) {
         const int si = x.per_layer_states ? l : (l == NL - 1 ? 0 : -1);
         for (int d = 0; d < (l == 0 ? 1 : 2); ++d) {
-            GemmParams g{};
-            g.A = l == 0 ? xp : yin + (long)d * H;
-            g.lda = l == 0 ? H : 2L * H;
-            g.W = l == 0 ? w.w_ih0.p : w.w_ih[d][l].p;
-            g.bias = (const float*)(l == 0 ? w.b_pre0.p : w.b_pre[d][l].p);
-            g.M = (int)M;
-            g.N = l == 0 ? 8 * H : 4 * H;
-            g.K = H;
-            g.batches = 1;
-            g.out32 = pre + (long)d * 4 * H;
-            g.ldo = 8L * H;
-            Prof pr(e, st, "gemm:decoar_in", 2.0 * M * g.N * H, 4.0 * ((double)M * H + (double)g.N * H + (double)M * g.N));
-            HIP_TRY(launch_gemm(F32, g, st));
+            if (l == 0)  // both directions read the same rows: one (8 H, H) operand
+                HIP_TRY(linear_f32(e, st, {"gemm:decoar_in", xp, w.w_ih0.p, w.b_pre0.p, M, 8 * H, H, 0, nullptr, pre}));
+            else
+                HIP_TRY(linear_f32(e, st, {"gemm:decoar_in", yin + (long)d * H, w.w_ih[d][l].p, w.b_pre[d][l].p, M, 4 * H, H, 0, nullptr,
+                                           pre + (long)d * 4 * H, nullptr, 2L * H, 8L * H}));
         }
         float* yout = sink.slot32(si) ? sink.slot32(si) : yb[l & 1];
         s3::RnnbParams r{};

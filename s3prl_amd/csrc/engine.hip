@@ -397,23 +397,6 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
     const std::string enc0 = multires ? "encoders.0" : "encoder";  // only the first block keeps its positional conv
     std::vector<float> t, t2;
 
-    // a GEMM weight in the handle's operand format; S3ENC_F16X2: + the MX-fp4 image of its lo term for the weights gemm16.hip's MXW K
-    // step pays for (gemm16_mx_weight_rule: decided per weight, never per batch; wsplit_of finds the image by the weight's pointer).
-    // Only the kinds the tuning key gemm16_mx names AT CREATE TIME get an image (default 14: conv1's would never be read, and with
-    // gemm16_mx = 0 none would — seconds of host packing and the device bytes on a large model): the mask can be narrowed after
-    // s3enc_create, widening it needs a new handle.
-#define UPW(buf, vec, N_, K_, KIND)                                   \
-    do {                                                              \
-        UP(upload_gemm_w(buf, vec, N_, K_, e->dtype, e->x2));         \
-        if (e->x2 && (tuning().gemm16_mx & ((KIND) | 16)) &&          \
-            (gemm16_mx_weight_rule(N_, K_) || ((tuning().gemm16_mx & 16) && !((K_) & 127) && (N_) >= 128))) { \
-            std::unique_ptr<MxImage> img(new MxImage());              \
-            UP(upload_mx4_lo(*img, vec, N_, K_));                     \
-            img->kind = KIND;                                         \
-            e->mx_images[(buf).p] = std::move(img);                   \
-        }                                                             \
-    } while (0)
-
     // ---- conv feature extractor ----
     // (round 5: layer-norm extractors too — their conv outputs are LayerNorm'd + GELU'd, which renormalises the scale but not the
     // relative rounding noise: six stacked fp16 roundings are 6.0e-4 on HuBERT-large and, amplified by the bias-sharpened
@@ -444,7 +427,7 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
             if (e->x2_conv_f32_from && i >= e->x2_conv_f32_from) {
                 UP(upload_gemm_w(e->conv[i].w, t2, C, (long)k * cin, e->dtype, e->x2));  // (read only if the three-term path declines)
             } else {
-                UPW(e->conv[i].w, t2, C, (long)k * cin, 1);
+                UP(upload_gemm_w_mx(e.get(), e->conv[i].w, t2, C, (long)k * cin, 1));
             }
             if (e->x3 || (e->x2_conv_f32_from && i >= e->x2_conv_f32_from)) UP(upload_x3(e->conv[i].w3, t2, C, (long)k * cin));
             if (f22) UP(upload_f32(e->conv[i].wp, wp));
@@ -566,53 +549,7 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
     // of the weight to the operand type either way.  The exact-fp32 and split-precision handles keep the power-of-two scale.
     const float qscale = (1.0f / std::sqrt((float)(D / H))) * (e->dtype != F32 ? 1.44269504088896340736f : 1.0f);
     e->x2_attn_f32 = e->x2 && !multires && x3_shape_ok(D, D, D);  // (the U-net keeps 16-bit)
-    // one TransformerSentenceEncoderLayer named `p` (…layers.N); returns non-zero after fail()
-    auto load_layer = [&](const std::string& p, LayerW& L) -> int {
-        std::vector<float> w(3L * D * D), bb(3L * D);
-        const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-        for (int s = 0; s < 3; ++s) {
-            GET(p + ".self_attn." + names[s] + ".weight", (long)D * D, t);
-            GET(p + ".self_attn." + names[s] + ".bias", D, t2);
-            const float sc = s == 0 ? qscale : 1.f;  // q *= head_dim^-0.5 folded into W_q, b_q
-            for (long i = 0; i < (long)D * D; ++i) w[(long)s * D * D + i] = t[i] * sc;
-            for (int i = 0; i < D; ++i) bb[(long)s * D + i] = t2[i] * sc;
-        }
-        UPW(L.wqkv, w, 3L * D, D, 2);
-        if (e->x3) UP(upload_x3(L.wqkv3, w, 3L * D, D));
-        UP(upload_f32(L.bqkv, bb));
-        GET(p + ".self_attn.out_proj.weight", (long)D * D, t);
-        UP(upload_gemm_w(L.wo, t, D, D, e->dtype, e->x2));
-        if (e->x3 || e->x2_attn_f32) UP(upload_x3(L.wo3, t, D, D));
-        GET(p + ".self_attn.out_proj.bias", D, t);
-        UP(upload_f32(L.bo, t));
-        GET(p + ".self_attn_layer_norm.weight", D, t);
-        UP(upload_f32(L.ln1g, t));
-        GET(p + ".self_attn_layer_norm.bias", D, t);
-        UP(upload_f32(L.ln1b, t));
-        GET(p + ".fc1.weight", (long)F * D, t);
-        UPW(L.w1, t, F, D, 4);
-        if (e->x3) UP(upload_x3(L.w13, t, F, D));
-        GET(p + ".fc1.bias", F, t);
-        UP(upload_f32(L.b1, t));
-        GET(p + ".fc2.weight", (long)D * F, t);
-        UPW(L.w2, t, D, F, 8);
-        if (e->x3) UP(upload_x3(L.w23, t, D, F));
-        GET(p + ".fc2.bias", D, t);
-        UP(upload_f32(L.b2, t));
-        GET(p + ".final_layer_norm.weight", D, t);
-        UP(upload_f32(L.ln2g, t));
-        GET(p + ".final_layer_norm.bias", D, t);
-        UP(upload_f32(L.ln2b, t));
-        if (c.rel_pos && c.gru_rel_pos) {
-            GET(p + ".self_attn.grep_linear.weight", 8 * 64, t);
-            UP(upload_f32(L.grep_w, t));
-            GET(p + ".self_attn.grep_linear.bias", 8, t);
-            UP(upload_f32(L.grep_b, t));
-            GET(p + ".self_attn.grep_a", H, t);
-            UP(upload_f32(L.grep_a, t));
-        }
-        return 0;
-    };
+    auto load = [&](const std::string& p, LayerW& L) { return load_layer(e.get(), ck, p, kFairseqLayer, qscale, c.rel_pos && c.gru_rel_pos, L); };
     // one ConformerEncoderLayer (wav2vec2_model.py:440-578) named `p`; returns non-zero after fail()
     auto load_conformer = [&](const std::string& p, ConformerLayerW& L) -> int {
         const int K = c.dw_kernel;
@@ -703,7 +640,7 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
     } else if (!multires) {
         e->layers.resize(c.encoder_layers);
         for (int l = 0; l < c.encoder_layers; ++l)
-            if (load_layer("encoder.layers." + std::to_string(l), e->layers[l])) return 1;
+            if (load("encoder.layers." + std::to_string(l) + ".", e->layers[l])) return 1;
     } else {
         // U-net blocks in execution order (hubert_model.py:399-507) and the conv adapters between them
         const int R = c.mr_pairs + 1, NB = 2 * R - 1, k = c.mr_kernel;
@@ -718,7 +655,7 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
             UP(upload_f32(bw.eln_b, t));
             bw.layers.resize(c.mr_layers[bi]);
             for (int l = 0; l < c.mr_layers[bi]; ++l)
-                if (load_layer(bp + ".layers." + std::to_string(l), bw.layers[l])) return 1;
+                if (load(bp + ".layers." + std::to_string(l) + ".", bw.layers[l])) return 1;
         }
         // A conv over all D channels becomes a GEMM whose A rows are k_eff * D contiguous elements of a zero-bordered
         // frame buffer (kernels.h, PadCopyParams):
@@ -802,7 +739,6 @@ static int create_impl(const s3enc_config* cfg, int own, const void* block, cons
         GET("output_layer.2.bias", (long)NH * D, t);
         UP(upload_f32(e->head_b2, t));
     }
-#undef UPW
     return finish_create(std::move(e), out);
 }
 
@@ -918,24 +854,6 @@ int conformer_tail(s3enc_handle e, hipStream_t st, Sink& sink, int B, long T, co
     float *xT = (float*)w.xT, *qkv = (float*)w.qkv, *attn = (float*)w.attn, *tmp1 = (float*)w.tmp1, *tmp2 = (float*)w.tmp2;
     float *hbuf = (float*)w.hbuf, *cbuf = (float*)w.cbuf, *pbuf = (float*)w.pbuf;
     auto other = [&](const float* busy) { return busy == (const float*)w.x32 ? (float*)w.xpc : (float*)w.x32; };
-    auto gemm = [&](const char* kind, const float* A, const DevBuf& W, const DevBuf* bias, int M_, int N, int K, int act,
-                    const float* res, float* out, long ldo) -> hipError_t {
-        GemmParams g{};
-        g.A = A;
-        g.lda = K;
-        g.W = W.p;
-        g.bias = bias ? (const float*)bias->p : nullptr;
-        g.M = M_;
-        g.N = N;
-        g.K = K;
-        g.batches = 1;
-        g.act = act;
-        g.residual = res;
-        g.out32 = out;
-        g.ldo = ldo;
-        Prof pr(e, st, kind, 2.0 * M_ * N * K, ((double)M_ * K + (double)N * K + (double)M_ * N * (res ? 2 : 1)) * 4);
-        return launch_gemm(F32, g, st);
-    };
     auto ln = [&](const char* kind, const float* x, const DevBuf& g, const DevBuf& b, float* y, const LnAcc& fa) -> hipError_t {
         Prof pr(e, st, kind, 0, gM * D * 8);
         return launch_layernorm(F32, x, (const float*)g.p, (const float*)b.p, M, D, 0, y, nullptr, st, fa);
@@ -956,13 +874,13 @@ int conformer_tail(s3enc_handle e, hipStream_t st, Sink& sink, int B, long T, co
         if (dbg_stop == 40 + l) return 0;
         // x + 0.5 FFN1(x): swish in fc1's epilogue, the 0.5 in w_2 / b_2, the residual in fc2's epilogue
         HIP_TRY(ln("layernorm:ffn", x_cur, L.f1_lng, L.f1_lnb, xT, LnAcc()));
-        HIP_TRY(gemm("gemm:ffn_w1", xT, L.f1_w1, &L.f1_b1, (int)M, F, D, 3, nullptr, hbuf, F));
-        HIP_TRY(gemm("gemm:ffn_w2", hbuf, L.f1_w2, &L.f1_b2, (int)M, D, F, 0, x_cur, tmp1, D));
+        HIP_TRY(linear_f32(e, st, {"gemm:ffn_w1", xT, L.f1_w1.p, L.f1_b1.p, M, F, D, 3, nullptr, hbuf}));
+        HIP_TRY(linear_f32(e, st, {"gemm:ffn_w2", hbuf, L.f1_w2.p, L.f1_b2.p, M, D, F, 0, x_cur, tmp1}));
         if (l == 0) e->taps["ffn1_0"] = {tmp1, M * D, F32};
         // x + MHA(LN(x))
         HIP_TRY(ln("layernorm:attn", tmp1, L.at_lng, L.at_lnb, xT, LnAcc()));
         if (relpos) {
-            HIP_TRY(gemm("gemm:qkv", xT, L.wqkv, &L.bqkv, (int)M, 3 * D, D, 0, nullptr, qkv, 3L * D));
+            HIP_TRY(linear_f32(e, st, {"gemm:qkv", xT, L.wqkv.p, L.bqkv.p, M, 3 * D, D, 0, nullptr, qkv}));
             // P = linear_pos(pe) for this T: the centre 2T - 1 rows of the table (depends on T and the layer only)
             GemmParams g{};
             g.A = (const float*)e->pe_tab.p + (long)(e->pe_T - T) * D;
@@ -982,7 +900,7 @@ int conformer_tail(s3enc_handle e, hipStream_t st, Sink& sink, int B, long T, co
                 Prof pr(e, st, "rope", 0, gM * D * 8);
                 HIP_TRY(launch_rope(xT, (const float*)e->rope_tab.p, M, (int)T, D, tmp2, st));
             }
-            HIP_TRY(gemm("gemm:qk", tmp2, L.wqkv, &L.bqkv, (int)M, 2 * D, D, 0, nullptr, qkv, 3L * D));
+            HIP_TRY(linear_f32(e, st, {"gemm:qk", tmp2, L.wqkv.p, L.bqkv.p, M, 2 * D, D, 0, nullptr, qkv, nullptr, 0, 3L * D}));
             GemmParams g{};
             g.A = xT;
             g.lda = D;
@@ -1011,10 +929,10 @@ int conformer_tail(s3enc_handle e, hipStream_t st, Sink& sink, int B, long T, co
             HIP_TRY(launch_attention(F32, a, st));
         }
         if (l == 0) e->taps["attn0"] = {attn, M * D, F32};
-        HIP_TRY(gemm("gemm:out_proj", attn, L.wo, &L.bo, (int)M, D, D, 0, tmp1, tmp2, D));
+        HIP_TRY(linear_f32(e, st, {"gemm:out_proj", attn, L.wo.p, L.bo.p, M, D, D, 0, tmp1, tmp2}));
         // x + Conv(x): LN -> pointwise_conv1 -> [GLU, depthwise conv, BatchNorm, swish] -> pointwise_conv2 + residual
         HIP_TRY(ln("layernorm:conv", tmp2, L.cv_lng, L.cv_lnb, xT, LnAcc()));
-        HIP_TRY(gemm("gemm:pw1", xT, L.pw1, nullptr, (int)M, 2 * D, D, 0, nullptr, cbuf, 2L * D));
+        HIP_TRY(linear_f32(e, st, {"gemm:pw1", xT, L.pw1.p, nullptr, M, 2 * D, D, 0, nullptr, cbuf}));
         {
             ConformerConvParams p{};
             p.x = cbuf;
@@ -1029,11 +947,11 @@ int conformer_tail(s3enc_handle e, hipStream_t st, Sink& sink, int B, long T, co
             HIP_TRY(launch_conformer_conv(p, st));
         }
         if (l == 0) e->taps["conv0_mod"] = {attn, M * D, F32};
-        HIP_TRY(gemm("gemm:pw2", attn, L.pw2, nullptr, (int)M, D, D, 0, tmp2, tmp1, D));
+        HIP_TRY(linear_f32(e, st, {"gemm:pw2", attn, L.pw2.p, nullptr, M, D, D, 0, tmp2, tmp1}));
         // x + 0.5 FFN2(x), then final_layer_norm: the next layer's input (a state, except behind a pre-LN stack's last layer)
         HIP_TRY(ln("layernorm:ffn", tmp1, L.f2_lng, L.f2_lnb, xT, LnAcc()));
-        HIP_TRY(gemm("gemm:ffn_w1", xT, L.f2_w1, &L.f2_b1, (int)M, F, D, 3, nullptr, hbuf, F));
-        HIP_TRY(gemm("gemm:ffn_w2", hbuf, L.f2_w2, &L.f2_b2, (int)M, D, F, 0, tmp1, tmp2, D));
+        HIP_TRY(linear_f32(e, st, {"gemm:ffn_w1", xT, L.f2_w1.p, L.f2_b1.p, M, F, D, 3, nullptr, hbuf}));
+        HIP_TRY(linear_f32(e, st, {"gemm:ffn_w2", hbuf, L.f2_w2.p, L.f2_b2.p, M, D, F, 0, tmp1, tmp2}));
         if (l == 0) e->taps["ffn2_0"] = {tmp2, M * D, F32};
         const int si_next = (l + 1 < NL || !prel) ? l + 1 : -1;
         float* x_next = sink.slot32(si_next) ? sink.slot32(si_next) : other(x_cur);
@@ -1577,201 +1495,53 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
 
     const double gM = (double)M;
     int si_cur = si_hidden(0);  // state index of x_cur (pre-LN featurize: its term is added by the LayerNorm that reads it)
-    for (int l = 0; l < NL; ++l) {
-        LayerW& Lw = e->layers[l];
+    LayerRun run{B, T, d_valid, prel};
+    run.xT = xT;
+    run.qkv = qkv;
+    run.attn = attn;
+    run.hbuf = hbuf;
+    run.tmp1 = (float*)tmp1;
+    run.tmp2 = (float*)tmp2;
+    run.lnst = (float2*)lnst;
+    run.bias_table = d_table;
+    run.table_R = e->rel_R;
+    run.gate = gated ? (const float*)gate : nullptr;
+    run.allow_ln1_fold = !ffn_tap && tuning().ln1_fold;
+    run.ln1_inplace = tuning().ws_inplace;
+    int l = 0;
+    if (ffn_tap)  // "fairseq_layers_before_residual": state l is fc2(x) + bias, final behind the GEMM that exports it
+        run.ffn_exported = [&]() -> int {
+            HIP_TRY(sink.emit(l, run.ffn_out32, false));
+            HIP_TRY(sink.done(l));
+            return 0;
+        };
+    for (; l < NL; ++l) {
         if (dbg_stop == 40 + l) return 0;  // (before layer l)
-        const bool lastl = l == NL - 1;
-        const void* a_in;       // operand of the q|k|v GEMM
-        const float* gate_src;  // WavLM: the attention module's input
-        if (prel) {
-            Prof pr(e, st, "layernorm:ln1", 0, gM * D * (4 + es));
-            // WavLM: the gate reads LN1's output — computed inside this pass (no fp32 copy, no separate kernel)
-            HIP_TRY(launch_layernorm(dt, x_cur, (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, M, D, 0,
-                                     dt == F32 ? (float*)xT : nullptr, dt == F32 ? nullptr : xT, st, sink.acc(si_cur, 1),
-                                     gate_of(l)));
-            a_in = xT;
-            gate_src = nullptr;
-        } else {
-            a_in = dt == F32 ? (const void*)x_cur : (const void*)a16_cur;
-            gate_src = x_cur;
-        }
-        (void)gate_src;  // the gate of this layer was written by the LayerNorm that produced its attention input
-        {
-            GemmParams g{};
-            g.A = a_in;
-            g.lda = D;
-            g.W = Lw.wqkv.p;
-            g.W_x3 = Lw.wqkv3.p;
-            g.bias = (const float*)Lw.bqkv.p;
-            g.M = (int)M;
-            g.N = 3 * D;
-            g.K = D;
-            g.batches = 1;
-            g.ldo = 3 * D;
-            if (dt == F32) g.out32 = (float*)qkv; else g.out16 = qkv;
-            Prof pr(e, st, "gemm:qkv", 2.0 * gM * 3 * D * D, (gM * D + 3.0 * D * D + gM * 3 * D) * es);
-            HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-            if (l == 0) e->taps["qkv0"] = {qkv, M * 3 * D, dt};
-            if (dbg_stop == 30 && l == 0) return 0;
-        }
-        {
-            AttnParams a{};
-            a.qkv = qkv;
-            a.out = attn;
-            a.valid = d_valid;
-            a.B = B;
-            a.T = (int)T;
-            a.H = H;
-            a.bias_table = d_table;
-            a.table_R = e->rel_R;
-            a.gate = gated ? (const float*)gate : nullptr;
-            a.out_f32 = e->x2_attn_f32 ? 1 : 0;
-            Prof pr(e, st, "attention", 4.0 * B * H * (double)T * T * 64, gM * 4 * D * es);
-            HIP_TRY(launch_attention(e->x3 ? 3 : dt, a, st));
-            if (l == 0) e->taps["attn0"] = {attn, M * D, e->x2_attn_f32 ? (int)F32 : dt};
-            if (dbg_stop == 31 && l == 0) return 0;
-        }
-        {   // out_proj + bias + residual
-            GemmParams g{};
-            g.A = attn;
-            g.lda = D;
-            g.W = Lw.wo.p;
-            g.W_x3 = Lw.wo3.p;
-            g.bias = (const float*)Lw.bo.p;
-            g.M = (int)M;
-            g.N = D;
-            g.K = D;
-            g.batches = 1;
-            g.ldo = D;
-            g.residual = x_cur;
-            g.out32 = (float*)tmp1;
-            Prof pr(e, st, "gemm:out_proj", 2.0 * gM * D * D, (gM * D + (double)D * D) * es + gM * D * 8);
-            if (e->x2_attn_f32) {
-                if (!gemm_x3_eligible(g)) return fail("out_proj is not a shape of the three-term GEMM (internal)");
-                HIP_TRY(launch_gemm(F32, g, st));
-            } else {
-                HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-            }
-        }
-        const float* ffn_res;
-        const void* ffn_in;
-        if (dbg_stop == 32 && l == 0) return 0;  // (behind out_proj)
-        // round 6 (second session): in the 16-bit modes a post-LN layer's LayerNorm 1 need not write its fp32 output — that tensor is only
-        // fc2's residual, and fc2's epilogue can rebuild it from the row it reads anyway and two numbers per row (GemmParams::res_ln_*;
-        // -49 MB of stores per layer at the reference batch).  Decided from fc2's shape class (gemm16_res_ln_ok), never from M
-        bool ln1_fold = false;
-        if (!prel && dt != F32 && !ffn_tap && tuning().ln1_fold) {
-            GemmParams q{};
-            q.A = hbuf;
-            q.lda = F;
-            q.W = Lw.w2.p;
-            q.W_x3 = Lw.w23.p;
-            q.bias = (const float*)Lw.b2.p;
-            q.M = (int)M;
-            q.N = D;
-            q.K = F;
-            q.batches = 1;
-            q.ldo = D;
-            q.residual = (const float*)tmp1;
-            q.out32 = (float*)tmp1;
-            ln1_fold = gemm16_res_ln_ok(dt, wsplit_of(e, q));
-        }
-        if (prel) {  // b = LN2(y) feeds fc1; residual is y itself
-            Prof pr(e, st, "layernorm:ln2", 0, gM * D * (4 + es));
-            HIP_TRY(launch_layernorm(dt, (const float*)tmp1, (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, M, D, 0,
-                                     dt == F32 ? (float*)xT : nullptr, dt == F32 ? nullptr : xT, st));
-            ffn_res = (const float*)tmp1;
-            ffn_in = xT;
-        } else if (ln1_fold) {  // 16-bit modes: LN1 writes the fc1 operand and the rows' (mean, rstd); fc2's epilogue rebuilds x1 = LN1(y)
-            Prof pr(e, st, "layernorm:ln1", 0, gM * D * (4 + es));
-            HIP_TRY(launch_layernorm(dt, (const float*)tmp1, (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, M, D, 0,
-                                     nullptr, xT, st, LnAcc(), LnGate(), (float2*)lnst));
-            ffn_res = (const float*)tmp1;  // (y itself: fc2 normalises the rows it adds, then overwrites them in place)
-            ffn_in = xT;
-        } else {  // x1 = LN1(y): both the fc1 operand and the FFN residual
-            Prof pr(e, st, "layernorm:ln1", 0, gM * D * (8 + (dt == F32 ? 0 : es)));
-            // (ws_inplace: LayerNorm 1 overwrites its input — a wave reads its whole row before it writes — and fc2 then adds its
-            //  product onto that buffer in place: every element is read and written by the same lane)
-            float* x1 = tuning().ws_inplace ? (float*)tmp1 : (float*)tmp2;
-            HIP_TRY(launch_layernorm(dt, (const float*)tmp1, (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, M, D, 0,
-                                     x1, dt == F32 ? nullptr : xT, st));
-            ffn_res = (const float*)x1;
-            ffn_in = dt == F32 ? (const void*)x1 : (const void*)xT;
-        }
-        {   // fc1 + bias + GELU
-        if (dbg_stop == 33 && l == 0) return 0;  // (behind LayerNorm 1 / 2)
-            GemmParams g{};
-            g.A = ffn_in;
-            g.lda = D;
-            g.W = Lw.w1.p;
-            g.W_x3 = Lw.w13.p;
-            g.bias = (const float*)Lw.b1.p;
-            g.M = (int)M;
-            g.N = F;
-            g.K = D;
-            g.batches = 1;
-            g.act = 1;
-            g.ldo = F;
-            if (dt == F32) g.out32 = (float*)hbuf; else g.out16 = hbuf;
-            Prof pr(e, st, "gemm:fc1", 2.0 * gM * F * D, (gM * D + (double)F * D + gM * F) * es);
-            HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-        }
-        if (dbg_stop == 34 && l == 0) return 0;  // (behind fc1)
-        // fc2 + bias + residual.  pre-LN: the result IS the residual stream after the layer (a state for l < NL-1, and
-        // for the fairseq_layers / DistilHuBERT selections); post-LN: it feeds final_layer_norm.
+        // pre-LN: fc2's result IS the residual stream after the layer (a state for l < NL-1, and for the fairseq_layers /
+        // DistilHuBERT selections); post-LN: the state is final_layer_norm's output
         const int si_next = si_stream(l);
+        void* s16 = sink.slot16(si_next);
+        run.x = x_cur;
+        run.x16 = a16_cur;
         // (the last pre-LN layer's raw stream goes to tmp2 when it is not a state, which keeps the "proj" debug tap in x32
         // alive through a default forward)
-        float* x_next = sink.slot32(si_next) ? sink.slot32(si_next) : ((prel && lastl) ? (float*)tmp2 : other(x_cur));
-        float* fc2_dst = prel ? x_next : (float*)tmp1;
-        {
-            GemmParams g{};
-            g.A = hbuf;
-            g.lda = F;
-            g.W = Lw.w2.p;
-            g.W_x3 = Lw.w23.p;
-            g.bias = (const float*)Lw.b2.p;
-            g.M = (int)M;
-            g.N = D;
-            g.K = F;
-            g.batches = 1;
-            g.ldo = D;
-            if (ffn_tap) {
-                // "fairseq_layers_before_residual": the GEMM exports fc2(x) + bias, the residual is re-applied by an
-                // elementwise add in the same order as the fused epilogue (bit-identical stream)
-                float* f_out = sink.slot32(l) ? sink.slot32(l) : (float*)ffnbuf;
-                g.out32 = f_out;
-                g.out16 = sink.slot16(l);
-                {
-                    Prof pr(e, st, "gemm:fc2", 2.0 * gM * D * F, (gM * F + (double)D * F) * es + gM * D * 4);
-                    HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-                }
-                HIP_TRY(sink.emit(l, f_out, false));
-                HIP_TRY(sink.done(l));
-                Prof pr(e, st, "residual_add", 0, gM * D * 12);
-                HIP_TRY(launch_add(f_out, ffn_res, fc2_dst, M * D, st));
-            } else {
-                g.residual = ffn_res;
-                g.out32 = fc2_dst;
-                g.out16 = prel ? sink.slot16(si_next) : nullptr;
-                if (ln1_fold) {
-                    g.res_ln_stats = (const float2*)lnst;
-                    g.res_ln_g = (const float*)Lw.ln1g.p;
-                    g.res_ln_b = (const float*)Lw.ln1b.p;
-                }
-                Prof pr(e, st, "gemm:fc2", 2.0 * gM * D * F, (gM * F + (double)D * F) * es + gM * D * 8);
-                HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-            }
+        run.x_next = sink.slot32(si_next) ? sink.slot32(si_next) : ((prel && l == NL - 1) ? (float*)tmp2 : other(x_cur));
+        run.x16_next = (prel || dt == F32 || s16) ? s16 : xT;
+        // the WavLM gate of a layer's attention is computed by the LayerNorm that produces that attention's input
+        run.gate_here = gate_of(l);
+        run.gate_next = gate_of(l + 1);
+        run.acc_in = prel ? sink.acc(si_cur, 1) : LnAcc();
+        run.acc_out = prel ? LnAcc() : sink.acc(si_next, 2);
+        if (ffn_tap) {
+            run.ffn_out32 = sink.slot32(l) ? sink.slot32(l) : (float*)ffnbuf;
+            run.ffn_out16 = sink.slot16(l);
         }
-        if (!prel) {
-            void* h16 = dt == F32 ? nullptr : (sink.slot16(si_next) ? sink.slot16(si_next) : xT);
-            Prof pr(e, st, "layernorm:ln2", 0, gM * D * (8 + (dt == F32 ? 0 : es)));
-            HIP_TRY(launch_layernorm(dt, (const float*)tmp1, (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, M, D, 0, x_next,
-                                     h16, st, sink.acc(si_next, 2), gate_of(l + 1)));
-            a16_cur = h16;
-        }
+        run.taps = l == 0;
+        run.stop_after = l == 0 ? dbg_stop : 0;
+        if (const int rc = encoder_layer(e, st, e->layers[l], run)) return rc == LAYER_STOPPED ? 0 : 1;
         HIP_TRY(sink.done(si_next));
-        x_cur = x_next;
+        if (!prel) a16_cur = run.x16_next;
+        x_cur = run.x_next;
         si_cur = si_next;
     }
     const float* enc_out = x_cur;  // what the DistilHuBERT heads read
@@ -1793,42 +1563,22 @@ int forward_body(s3enc_handle e, const float* const* wav_ptrs_host, const int64_
         // DistilHuBERT prediction heads (distiller/model.py:155-161,245-258): Linear(D, NH*D) + GELU, then per head k
         // the (D x D) slice of SplitLinear on columns [k*D, (k+1)*D) of the intermediate
         {
-            GemmParams g{};
-            g.A = dt == F32 ? (const void*)enc_out : enc_out16;
-            g.lda = D;
-            g.W = e->head_w1.p;
-            g.W_x3 = e->head_w13.p;
-            g.bias = (const float*)e->head_b1.p;
-            g.M = (int)M;
-            g.N = NH * D;
-            g.K = D;
-            g.batches = 1;
-            g.act = 1;
-            g.ldo = (long)NH * D;
-            if (dt == F32) g.out32 = (float*)hbuf; else g.out16 = hbuf;
-            Prof pr(e, st, "gemm:head1", 2.0 * gM * NH * D * D, (gM * D + (double)NH * D * D + gM * NH * D) * es);
-            HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
+            Linear q{"gemm:head1", dt == F32 ? (const void*)enc_out : enc_out16, e->head_w1.p, e->head_b1.p, M, NH * D, D, 1};
+            q.W_x3 = e->head_w13.p;
+            if (dt == F32) q.out32 = (float*)hbuf; else q.out16 = hbuf;
+            if (linear(e, st, q)) return 1;
         }
         for (int k = 0; k < NH; ++k) {
             const int si = 1 + NL + k;
             float* dst = sink.slot32(si) ? sink.slot32(si) : (float*)tmp1;
-            GemmParams g{};
-            g.A = (const char*)hbuf + (size_t)k * D * es;
-            g.lda = (long)NH * D;
-            g.W = (const char*)e->head_w2.p + (size_t)k * D * D * es * (e->x2 ? 2 : 1);  // x2: rows are [hi | lo]
-            g.W_x3 = e->head_w23.p ? (const char*)e->head_w23.p + (size_t)k * D * D * 4 : nullptr;
-            g.bias = (const float*)e->head_b2.p + (long)k * D;
-            g.M = (int)M;
-            g.N = D;
-            g.K = D;
-            g.batches = 1;
-            g.ldo = D;
-            g.out32 = dst;
-            g.out16 = sink.slot16(si);
-            {
-                Prof pr(e, st, "gemm:head2", 2.0 * gM * D * D, (gM * D + (double)D * D) * es + gM * D * 4);
-                HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-            }
+            // (x2: W rows are [hi | lo])
+            Linear q{"gemm:head2", (const char*)hbuf + (size_t)k * D * es, (const char*)e->head_w2.p + (size_t)k * D * D * es * (e->x2 ? 2 : 1),
+                     (const float*)e->head_b2.p + (long)k * D, M, D, D};
+            q.W_x3 = e->head_w23.p ? (const char*)e->head_w23.p + (size_t)k * D * D * 4 : nullptr;
+            q.lda = (long)NH * D;
+            q.out32 = dst;
+            q.out16 = sink.slot16(si);
+            if (linear(e, st, q)) return 1;
             HIP_TRY(sink.emit(si, dst, false));
             HIP_TRY(sink.done(si));
         }

@@ -1,9 +1,11 @@
 // engine_internal.h — what the translation units of the engine share: error reporting, device buffers, the weight containers,
 // the checkpoint reader (Ckpt, GET / UP), the handle (struct s3enc_encoder), per-kernel profiling, the plumbing every family's
-// forward starts with (batch checks, the pinned staging ring, Sink: where the states go), the workspace allocator and the
-// multires-HuBERT plan.
+// forward starts with (batch checks, the pinned staging ring, Sink: where the states go), the Linear / layer weights / layer schedule
+// of the Transformer encoders, the workspace allocator and the multires-HuBERT plan.
 //   engine.hip    s3enc_create (weight packing), the single-resolution forward schedule, the handle's C ABI, and the shared
 //                 plumbing's definitions (Ckpt::get, tap_major, load_rnn_layer, batch_n_max, check_out, stage_begin / stage_commit)
+//   transformer.hip  what the Transformer encoders share: the un-batched Linear every dense product goes through (linear_f32 / linear),
+//                 one layer's weights from a checkpoint (load_layer) and one layer's schedule in either LayerNorm order (encoder_layer)
 //   multires.hip  the multires-HuBERT U-net behind post_extract_proj
 //   wav2vec.hip / cpc.hip  the convolutional families (wav2vec, modified CPC); rnn.hip: the LSTM / GRU recurrence
 //   apc.hip / mockingjay.hip  the log-mel families (APC / VQ-APC on GRU layers; Mockingjay / TERA / AudioALBERT on BERT layers)
@@ -11,7 +13,7 @@
 //   npc.hip     NPC: the log-mel front end, ConvBlocks and masked convolutions on convtaps.hip's two-run implicit GEMM
 //   vggish.hip  VGGish: the un-padded log-mel examples, the 3 x 3 conv + pool stack on conv2d.hip, three Linears, the quantiser
 //   byol_a.hip  BYOL-A: per-segment FFT log-mel (melspec.hip), conv + BatchNorm + floor-pool on conv2d.hip, two Linears, max + mean
-//   mae_ast.hip MAE-AST: per-utterance kaldi fbank, the fused patch embedding (patchembed.hip), pre- / post-LN Transformer layers
+//   mae_ast.hip MAE-AST: per-utterance kaldi fbank, the fused patch embedding (patchembed.hip), pre- / post-LN layers of transformer.hip
 //   byol_s.hip  BYOL-S: centred windows -> hann(400) FFT log-mel -> whole-batch statistics -> ResNet on stem.hip + conv2d.hip (or BYOL-A's
 //               network) -> max + mean, the windows in chunks
 //   (a family file holds its configuration check, its weights, its forward schedule and its shape rules, and hands them to the engine
@@ -24,6 +26,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -358,6 +361,8 @@ inline hipError_t upload_posconv_x3(DevBuf& d, const std::vector<float>& w, int 
     return hipMemcpy(d.p, img.data(), img.size() * 2, hipMemcpyHostToDevice);
 }
 
+// One Transformer layer as transformer.hip's load_layer packs it: q|k|v stacked as one (3 D, D) operand with q pre-scaled, the other
+// projections, the LayerNorm affines (ln1: behind the attention, ln2: behind the FFN) and, for WavLM, the gate's tensors
 struct LayerW {
     DevBuf wqkv, bqkv, wo, bo, ln1g, ln1b, w1, b1, w2, b2, ln2g, ln2b;
     DevBuf wqkv3, wo3, w13, w23;  // S3ENC_F32X3: pair-packed bf16 hi / lo images of the four weight matrices
@@ -475,22 +480,19 @@ struct ByolANet {
     float* fcb[2];
 };
 
-// Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table, and per layer (ONE layer with
-// share_layer) q|k|v stacked as one (3 D, D) operand with q pre-scaled by head_dim^-0.5, the other projections and LayerNorm affines
-struct MjLayerW {
-    DevBuf wqkv, bqkv, wo, bo, g1, b1n, w1, b1, w2, b2, g2, b2n;
-};
+// Mockingjay / TERA / AudioALBERT (mockingjay.hip): the input representation, the position table and the BERT layers (ONE layer with
+// share_layer)
 struct MjW {
     DevBuf in_w, in_b, in_g, in_beta, pos;
     int pos_rows = 0;
-    std::vector<MjLayerW> layers;
+    std::vector<LayerW> layers;
 };
 
 // MAE-AST (mae_ast.hip): the patch Linear with the eval BatchNorm folded in (W' = s W, b' = b - s mean rowsum(W)), the leading rows
-// of the checkpoint's own sinusoidal table, encoder.layer_norm (post-LN only) and the layers as Mockingjay's struct holds them
+// of the checkpoint's own sinusoidal table, encoder.layer_norm (post-LN only) and the layers
 struct MaeAstW {
     DevBuf pw, pb, pos, eln_g, eln_b;
-    std::vector<MjLayerW> layers;
+    std::vector<LayerW> layers;
 };
 
 struct ProfRec {
@@ -798,6 +800,75 @@ inline GemmParams wsplit_of(const s3enc_encoder* e, GemmParams g) {
     }
     return g;
 }
+
+// ---- transformer.hip: the Linear, the layer weights and the layer schedule behind every Transformer encoder -------------------------
+// out(M, N) = act(A(M, K) . W(N, K)^T + bias) (+ residual), one batch, under the profile record `kind`: 2 M N K flops and
+// (M K + N K) es_in + M N es_out (+ 4 M N for the residual) bytes
+struct Linear {
+    const char* kind;
+    const void *A, *W;
+    const void* bias;  // fp32 (N), or null
+    long M;
+    int N, K;
+    int act = 0;  // GemmParams::act
+    const float* residual = nullptr;
+    float* out32 = nullptr;
+    void* out16 = nullptr;
+    long lda = 0, ldo = 0;             // row pitches of A and of the output; 0: dense (K, N)
+    const void* W_x3 = nullptr;        // `linear`: the S3ENC_F32X3 image of W, or null
+    const char* x3_or_fail = nullptr;  // S3ENC_F16X2 hybrids: A is fp32 — the three-term GEMM takes the product or the forward fails, naming this
+    const float2* res_ln_stats = nullptr;  // GemmParams::res_ln_*
+    const float *res_ln_g = nullptr, *res_ln_b = nullptr;
+};
+hipError_t linear_f32(s3enc_encoder* e, hipStream_t st, const Linear& l);  // exact fp32 operands, whatever the handle's mode
+// operands in the handle's mode (e->dtype, W_x3, wsplit_of), 16-bit output unless out32 is set; non-zero after fail()
+int linear(s3enc_encoder* e, hipStream_t st, const Linear& l);
+GemmParams linear_params(const s3enc_encoder* e, const Linear& l);  // what `linear` launches (for the eligibility predicates)
+
+// a GEMM weight in the handle's operand format; S3ENC_F16X2: + the MX-fp4 image of its lo term for the weights gemm16.hip's MXW K
+// step pays for (gemm16_mx_weight_rule: decided per weight, never per batch; wsplit_of finds the image by the weight's pointer).
+// Only the kinds the tuning key gemm16_mx names AT CREATE TIME get an image (default 14: conv1's would never be read, and with
+// gemm16_mx = 0 none would — seconds of host packing and the device bytes on a large model): the mask can be narrowed after
+// s3enc_create, widening it needs a new handle.
+hipError_t upload_gemm_w_mx(s3enc_encoder* e, DevBuf& buf, const std::vector<float>& v, long N, long K, int kind);
+// the tensor names of a layer under its prefix: fairseq's TransformerSentenceEncoderLayer, BERT's (Mockingjay)
+struct LayerNames {
+    const char *qkv[3], *out, *ln1, *fc1, *fc2, *ln2;
+};
+extern const LayerNames kFairseqLayer, kBertLayer;
+// the layer named `prefix` (ending in '.') in the handle's operand mode, the q rows and bias times `qscale`; gate: WavLM's grep tensors too
+int load_layer(s3enc_encoder* e, const Ckpt& ck, const std::string& prefix, const LayerNames& n, float qscale, bool gate, LayerW& L);
+
+// One layer of B sequences of T rows, enqueued on `st`.  The caller owns the buffers and decides where states go: the layer sees pointers.
+struct LayerRun {
+    int B;
+    long T;
+    const int* valid;  // [B] keys >= valid[b] are masked
+    bool pre_ln;
+    const float* x;   // the layer's input: the fp32 residual stream
+    const void* x16;  // post-LN 16-bit modes: its 16-bit copy, the q|k|v operand
+    float* x_next;    // the layer's output — pre-LN: fc2's, post-LN: LayerNorm 2's
+    void* x16_next;   // ... and its 16-bit copy (pre-LN: a slab slot or null)
+    void *xT, *qkv, *attn, *hbuf;  // (M, D) LayerNorm output, (M, 3 D), (M, D), (M, F) in the compute dtype (attn: fp32 with x2_attn_f32)
+    float *tmp1, *tmp2;            // (M, D) fp32
+    float2* lnst = nullptr;        // (M) row statistics of LayerNorm 1 (allow_ln1_fold)
+    const float* bias_table = nullptr;  // WavLM: AttnParams::bias_table / table_R / gate
+    int table_R = 0;
+    const float* gate = nullptr;
+    LnGate gate_here, gate_next;  // the gate of this layer's attention (pre-LN: LayerNorm 1 writes it), of the next layer's (post-LN: LayerNorm 2)
+    LnAcc acc_in, acc_out;        // Featurizer terms: of the input (pre-LN, LayerNorm 1 adds it), of the output (post-LN, LayerNorm 2)
+    // the ffn_out selection (ffn_out32 set): fc2 exports fc2(x) + bias here, `ffn_exported` runs behind it (non-zero after fail()),
+    // then an elementwise add re-applies the residual
+    float* ffn_out32 = nullptr;
+    void* ffn_out16 = nullptr;
+    std::function<int()> ffn_exported;
+    bool allow_ln1_fold = false;  // post-LN 16-bit: fc2's epilogue rebuilds LayerNorm 1's output where its shape class can (tuning key ln1_fold)
+    bool ln1_inplace = false;     // post-LN: LayerNorm 1 overwrites tmp1 instead of writing tmp2 (tuning key ws_inplace)
+    bool taps = false;            // keep the debug taps qkv0 / attn0
+    int stop_after = 0;           // S3ENC_DEBUG_STOP 30..34: return LAYER_STOPPED behind q|k|v, attention, out_proj, LayerNorm 1 / 2, fc1
+};
+enum { LAYER_DONE = 0, LAYER_FAILED = 1, LAYER_STOPPED = 2 };
+int encoder_layer(s3enc_encoder* e, hipStream_t st, const LayerW& Lw, const LayerRun& r);
 
 long conv_len(const s3enc_config& c, long n, int upto /*exclusive*/);  // frames after the first `upto` conv layers
 int valid_frames(const s3enc_config& c, long length, long n_max);      // un-masked frames under the family's mask rule

@@ -97,41 +97,8 @@ static int mae_ast_create(s3enc_encoder* e, const Ckpt& ck) {
         UP(upload_f32(w.eln_b, t));
     }
     w.layers.resize(c.encoder_layers);
-    for (int l = 0; l < c.encoder_layers; ++l) {
-        MjLayerW& L = w.layers[l];
-        const std::string n = "encoder.layers." + std::to_string(l) + ".";
-        std::vector<float> qkv((size_t)3 * D * D), bqkv((size_t)3 * D);
-        const char* part[3] = {"q_proj", "k_proj", "v_proj"};
-        for (int k = 0; k < 3; ++k) {
-            GET(n + "self_attn." + part[k] + ".weight", (long)D * D, t);
-            GET(n + "self_attn." + part[k] + ".bias", D, t2);
-            const float sc = k == 0 ? 0.125f : 1.f;  // head_dim^-0.5 = 1 / sqrt(64): exact
-            for (size_t i = 0; i < t.size(); ++i) qkv[(size_t)k * D * D + i] = t[i] * sc;
-            for (int i = 0; i < D; ++i) bqkv[(size_t)k * D + i] = t2[i] * sc;
-        }
-        UP(upload_f32(L.wqkv, qkv));
-        UP(upload_f32(L.bqkv, bqkv));
-        GET(n + "self_attn.out_proj.weight", (long)D * D, t);
-        UP(upload_f32(L.wo, t));
-        GET(n + "self_attn.out_proj.bias", D, t);
-        UP(upload_f32(L.bo, t));
-        GET(n + "self_attn_layer_norm.weight", D, t);
-        UP(upload_f32(L.g1, t));
-        GET(n + "self_attn_layer_norm.bias", D, t);
-        UP(upload_f32(L.b1n, t));
-        GET(n + "fc1.weight", (long)FF * D, t);
-        UP(upload_f32(L.w1, t));
-        GET(n + "fc1.bias", FF, t);
-        UP(upload_f32(L.b1, t));
-        GET(n + "fc2.weight", (long)D * FF, t);
-        UP(upload_f32(L.w2, t));
-        GET(n + "fc2.bias", D, t);
-        UP(upload_f32(L.b2, t));
-        GET(n + "final_layer_norm.weight", D, t);
-        UP(upload_f32(L.g2, t));
-        GET(n + "final_layer_norm.bias", D, t);
-        UP(upload_f32(L.b2n, t));
-    }
+    for (int l = 0; l < c.encoder_layers; ++l)  // head_dim^-0.5 = 1 / sqrt(64): exact
+        if (load_layer(e, ck, "encoder.layers." + std::to_string(l) + ".", kFairseqLayer, 0.125f, false, w.layers[l])) return 1;
     return 0;
 }
 
@@ -221,28 +188,6 @@ static int mae_ast_forward(s3enc_handle e, const float* const* wav_ptrs_host, co
     // ---- where the states go ----
     Sink sink{e, st, feat_sum ? 2 : 0, out, (long)layer_stride, F32, M, D, fo.w, fo.feat_norm};
     HIP_TRY(sink.zero_without_terms(NL, M));
-    auto gemm = [&](const char* kind, const float* A, int K, const DevBuf& W, const DevBuf& bias, int N, int act, const float* res,
-                    float* o) -> hipError_t {
-        GemmParams g{};
-        g.A = A;
-        g.lda = K;
-        g.W = W.p;
-        g.bias = (const float*)bias.p;
-        g.M = (int)M;
-        g.N = N;
-        g.K = K;
-        g.batches = 1;
-        g.act = act;
-        g.residual = res;
-        g.out32 = o;
-        g.ldo = N;
-        Prof pr(e, st, kind, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N * (res ? 2 : 1)));
-        return launch_gemm(F32, g, st);
-    };
-    auto ln = [&](const char* kind, const float* in, const DevBuf& g, const DevBuf& b, float* o, const LnAcc& fa) -> hipError_t {
-        Prof pr(e, st, kind, 0, 4.0 * M * D * 2);
-        return launch_layernorm(F32, in, (const float*)g.p, (const float*)b.p, M, D, 0, o, nullptr, st, fa);
-    };
 
     // ---- front end: (B, F_max, 128) raw log-mel, zeros behind every utterance's frames ----
     {
@@ -262,45 +207,30 @@ static int mae_ast_forward(s3enc_handle e, const float* const* wav_ptrs_host, co
         Prof pr(e, st, "patch_embed_two_step", 2.0 * M * D * Kp, 4.0 * (3.0 * M * Kp + (double)D * Kp + 4.0 * M * D));
         HIP_TRY(launch_patch_embed_two_step(pe, rows, st));
     }
-    if (!prel) HIP_TRY(ln("layernorm:enc", tmp, w.eln_g, w.eln_b, xa, LnAcc()));
+    if (!prel) {
+        Prof pr(e, st, "layernorm:enc", 0, 4.0 * M * D * 2);
+        HIP_TRY(launch_layernorm(F32, tmp, (const float*)w.eln_g.p, (const float*)w.eln_b.p, M, D, 0, xa, nullptr, st));
+    }
 
     // ---- Transformer layers over B sequences of Ttok tokens; x_cur is the layer's input ----
     float* x_cur = xa;
+    LayerRun run{B, Ttok, d_kv, prel};
+    run.xT = xn;
+    run.qkv = qkv;
+    run.attn = ctx;
+    run.hbuf = hbuf;
+    run.tmp1 = tmp;
+    run.tmp2 = xn;
     for (int l = 0; l < NL; ++l) {
-        const MjLayerW& L = w.layers[l];
         // the state's home: its slot of the caller's slab (the next layer reads it there), or the buffer x_cur does not occupy
         float* x_next = sink.slot32(l) ? sink.slot32(l) : (x_cur == xa ? xb : xa);
-        const float* a_in = x_cur;
-        if (prel) {
-            HIP_TRY(ln("layernorm:ln1", x_cur, L.g1, L.b1n, xn, LnAcc()));
-            a_in = xn;
-        }
-        HIP_TRY(gemm("gemm:qkv", a_in, D, L.wqkv, L.bqkv, 3 * D, 0, nullptr, qkv));
-        {
-            AttnParams a{};
-            a.qkv = qkv;
-            a.out = ctx;
-            a.valid = d_kv;
-            a.B = B;
-            a.T = (int)Ttok;
-            a.H = H;
-            Prof pr(e, st, "attention", 4.0 * B * H * (double)Ttok * Ttok * 64, 4.0 * M * D * 4);
-            HIP_TRY(launch_attention(F32, a, st));
-        }
-        HIP_TRY(gemm("gemm:out_proj", ctx, D, L.wo, L.bo, D, 0, x_cur, tmp));
-        if (prel) {
-            HIP_TRY(ln("layernorm:ln2", tmp, L.g2, L.b2n, xn, LnAcc()));
-            HIP_TRY(gemm("gemm:fc1", xn, D, L.w1, L.b1, FF, 1, nullptr, hbuf));
-            HIP_TRY(gemm("gemm:fc2", hbuf, FF, L.w2, L.b2, D, 0, tmp, x_next));
-            if (sink.term(l)) {
-                Prof pr(e, st, "emit_state", 0, 4.0 * M * D * 2);
-                HIP_TRY(sink.emit(l, x_next));
-            }
-        } else {
-            HIP_TRY(ln("layernorm:ln1", tmp, L.g1, L.b1n, xn, LnAcc()));
-            HIP_TRY(gemm("gemm:fc1", xn, D, L.w1, L.b1, FF, 1, nullptr, hbuf));
-            HIP_TRY(gemm("gemm:fc2", hbuf, FF, L.w2, L.b2, D, 0, xn, tmp));
-            HIP_TRY(ln("layernorm:ln2", tmp, L.g2, L.b2n, x_next, sink.acc(l, 2)));
+        run.x = x_cur;
+        run.x_next = x_next;
+        run.acc_out = prel ? LnAcc() : sink.acc(l, 2);
+        if (encoder_layer(e, st, w.layers[l], run)) return 1;
+        if (prel && sink.term(l)) {
+            Prof pr(e, st, "emit_state", 0, 4.0 * M * D * 2);
+            HIP_TRY(sink.emit(l, x_next));
         }
         HIP_TRY(sink.done(l));
         x_cur = x_next;

@@ -203,41 +203,8 @@ static int mj_create(s3enc_encoder* e, const Ckpt& ck) {
     UP(upload_f32(w.in_beta, t));
     const int NW = x.share_layer ? 1 : c.encoder_layers;  // share_layer: the ModuleList holds ONE module (model.py:343-344)
     w.layers.resize(NW);
-    for (int l = 0; l < NW; ++l) {
-        MjLayerW& L = w.layers[l];
-        const std::string n = "encoder.layer." + std::to_string(l) + ".";
-        std::vector<float> qkv((size_t)3 * D * D), bqkv((size_t)3 * D);
-        const char* part[3] = {"query", "key", "value"};
-        for (int k = 0; k < 3; ++k) {
-            GET(n + "attention.self." + part[k] + ".weight", (long)D * D, t);
-            GET(n + "attention.self." + part[k] + ".bias", D, t2);
-            const float sc = k == 0 ? 0.125f : 1.f;  // 1 / sqrt(64): exact
-            for (size_t i = 0; i < t.size(); ++i) qkv[(size_t)k * D * D + i] = t[i] * sc;
-            for (int i = 0; i < D; ++i) bqkv[(size_t)k * D + i] = t2[i] * sc;
-        }
-        UP(upload_f32(L.wqkv, qkv));
-        UP(upload_f32(L.bqkv, bqkv));
-        GET(n + "attention.output.dense.weight", (long)D * D, t);
-        UP(upload_f32(L.wo, t));
-        GET(n + "attention.output.dense.bias", D, t);
-        UP(upload_f32(L.bo, t));
-        GET(n + "attention.output.LayerNorm.weight", D, t);
-        UP(upload_f32(L.g1, t));
-        GET(n + "attention.output.LayerNorm.bias", D, t);
-        UP(upload_f32(L.b1n, t));
-        GET(n + "intermediate.dense.weight", (long)FF * D, t);
-        UP(upload_f32(L.w1, t));
-        GET(n + "intermediate.dense.bias", FF, t);
-        UP(upload_f32(L.b1, t));
-        GET(n + "output.dense.weight", (long)D * FF, t);
-        UP(upload_f32(L.w2, t));
-        GET(n + "output.dense.bias", D, t);
-        UP(upload_f32(L.b2, t));
-        GET(n + "output.LayerNorm.weight", D, t);
-        UP(upload_f32(L.g2, t));
-        GET(n + "output.LayerNorm.bias", D, t);
-        UP(upload_f32(L.b2n, t));
-    }
+    for (int l = 0; l < NW; ++l)  // 1 / sqrt(64): exact
+        if (load_layer(e, ck, "encoder.layer." + std::to_string(l) + ".", kBertLayer, 0.125f, false, w.layers[l])) return 1;
     w.pos_rows = x.sequence_length > 0 ? x.sequence_length : 3008;  // a chunk never has more rows than sequence_length
     mj_position_rows(w.pos_rows, D, t);
     UP(upload_f32(w.pos, t));
@@ -348,24 +315,6 @@ static int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const i
         HIP_TRY(sink.done(si));
         return 0;
     };
-    auto gemm = [&](const char* kind, const float* A, int K, const DevBuf& W, const DevBuf& bias, int N, int act, const float* res,
-                    float* o) -> hipError_t {
-        GemmParams g{};
-        g.A = A;
-        g.lda = K;
-        g.W = W.p;
-        g.bias = (const float*)bias.p;
-        g.M = (int)Mp;
-        g.N = N;
-        g.K = K;
-        g.batches = 1;
-        g.act = act;
-        g.residual = res;
-        g.out32 = o;
-        g.ldo = N;
-        Prof pr(e, st, kind, 2.0 * Mp * N * K, 4.0 * ((double)Mp * K + (double)N * K + (double)Mp * N * (res ? 2 : 1)));
-        return launch_gemm(F32, g, st);
-    };
     auto ln = [&](const float* in, const float* pos, const DevBuf& g, const DevBuf& b, float* o, int si) -> hipError_t {
         LnEpsParams p;
         p.x = in;
@@ -411,14 +360,14 @@ static int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const i
     }
 
     // ---- input representation: state 0 ----
-    HIP_TRY(gemm("gemm:mj_in", feat, F, w.in_w, w.in_b, D, 0, nullptr, tmp));
+    HIP_TRY(linear_f32(e, st, {"gemm:mj_in", feat, w.in_w.p, w.in_b.p, Mp, D, F, 0, nullptr, tmp}));
     HIP_TRY(ln(tmp, (const float*)w.pos.p, w.in_g, w.in_beta, xa, 0));
     if (state_done(0)) return 1;
 
     // ---- post-LN BERT layers over B * n sequences of Tc rows ----
     for (int l = 0; l < NL; ++l) {
-        const MjLayerW& L = w.layers[x.share_layer ? 0 : l];
-        HIP_TRY(gemm("gemm:qkv", xa, D, L.wqkv, L.bqkv, 3 * D, 0, nullptr, qkv));
+        const LayerW& L = w.layers[x.share_layer ? 0 : l];
+        HIP_TRY(linear_f32(e, st, {"gemm:qkv", xa, L.wqkv.p, L.bqkv.p, Mp, 3 * D, D, 0, nullptr, qkv}));
         {
             AttnParams a{};
             a.qkv = qkv;
@@ -430,11 +379,11 @@ static int mj_forward(s3enc_handle e, const float* const* wav_ptrs_host, const i
             Prof pr(e, st, "attention", 4.0 * NS * H * Tc * Tc * 64, 4.0 * Mp * D * 4);
             HIP_TRY(launch_attention(F32, a, st));
         }
-        HIP_TRY(gemm("gemm:out_proj", ctx, D, L.wo, L.bo, D, 0, xa, tmp));
-        HIP_TRY(ln(tmp, nullptr, L.g1, L.b1n, xb, -1));
-        HIP_TRY(gemm("gemm:fc1", xb, D, L.w1, L.b1, FF, 1, nullptr, hbuf));
-        HIP_TRY(gemm("gemm:fc2", hbuf, FF, L.w2, L.b2, D, 0, xb, tmp));
-        HIP_TRY(ln(tmp, nullptr, L.g2, L.b2n, xa, l + 1));
+        HIP_TRY(linear_f32(e, st, {"gemm:out_proj", ctx, L.wo.p, L.bo.p, Mp, D, D, 0, xa, tmp}));
+        HIP_TRY(ln(tmp, nullptr, L.ln1g, L.ln1b, xb, -1));
+        HIP_TRY(linear_f32(e, st, {"gemm:fc1", xb, L.w1.p, L.b1.p, Mp, FF, D, 1, nullptr, hbuf}));
+        HIP_TRY(linear_f32(e, st, {"gemm:fc2", hbuf, L.w2.p, L.b2.p, Mp, D, FF, 0, xb, tmp}));
+        HIP_TRY(ln(tmp, nullptr, L.ln2g, L.ln2b, xa, l + 1));
         if (state_done(l + 1)) return 1;
     }
     return 0;

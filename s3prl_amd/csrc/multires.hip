@@ -192,118 +192,22 @@ int multires_tail(s3enc_handle e, hipStream_t st, int B, const MrPlan& plan, con
             cur = h0;
         }
         if (emit(cur, T, bp.factor)) return 1;  // the input of the block's first layer
+        // (the U-net's layers keep LayerNorm 1's fp32 output in its own buffer: neither the in-place form nor the fold into fc2)
+        LayerRun run{B, T, d_valid[bi], prel};
+        run.xT = xT;
+        run.qkv = qkv;
+        run.attn = attn;
+        run.hbuf = hbuf;
+        run.tmp1 = tmp1;
+        run.tmp2 = tmp2;
         for (int l = 0; l < NLb; ++l) {
-            LayerW& Lw = bw.layers[l];
             const bool lastl = l == NLb - 1;
-            const void* a_in;
-            if (prel) {
-                Prof pr(e, st, "layernorm:ln1", 0, gM * D * (4 + es));
-                HIP_TRY(launch_layernorm(dt, cur, (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, M, D, 0,
-                                         dt == F32 ? (float*)xT : nullptr, dt == F32 ? nullptr : xT, st));
-                a_in = xT;
-            } else {
-                a_in = dt == F32 ? (const void*)cur : (const void*)xT;
-            }
-            {
-                GemmParams g{};
-                g.A = a_in;
-                g.lda = D;
-                g.W = Lw.wqkv.p;
-                g.W_x3 = Lw.wqkv3.p;
-                g.bias = (const float*)Lw.bqkv.p;
-                g.M = (int)M;
-                g.N = 3 * D;
-                g.K = D;
-                g.batches = 1;
-                g.ldo = 3 * D;
-                if (dt == F32) g.out32 = (float*)qkv; else g.out16 = qkv;
-                Prof pr(e, st, "gemm:qkv", 2.0 * gM * 3 * D * D, (gM * D + 3.0 * D * D + gM * 3 * D) * es);
-                HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-            }
-            {
-                AttnParams a{};
-                a.qkv = qkv;
-                a.out = attn;
-                a.valid = d_valid[bi];
-                a.B = B;
-                a.T = (int)T;
-                a.H = H;
-                Prof pr(e, st, "attention", 4.0 * B * H * (double)T * T * 64, gM * 4 * D * es);
-                HIP_TRY(launch_attention(e->x3 ? 3 : dt, a, st));
-            }
-            {
-                GemmParams g{};
-                g.A = attn;
-                g.lda = D;
-                g.W = Lw.wo.p;
-                g.W_x3 = Lw.wo3.p;
-                g.bias = (const float*)Lw.bo.p;
-                g.M = (int)M;
-                g.N = D;
-                g.K = D;
-                g.batches = 1;
-                g.ldo = D;
-                g.residual = cur;
-                g.out32 = tmp1;
-                Prof pr(e, st, "gemm:out_proj", 2.0 * gM * D * D, (gM * D + (double)D * D) * es + gM * D * 8);
-                HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-            }
-            const float* ffn_res;
-            const void* ffn_in;
-            if (prel) {
-                Prof pr(e, st, "layernorm:ln2", 0, gM * D * (4 + es));
-                HIP_TRY(launch_layernorm(dt, tmp1, (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, M, D, 0,
-                                         dt == F32 ? (float*)xT : nullptr, dt == F32 ? nullptr : xT, st));
-                ffn_res = tmp1;
-                ffn_in = xT;
-            } else {
-                Prof pr(e, st, "layernorm:ln1", 0, gM * D * (8 + (dt == F32 ? 0 : es)));
-                HIP_TRY(launch_layernorm(dt, tmp1, (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, M, D, 0, tmp2,
-                                         dt == F32 ? nullptr : xT, st));
-                ffn_res = tmp2;
-                ffn_in = dt == F32 ? (const void*)tmp2 : (const void*)xT;
-            }
-            {
-                GemmParams g{};
-                g.A = ffn_in;
-                g.lda = D;
-                g.W = Lw.w1.p;
-                g.W_x3 = Lw.w13.p;
-                g.bias = (const float*)Lw.b1.p;
-                g.M = (int)M;
-                g.N = F;
-                g.K = D;
-                g.batches = 1;
-                g.act = 1;
-                g.ldo = F;
-                if (dt == F32) g.out32 = (float*)hbuf; else g.out16 = hbuf;
-                Prof pr(e, st, "gemm:fc1", 2.0 * gM * F * D, (gM * D + (double)F * D + gM * F) * es);
-                HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-            }
-            float* nxt = (!prel && lastl) ? y_out : pick(cur);
-            {
-                GemmParams g{};
-                g.A = hbuf;
-                g.lda = F;
-                g.W = Lw.w2.p;
-                g.W_x3 = Lw.w23.p;
-                g.bias = (const float*)Lw.b2.p;
-                g.M = (int)M;
-                g.N = D;
-                g.K = F;
-                g.batches = 1;
-                g.ldo = D;
-                g.residual = ffn_res;
-                g.out32 = prel ? nxt : tmp1;
-                Prof pr(e, st, "gemm:fc2", 2.0 * gM * D * F, (gM * F + (double)D * F) * es + gM * D * 8);
-                HIP_TRY(launch_gemm(dt, wsplit_of(e, g), st));
-            }
-            if (!prel) {
-                Prof pr(e, st, "layernorm:ln2", 0, gM * D * (8 + (dt == F32 ? 0 : es)));
-                HIP_TRY(launch_layernorm(dt, tmp1, (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, M, D, 0, nxt,
-                                         dt == F32 ? nullptr : xT, st));
-            }
-            cur = nxt;
+            run.x = cur;
+            run.x16 = xT;
+            run.x_next = (!prel && lastl) ? y_out : pick(cur);
+            run.x16_next = (prel || dt == F32) ? nullptr : xT;
+            if (encoder_layer(e, st, bw.layers[l], run)) return 1;
+            cur = run.x_next;
             // post-LN: the layer output is the next layer's input / the block output; pre-LN: the last stream is not a state
             if (!prel || !lastl)
                 if (emit(cur, T, bp.factor)) return 1;

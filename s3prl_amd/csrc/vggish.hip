@@ -322,22 +322,8 @@ static int vggish_forward(s3enc_handle e, const float* const* wav_ptrs_host, con
     const float* a = act[NL - 1];
     long K = Kflat;
     for (int i = 0; i < 3; ++i) {
-        GemmParams g{};
-        g.A = a;
-        g.lda = K;
-        g.W = w.fw[i].p;
-        g.bias = (const float*)w.fb[i].p;
-        g.M = (int)Etot;
-        g.N = x.fc[i];
-        g.K = (int)K;
-        g.batches = 1;
-        g.out32 = fcb[i & 1];
-        g.ldo = x.fc[i];
-        {
-            const std::string kind = "gemm:vggish_fc" + std::to_string(i);
-            Prof pr(e, st, kind.c_str(), 2.0 * Etot * x.fc[i] * K, 4.0 * ((double)Etot * K + (double)x.fc[i] * K + (double)Etot * x.fc[i]));
-            HIP_TRY(launch_gemm(F32, g, st));
-        }
+        const std::string kind = "gemm:vggish_fc" + std::to_string(i);
+        HIP_TRY(linear_f32(e, st, {kind.c_str(), a, w.fw[i].p, w.fb[i].p, Etot, x.fc[i], (int)K, 0, nullptr, fcb[i & 1]}));
         {
             Prof pr(e, st, "relu", 0, 8.0 * Etot * x.fc[i]);
             HIP_TRY(launch_relu(fcb[i & 1], Etot * x.fc[i], st));

@@ -600,30 +600,12 @@ static int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, co
 
     // ---- vector quantizer: codewords replace z as the aggregator's input ----
     if (c.vq_type) {
-        auto gemm = [&](const char* kind, const float* A, long lda, const void* W, const float* bias, int N, int K, float* o,
-                        long ldo) -> hipError_t {
-            GemmParams g{};
-            g.A = A;
-            g.lda = lda;
-            g.a_bs = 0;
-            g.W = W;
-            g.bias = bias;
-            g.M = (int)M;
-            g.N = N;
-            g.K = K;
-            g.batches = 1;
-            g.out32 = o;
-            g.ldo = ldo;
-            g.o_bs = 0;
-            Prof pr(e, st, kind, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-            return launch_gemm(F32, g, st);
-        };
         if (c.vq_type == 1) {
             const float* h = zbuf;
             int in = C;
             for (int i = 0; i + 1 < c.vq_depth; ++i) {
                 float* o = (i & 1) ? h1 : h0;
-                HIP_TRY(gemm("gemm:w2v_vq_proj", h, in, w.vq_w[i].p, (const float*)w.vq_b[i].p, 2 * C, in, o, 2L * C));
+                HIP_TRY(linear_f32(e, st, {"gemm:w2v_vq_proj", h, w.vq_w[i].p, w.vq_b[i].p, M, 2 * C, in, 0, nullptr, o}));
                 {
                     Prof pr(e, st, "w2v_relu", 0, 8.0 * M * 2 * C);
                     HIP_TRY(launch_relu(o, M * 2L * C, st));
@@ -632,10 +614,10 @@ static int wav2vec_forward(s3enc_handle e, const float* const* wav_ptrs_host, co
                 in = 2 * C;
             }
             const int d = c.vq_depth - 1;
-            HIP_TRY(gemm("gemm:w2v_vq_logits", h, in, w.vq_w[d].p, (const float*)w.vq_b[d].p, G * V, in, scores, (long)G * V));
+            HIP_TRY(linear_f32(e, st, {"gemm:w2v_vq_logits", h, w.vq_w[d].p, w.vq_b[d].p, M, G * V, in, 0, nullptr, scores}));
         } else {
             for (int g = 0; g < G; ++g)
-                HIP_TRY(gemm("gemm:w2v_km_proj", zbuf + (long)g * Dv, C, w.km_w[g].p, nullptr, Dv, Dv, proj + (long)g * Dv, C));
+                HIP_TRY(linear_f32(e, st, {"gemm:w2v_km_proj", zbuf + (long)g * Dv, w.km_w[g].p, nullptr, M, Dv, Dv, 0, nullptr, proj + (long)g * Dv, nullptr, C, C}));
             Prof pr(e, st, "w2v_kmeans", 3.0 * M * G * V * Dv, 4.0 * ((double)M * C * 2 + (double)M * G * V));
             HIP_TRY(launch_kmeans_stats(proj, B, (int)T, C, G, d_kst, st));
             HIP_TRY(launch_kmeans_scores(proj, d_kst, (const float*)w.km_g.p, (const float*)w.km_b.p, (const float*)w.emb_t.p, B, (int)T,
