@@ -135,7 +135,18 @@ enum { S3ENC_HUBERT = 0, S3ENC_WAV2VEC2 = 1, S3ENC_WAVLM = 2,
         * (embed_dim, 80), bias}, encoder.pos_conv.0.{weight_g,weight_v,bias}, encoder.layer_norm.*, encoder.layers.N.*.  Refused by name:
         * layer_norm_first, pos_conv_depth > 1, the Conformer / WavLM / DistilHuBERT options, and by the forward an utterance with F < 2
         * (the reference's std over one frame is NaN). */
-       S3ENC_DECOAR2 = 16 };
+       S3ENC_DECOAR2 = 16,
+       /* SSAST (upstream/ssast/{expert,ast_models,audio}.py; ssast_frame_base, ssast_patch_base): every utterance zero-padded to nseg =
+        * ceil(n_max / window_samples) windows of window_samples samples; per window a kaldi log-mel front end at 128 bins with a hanning
+        * window (25 ms / 10 ms, pre-emphasis 0.97, snip_edges), (y + 4.2677393) / (4.5689974 * 2), zero rows up to target_length; a
+        * Conv2d(1, D, (fshape, tshape), stride (fstride, tstride)) patch embedding on the (128, target_length) image, f_dim x t_dim
+        * tokens behind a cls and a dist token, the checkpoint's position rows (cut or interpolated at load); encoder_layers pre-LN timm
+        * blocks (one fused attn.qkv Linear, LayerNorm eps from the block, erf-GELU) with no key mask.  encoder_layers states of (B,
+        * T_out, f_dim * D), T_out = min(nseg * t_dim, ceil(n_max / (160 * tstride))): the layer outputs without the two prefix tokens,
+        * row s * t_dim + ti the f_dim tokens of time step ti of window s.  Nothing is masked: rows behind an utterance's own length
+        * are the reference's values (zero samples through the whole model), not zeros.  compute_dtype S3ENC_F32 only; built by
+        * s3enc_create_ssast.  (17 is not assigned: the suite keeps it as its probe of an unknown family id.) */
+       S3ENC_SSAST = 18 };
 /* arithmetic type of the GEMM / attention operands; accumulation, norms, softmax, GELU and the residual
  * stream are always fp32 (the reference's Fp32GroupNorm / Fp32LayerNorm / fp32 softmax guards,
  * wav2vec2_model.py:1826-1853,1899-1900). */
@@ -465,6 +476,31 @@ typedef struct s3enc_mae_ast_config {
     int32_t pos_rows;                               /* rows of enc_sine_pos_embed.pe handed over: min(max_token_length, 8192) */
 } s3enc_mae_ast_config;
 
+/* S3ENC_SSAST only (ssast/expert.py:24-133, ast_models.py:263-393, audio.py:88-116): the second configuration block of
+ * s3enc_create_ssast.  s3enc_config carries embed_dim = D, heads, ffn_dim and encoder_layers; layer_norm_first must be 1; its conv fields
+ * are not read.  f_dim = (128 - fshape) / fstride + 1, t_dim = (target_length - tshape) / tstride + 1, 2 + f_dim * t_dim tokens per
+ * window.  Inside the handle the patch tokens of a window are TIME-major (token 2 + ti * f_dim + fi; the reference's order is f-major):
+ * with neither a mask nor a relative position the model is equivariant under the permutation, and every f_dim-row group of a sequence
+ * is one state row.  Tensors, prepared by the binder from the released file's module.v.* (s3prl_amd/ckpt.py: ssast_hot_path):
+ * patch.weight (D, tshape * fshape), the conv weight summed over its input channel and permuted to [n][t][f]; patch.bias (D); prefix
+ * (2, D) = cls_token + pos_embed[0], dist_token + pos_embed[1]; pos (pos_rows, D), pos_rows = f_dim * t_dim, the position rows of the
+ * patch tokens after the reference's cut / bilinear interpolation, in the time-major order; blocks.N.{norm1,attn.qkv,attn.proj,norm2,
+ * mlp.fc1,mlp.fc2}.{weight,bias} as stored (attn.qkv rows q | k | v; the q rows are scaled by head_dim^-0.5 = 0.125 at create).  v.norm
+ * reaches no returned state and is not read.  s3enc_create_ssast refuses by name: every compute dtype but fp32, layer_norm_first = 0,
+ * embed_dim / heads != 64, a geometry patchstrided.hip does not take (fshape outside {16, 32, 64, 128}, tshape outside 1..32, an odd
+ * fstride), window_samples < 400 or not a multiple of 4, target_length < tshape or below the window's own frame count, pos_rows !=
+ * f_dim * t_dim. */
+typedef struct s3enc_ssast_config {
+    int32_t fshape;                                 /* patch extent in mel bins: 16 (patch), 128 (frame) */
+    int32_t tshape;                                 /* patch extent in frames: 16 (patch), 2 (frame) */
+    int32_t fstride;                                /* 10 (patch), 128 (frame) */
+    int32_t tstride;                                /* 10 (patch), 1 (frame) */
+    int32_t window_samples;                         /* int(window_secs * 16000) */
+    int32_t target_length;                          /* int(window_secs * 16000 / 160): image rows per window */
+    float ln_eps;                                   /* the blocks' LayerNorm eps: 1e-6 */
+    int32_t pos_rows;                               /* f_dim * t_dim */
+} s3enc_ssast_config;
+
 /* S3ENC_BYOL_S only: the second configuration block of s3enc_create_byol_s.  s3enc_config carries the window geometry as n_conv = 1,
  * conv_kernel[0] / conv_stride[0] = window / step in samples, conv_dim = embed_dim = 2048, encoder_layers = 0 (one state).  The
  * caller computes window = int(window_secs * 1000 / 1000 * 16000) and step = int(hop_secs * 1000 / 1000.0 * 16000) with the
@@ -586,6 +622,16 @@ int s3enc_create_mae_ast(const s3enc_config* cfg, const s3enc_mae_ast_config* ma
  * stem_fused, conv2d_n64. */
 int s3enc_create_byol_s(const s3enc_config* cfg, const s3enc_byol_s_config* byol_s, const s3enc_tensor* tensors, int32_t n_tensors,
                         int32_t device, s3enc_handle* out);
+/* The S3ENC_SSAST family: s3enc_config beside its own block (the other create entries refuse the family by name).  Replaces
+ * UpstreamExpert.__init__ of upstream/ssast/expert.py.  On the handle: s3enc_num_frames(n) is T_out(n) = min(ceil(n / W) * t_dim,
+ * ceil(n / (160 * tstride))), W = window_samples; s3enc_valid_frames(length, n_max) is min(ceil(length / (160 * tstride)), T_out(n_max)),
+ * the wrapper's rule (the rows behind it are the reference's values, not zeros); s3enc_downsample_rate is 160 * tstride;
+ * s3enc_num_states is encoder_layers for S3ENC_SEL_HIDDEN (the layer outputs; the other selections are refused); a state row is f_dim * D
+ * wide (layer_stride counts B * T_out * f_dim * D elements); out_dtype must be S3ENC_F32; featurize is the elementwise weighted sum
+ * (feat_normalize is refused).  There is no minimum length: a window wholly behind an utterance's end is embedded and encoded like any
+ * other.  The forward status word is not fed by this family's LayerNorms.  Tuning keys patch_strided_fused, ssast_chunk. */
+int s3enc_create_ssast(const s3enc_config* cfg, const s3enc_ssast_config* ssast, const s3enc_tensor* tensors, int32_t n_tensors,
+                       int32_t device, s3enc_handle* out);
 int s3enc_destroy(s3enc_handle h);
 
 /* T = frames produced for an n-sample input: floor((L-k)/s)+1 through the conv stack
@@ -830,6 +876,13 @@ int s3enc_debug_gemm_schedule(int32_t M, int32_t N, int32_t batches, int32_t tm,
  *                   the image in place (patchembed.hip), 0 = a gather kernel that writes the (B * tokens, kt * kc) rows, the tile GEMM
  *                   and a position add — the yardstick and a second implementation, held to the fixture bound; measured 0.0625
  *                   against 0.0798 ms per 32 x 10 s mae_ast_patch embedding, the forwards indistinguishable (profiles/mae_ast_fp32.md);
+ *   "patch_strided_fused": S3ENC_SSAST handles and s3enc_op_patch_embed_strided: 1 (default) = the overlapping patch embedding as one
+ *                   implicit GEMM that reads the image in place (patchstrided.hip), 0 = a gather kernel that writes the (windows *
+ *                   tokens, tshape * fshape) rows, the tile GEMM and a position add — the yardstick and a second implementation, held
+ *                   to the same bound; measured 0.147 against 0.187 ms per 32 x 10 s ssast_patch_base embedding, the forwards
+ *                   indistinguishable and the states bit-equal (profiles/ssast_fp32.md);
+ *   "ssast_chunk": S3ENC_SSAST handles: tokens per pass of the embedding and the layers (default 65536, 1..4194304; whole windows, at
+ *                   least one): the workspace is bounded by it and does not grow with B x nseg; a row's bits do not depend on it;
  *   "stem_fused":   S3ENC_BYOL_S resnetish handles: 1 = the stem's 7 x 7 convolution, affine, ReLU and 3 x 3 / stride-2 max-pool in one
  *                   kernel (2.25 x the multiply-adds, no un-pooled map), 0 (default) = the un-pooled map written once and pooled by
  *                   a second kernel — the same bits; measured 223.0 against 222.2 ms per forward (profiles/byol_s_fp32.md);
@@ -1059,6 +1112,23 @@ int s3enc_op_stem7x7_pool(const float* x, const float* w_host, const float* scal
  * operands that are not 16-byte aligned.  Tuning key patch_embed_fused = 0: gather + tile GEMM + position add.  Synchronises. */
 int s3enc_op_patch_embed(const float* img, int64_t img_bs, const float* w_host, const float* bias, const float* pos, const int32_t* kv,
                          int32_t B, int32_t Tt, int32_t kt, int32_t kc, int32_t N, float* out, void* stream);
+
+/* The patch embedding with OVERLAPPING patches of (rows, 128) fp32 images as an implicit GEMM over the tokens of all windows
+ * (patchstrided.hip): SSAST's Conv2d(1, N, (fshape, tshape), stride (fstride, tstride)), the position row and the sequence layout.
+ *   out[w][2 + ti*f_dim + fi][n] = sum_{t<tshape} sum_{f<fshape} img[w][ti*tstride + t][fi*fstride + f] * w[n][t*fshape + f] + bias[n]
+ *                                  + pos[ti*f_dim + fi][n];   out[w][0 | 1][n] = prefix[0 | 1][n]
+ *   f_dim = (128 - fshape) / fstride + 1, t_dim = (rows - tshape) / tstride + 1.  img: device fp32, window w at img + w * img_bs, `rows`
+ *   rows of 128 floats: nothing behind them is read.  w_host: HOST fp32 (N, tshape * fshape), the conv weight permuted to [n][t][f].
+ *   bias: device [N] or null.  pos: device (f_dim * t_dim, N) in the time-major token order, or null.  prefix: device (2, N) or null
+ *   (rows 0 and 1 are then not written).  out: device (nwin, 2 + f_dim * t_dim, N).  tile_rows: 0 = the launcher's choice, 64 | 128 =
+ *   that tile height (the bits are the same).  fp32 MFMA on 64-byte K steps in a fixed order: a token's bits depend neither on nwin,
+ *   nor on the window it sits in, nor on the tile height.
+ * Refused by message: fshape outside {16, 32, 64, 128}, tshape outside 1..32, an odd fstride, rows < tshape, N % 4 != 0, img_bs < rows
+ * * 128 or not a multiple of 4, operands that are not 16-byte aligned.  Tuning key patch_strided_fused = 0: gather + tile GEMM +
+ * position add (tile_rows is then not read).  Synchronises. */
+int s3enc_op_patch_embed_strided(const float* img, int64_t img_bs, const float* w_host, const float* bias, const float* pos,
+                                 const float* prefix, int32_t nwin, int32_t rows, int32_t fshape, int32_t tshape, int32_t fstride,
+                                 int32_t tstride, int32_t N, int32_t tile_rows, float* out, void* stream);
 
 /* A forward and a backward unidirectional nn.LSTM on packed sequences, side by side, on the batch-shared kernel: one launch per
  * time step for both directions, W_hh read once per step for the whole batch (fp32 MFMA).  pre_fwd / pre_bwd: device fp32, row

@@ -20,7 +20,7 @@ STATUS_NONFINITE, STATUS_PENDING = 1, 1 << 30  # s3enc_forward_status bits (incl
 DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16, "fp16": F16, "f16": F16,
           "float16": F16, "fp32x3": F32X3, "f32x3": F32X3, "bf16x3": F32X3,
           "fp16x2": F16X2, "f16x2": F16X2}
-FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13, "byol_s": 14, "lighthubert": 15, "decoar2": 16}
+FAMILY = {"hubert": 0, "wav2vec2": 1, "wavlm": 2, "distiller": 3, "multires_hubert": 4, "wav2vec": 5, "cpc": 6, "apc": 7, "mockingjay": 8, "decoar": 9, "npc": 10, "vggish": 11, "byol_a": 12, "mae_ast": 13, "byol_s": 14, "lighthubert": 15, "decoar2": 16, "ssast": 18}
 CPC_NORM = {"layerNorm": 0, "instanceNorm": 1, "ID": 2, "batchNorm": 3}            # s3enc_cpc_config.norm_mode
 CPC_AR = {"LSTM": 0, "GRU": 1, "RNN": 2, "transformer": 3, "no_ar": 4}             # s3enc_cpc_config.ar_mode
 APC_WINDOW = {"povey": 0, "hamming": 1}                                            # s3enc_apc_config.window
@@ -132,6 +132,12 @@ class S3MaeAstConfig(C.Structure):
                 ("bn_eps", C.c_float), ("pos_rows", C.c_int32)]
 
 
+class S3SsastConfig(C.Structure):
+    """s3enc_ssast_config: the window / patch block of an SSAST handle (s3enc_create_ssast)."""
+    _fields_ = [("fshape", C.c_int32), ("tshape", C.c_int32), ("fstride", C.c_int32), ("tstride", C.c_int32),
+                ("window_samples", C.c_int32), ("target_length", C.c_int32), ("ln_eps", C.c_float), ("pos_rows", C.c_int32)]
+
+
 BYOL_S_NETWORK = {"default": 0, "resnetish": 1, "cvt": 2, "clstm": 3}          # s3enc_byol_s_config.network
 
 
@@ -236,6 +242,7 @@ _PROTOS = {
     "s3enc_op_conv2d_res": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I64, _VP]),
     "s3enc_op_stem7x7_pool": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_patch_embed": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
+    "s3enc_op_patch_embed_strided": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "s3enc_op_argmax_gather": (C.c_int, [_VP, _VP, _I32, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_relpos_attention": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "s3enc_op_posconv": (C.c_int, [_I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
@@ -519,6 +526,17 @@ def make_byol_s_config(cfg) -> S3ByolSConfig:
     return c
 
 
+def make_ssast_config(cfg) -> S3SsastConfig:
+    """The second configuration block of a ``family="ssast"`` EncoderConfig (``s3enc_create_ssast``)."""
+    if cfg.family != "ssast":
+        raise S3EncError("make_ssast_config needs an ssast configuration")
+    c = S3SsastConfig()
+    c.fshape, c.tshape, c.fstride, c.tstride = int(cfg.ss_fshape), int(cfg.ss_tshape), int(cfg.ss_fstride), int(cfg.ss_tstride)
+    c.window_samples, c.target_length = int(cfg.ss_window_samples), int(cfg.ss_target_length)
+    c.ln_eps, c.pos_rows = float(cfg.ss_ln_eps), int(cfg.ss_f_dim * cfg.ss_t_dim)
+    return c
+
+
 class BlockFamily(NamedTuple):
     """A family whose handle takes a second configuration block through a create entry of its own (csrc: its FamilyOps record)."""
     block: type                  # the ctypes struct of the block
@@ -543,6 +561,7 @@ BLOCK_FAMILIES = {
     "byol_a": BlockFamily(S3ByolAConfig, make_byol_a_config, "s3enc_create_byol_a", "BYOL-A is"),
     "mae_ast": BlockFamily(S3MaeAstConfig, make_mae_ast_config, "s3enc_create_mae_ast", "MAE-AST is", reads_weights=True),
     "byol_s": BlockFamily(S3ByolSConfig, make_byol_s_config, "s3enc_create_byol_s", "BYOL-S is"),
+    "ssast": BlockFamily(S3SsastConfig, make_ssast_config, "s3enc_create_ssast", "SSAST is"),
 }
 assert set(BLOCK_FAMILIES) <= set(FAMILY)
 _PROTOS.update({f.create: (C.c_int, [C.POINTER(S3Config), C.POINTER(f.block), C.POINTER(S3Tensor), _I32, _I32, C.POINTER(_VP)])

@@ -267,6 +267,135 @@ def mae_ast_cfg_blocks(cfg: EncoderConfig) -> Dict:
     return dict(model=model, task=task)
 
 
+# what an SSAST file holds and the upstream never reads (ast_models.py:96-208, 381-398): v.norm reaches no returned state, the heads and
+# the pretext layers are training state
+SSAST_UNUSED = ("module.v.norm.", "module.v.head.", "module.v.head_dist.", "module.cpredlayer.", "module.gpredlayer.", "module.mask_embed")
+
+
+def ssast_bilinear(x: np.ndarray, Ho: int, Wo: int) -> np.ndarray:
+    """``F.interpolate(x, size=(Ho, Wo), mode="bilinear")`` (align_corners=False) of a (C, H, W) array, in float64: source coordinate
+    (i + 0.5) * in / out - 0.5 clamped at 0, the two neighbours with the upper one clamped to the last index."""
+    x = np.asarray(x, np.float64)
+    _, H, W = x.shape
+
+    def axis(n_in, n_out):
+        src = np.maximum((np.arange(n_out) + 0.5) * (n_in / n_out) - 0.5, 0.0)
+        i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+        i1 = np.minimum(i0 + 1, n_in - 1)
+        return i0, i1, src - i0
+
+    h0, h1, lh = axis(H, Ho)
+    w0, w1, lw = axis(W, Wo)
+    top = x[:, h0][:, :, w0] * (1.0 - lw) + x[:, h0][:, :, w1] * lw
+    bot = x[:, h1][:, :, w0] * (1.0 - lw) + x[:, h1][:, :, w1] * lw
+    return top * (1.0 - lh)[None, :, None] + bot * lh[None, :, None]
+
+
+def ssast_position_rows(pos_patch: np.ndarray, p_f_dim: int, p_t_dim: int, f_dim: int, t_dim: int) -> np.ndarray:
+    """The patch tokens' position rows for an (f_dim, t_dim) grid out of the pretraining table (p_f_dim * p_t_dim, D), by the
+    reference's rule (ast_models.py:303-342): time — a centre cut when t_dim < p_t_dim, else a bilinear interpolation to (8, t_dim);
+    frequency — a bilinear interpolation to (f_dim, t_dim).  The reference's other frequency branch (f_dim < p_f_dim) slices with
+    ``+ t_dim`` and is refused.  Returns (f_dim * t_dim, D) float64 in the reference's f-major token order."""
+    pos_patch = np.asarray(pos_patch, np.float64)
+    P, D = pos_patch.shape
+    if P != p_f_dim * p_t_dim:
+        raise ValueError(f"ssast position table has {P} patch rows, the pretraining grid is {p_f_dim} x {p_t_dim}")
+    if f_dim < p_f_dim:
+        raise ValueError(f"ssast f_dim {f_dim} < p_f_dim {p_f_dim}: the reference's frequency cut of the position rows slices with "
+                         "t_dim (ast_models.py:325-334) and is reached by neither released model; it is not built")
+    g = pos_patch.T.reshape(D, p_f_dim, p_t_dim)
+    if t_dim < p_t_dim:
+        lo = int(p_t_dim / 2) - int(t_dim / 2)
+        g = g[:, :, lo:lo + t_dim]
+    else:
+        g = ssast_bilinear(g, 8, t_dim)
+    g = ssast_bilinear(g, f_dim, t_dim)
+    return g.reshape(D, f_dim * t_dim).T
+
+
+def ssast_hot_path(what: str, cfg: EncoderConfig, sd) -> Dict[str, np.ndarray]:
+    """The tensors an SSAST handle reads (include/s3enc.h: s3enc_ssast_config), out of the released ``module.v.*`` state dict — or an
+    already prepared set, which passes through.  ``patch.weight``: the conv weight summed over its input channel (ast_models.py:297-299)
+    and permuted to [n][t][f]; ``prefix``: cls_token + pos_embed[0], dist_token + pos_embed[1]; ``pos``: the patch tokens' rows by
+    ``ssast_position_rows``, permuted to the handle's time-major token order (row ti * f_dim + fi); the blocks as stored.  The keys
+    of ``SSAST_UNUSED`` are ignored, any other unknown key fails."""
+    if "patch.weight" in sd:
+        return {k: (v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, np.float32)) for k, v in sd.items()}
+    arr = lambda w: w.detach().cpu().double().numpy() if hasattr(w, "detach") else np.asarray(w, dtype=np.float64)
+    D, F = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim
+    need = {"module.v.cls_token": (1, 1, D), "module.v.dist_token": (1, 1, D), "module.v.patch_embed.proj.bias": (D,)}
+    for l in range(cfg.encoder_layers):
+        for name, shape in (("norm1", (D,)), ("attn.qkv", (3 * D, D)), ("attn.proj", (D, D)), ("norm2", (D,)), ("mlp.fc1", (F, D)),
+                            ("mlp.fc2", (D, F))):
+            need[f"module.v.blocks.{l}.{name}.weight"], need[f"module.v.blocks.{l}.{name}.bias"] = shape, shape[:1]
+    free = ("module.v.pos_embed", "module.v.patch_embed.proj.weight", "module.p_input_fdim", "module.p_input_tdim")
+    for k in sd:
+        if k not in need and k not in free and not k.startswith(SSAST_UNUSED):
+            raise ValueError(f"{what}: unexpected parameter {k} (not a tensor of an SSAST model with this configuration)")
+    for k in list(need) + list(free):
+        if k not in sd:
+            raise ValueError(f"{what}: missing parameter {k}")
+    for k, shape in need.items():
+        if tuple(np.shape(sd[k])) != tuple(shape):
+            raise ValueError(f"{what}: parameter {k} has shape {tuple(np.shape(sd[k]))}, expected {tuple(shape)}")
+    p_fdim, p_tdim = int(arr(sd["module.p_input_fdim"]).reshape(-1)[0]), int(arr(sd["module.p_input_tdim"]).reshape(-1)[0])
+    if (p_fdim, p_tdim) != (cfg.ss_p_input_fdim, cfg.ss_p_input_tdim):
+        raise ValueError(f"{what}: pretraining input size {(p_fdim, p_tdim)}, the configuration says "
+                         f"{(cfg.ss_p_input_fdim, cfg.ss_p_input_tdim)}")
+    cw = arr(sd["module.v.patch_embed.proj.weight"])
+    if cw.ndim != 4 or cw.shape[0] != D or cw.shape[2:] != (cfg.ss_fshape, cfg.ss_tshape):
+        raise ValueError(f"{what}: parameter module.v.patch_embed.proj.weight has shape {tuple(cw.shape)}, expected "
+                         f"{(D, 1, cfg.ss_fshape, cfg.ss_tshape)}")
+    pf, pt = cfg.ss_pretrain_grid
+    pe = arr(sd["module.v.pos_embed"])
+    if pe.shape != (1, pf * pt + 2, D):
+        raise ValueError(f"{what}: parameter module.v.pos_embed has shape {tuple(pe.shape)}, expected {(1, pf * pt + 2, D)}")
+    f_dim, t_dim = cfg.ss_f_dim, cfg.ss_t_dim
+    rows = ssast_position_rows(pe[0, 2:], pf, pt, f_dim, t_dim)  # f-major: row fi * t_dim + ti
+    out = {
+        "patch.weight": cw.sum(1).transpose(0, 2, 1).reshape(D, cfg.ss_tshape * cfg.ss_fshape),  # [n][f][t] -> [n][t][f]
+        "patch.bias": arr(sd["module.v.patch_embed.proj.bias"]),
+        "prefix": np.stack([arr(sd["module.v.cls_token"]).reshape(D) + pe[0, 0], arr(sd["module.v.dist_token"]).reshape(D) + pe[0, 1]]),
+        "pos": rows.reshape(f_dim, t_dim, D).transpose(1, 0, 2).reshape(t_dim * f_dim, D),
+    }
+    for k in need:
+        if k.startswith("module.v.blocks."):
+            out[k[len("module.v."):]] = arr(sd[k])
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+
+
+def load_ssast_checkpoint(ckpt, model_size: str = "base_p", window_secs: float = 1.0) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
+    """An SSAST pretraining file (ast_models.py:217-251: ``torch.load`` of a PLAIN state dict with ``module.`` keys) or the dict it
+    holds.  The file carries no configuration beyond its shapes and the two ``p_input_*`` scalars: ``model_size`` is the reference's
+    "<size>_<p|f>" and ``window_secs`` its constructor argument.  Returns the configuration and the RELEASED-layout tensors the
+    forward needs (``ssast_hot_path`` prepares them for the handle)."""
+    from .config import SSAST_SIZES, ssast_config
+
+    what = ckpt if isinstance(ckpt, str) else "the SSAST checkpoint"
+    if not isinstance(ckpt, dict):
+        import torch
+
+        ckpt = torch.load(ckpt, map_location="cpu", weights_only=False)
+    size, _, mtype = str(model_size).partition("_")
+    if size not in SSAST_SIZES or mtype not in ("p", "f"):
+        raise ValueError(f"ssast model_size must be '<tiny|small|base>_<p|f>', got {model_size!r}")
+    for k in ("module.v.pos_embed", "module.p_input_fdim", "module.p_input_tdim"):
+        if k not in ckpt:
+            raise ValueError(f"{what} is not a valid checkpoint since the required key: {k} is missing (the reference asks for a "
+                             "model saved from a torch.nn.DataParallel object)")
+    num = lambda w: int(w.reshape(-1)[0]) if hasattr(w, "reshape") else int(w)
+    D = int(np.shape(ckpt["module.v.pos_embed"])[2])
+    layers = 1 + max(int(k.split(".")[3]) for k in ckpt if k.startswith("module.v.blocks."))
+    ffn = int(np.shape(ckpt["module.v.blocks.0.mlp.fc1.weight"])[0])
+    if D != SSAST_SIZES[size][0]:
+        raise ValueError(f"{what}: the file is {D} wide, model size {size!r} is {SSAST_SIZES[size][0]} wide")
+    cfg = ssast_config(model_type=mtype, model_size=size, window_secs=window_secs, layers=layers, ffn=ffn,
+                       p_input_fdim=num(ckpt["module.p_input_fdim"]), p_input_tdim=num(ckpt["module.p_input_tdim"]))
+    keep = {k: v for k, v in ckpt.items() if not k.startswith(SSAST_UNUSED)}
+    ssast_hot_path(what, cfg, keep)  # every check of the file happens at load time
+    return cfg, {k: (v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, np.float32)) for k, v in keep.items()}
+
+
 def load_byol_s_checkpoint(ckpt, model_name: str = None, window_secs: float = 1, hop_secs: float = 0.05, blocks=None
                            ) -> Tuple[EncoderConfig, Dict[str, np.ndarray]]:
     """A BYOL-S weight file (upstream/byol_s/serab_byols/serab.py:74-103: ``model.load_state_dict(torch.load(path))``, a PLAIN
@@ -540,6 +669,8 @@ def load_checkpoint(ckpt: str, family: str) -> Tuple[EncoderConfig, Dict[str, np
         return load_lighthubert_checkpoint(ckpt)
     if family == "decoar2":
         return load_decoar2_checkpoint(ckpt)
+    if family == "ssast":
+        return load_ssast_checkpoint(ckpt)
 
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     if family == "wav2vec" and "model_cfg" not in state and "model" in state and ("cfg" in state or "args" in state):
@@ -598,6 +729,12 @@ def save_checkpoint(path: str, cfg: EncoderConfig, weights: Dict[str, np.ndarray
         if "batch_norm.num_batches_tracked" in sd:
             sd["batch_norm.num_batches_tracked"] = sd["batch_norm.num_batches_tracked"].to(torch.int64).reshape(())
         torch.save({"cfg": mae_ast_cfg_blocks(cfg), "model": sd}, path)
+        return
+    if cfg.family == "ssast":  # upstream/ssast/ast_models.py:217-227: a plain state dict, the two input sizes as scalar tensors
+        for k in ("module.p_input_fdim", "module.p_input_tdim"):
+            if k in sd:
+                sd[k] = sd[k].to(torch.int64).reshape(())
+        torch.save(sd, path)
         return
     if cfg.family == "lighthubert":  # upstream/lighthubert/expert.py:17-21: the SUPERNET state dict beside cfg.model
         torch.save({"cfg": {"model": lighthubert_model_cfg(cfg)}, "model": sd}, path)

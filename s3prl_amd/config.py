@@ -17,7 +17,7 @@ import ast
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast", "byol_s", "lighthubert", "decoar2")
+FAMILIES = ("hubert", "wav2vec2", "wavlm", "distiller", "multires_hubert", "wav2vec", "cpc", "apc", "mockingjay", "decoar", "npc", "vggish", "byol_a", "mae_ast", "byol_s", "lighthubert", "decoar2", "ssast")
 
 # reference default: "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"
@@ -248,6 +248,19 @@ class EncoderConfig:
     bs_hop_secs: float = 0.05
     bs_bn_eps: float = 1e-5           # nn.BatchNorm2d's default
 
+    # SSAST (family "ssast", upstream/ssast/{expert,ast_models,audio}.py): fixed windows of ``ss_window_secs``, per window a hanning
+    # kaldi log-mel at 128 bins with an affine normalisation, zero rows up to ``ss_target_length``, a Conv2d patch embedding with
+    # overlapping patches behind a cls and a dist token, ``encoder_layers`` pre-LN timm blocks.  ``conv_layers`` = [(D, 400, 160)]
+    # carries the frame geometry; the states are ``encoder_layers`` x (B, T_out, f_dim * D)
+    ss_fshape: int = 16               # patch extent in mel bins (frame model: 128)
+    ss_tshape: int = 16               # patch extent in frames (frame model: 2)
+    ss_fstride: int = 10              # (frame model: 128)
+    ss_tstride: int = 10              # (frame model: 1)
+    ss_window_secs: float = 1.0       # the expert's constructor argument as given; the samples are int(secs * 16000)
+    ss_ln_eps: float = 1e-6           # timm 0.4.5 VisionTransformer: partial(nn.LayerNorm, eps=1e-6)
+    ss_p_input_fdim: int = 128        # module.p_input_fdim / p_input_tdim of the pretraining file: the grid its pos_embed was made for
+    ss_p_input_tdim: int = 1024
+
     # ---- derived -------------------------------------------------------------------------
     @property
     def conv_dim(self) -> int:
@@ -269,7 +282,38 @@ class EncoderConfig:
             return sum(n + 1 for n in self.block_layers)
         if self.family == "mae_ast":  # the layer outputs; the embedding is not among them (mae_ast.py:671-677)
             return self.encoder_layers
+        if self.family == "ssast":  # the blocks' outputs (ast_models.py:381-393)
+            return self.encoder_layers
         return self.encoder_layers + 1 + self.pred_heads
+
+    # ---- SSAST geometry (ssast/expert.py:44-78, ast_models.py:354-365) ----------------------
+    @property
+    def ss_window_samples(self) -> int:
+        return int(self.ss_window_secs * 16000)
+
+    @property
+    def ss_target_length(self) -> int:
+        return int(self.ss_window_secs * 16000 / 160)
+
+    @property
+    def ss_f_dim(self) -> int:
+        return (128 - self.ss_fshape) // self.ss_fstride + 1
+
+    @property
+    def ss_t_dim(self) -> int:
+        return (self.ss_target_length - self.ss_tshape) // self.ss_tstride + 1
+
+    @property
+    def ss_pretrain_grid(self) -> Tuple[int, int]:
+        """(p_f_dim, p_t_dim): the patch grid of the pretraining stage, where stride = shape (ast_models.py:236-249)."""
+        return self.ss_p_input_fdim // self.ss_fshape, self.ss_p_input_tdim // self.ss_tshape
+
+    def ss_num_windows(self, n: int) -> int:
+        return -(-n // self.ss_window_samples) if n > 0 else 0
+
+    def ss_num_steps(self, n: int) -> int:
+        """T_out: nseg * t_dim rows cut to len(range(0, max_len, 160 * tstride)) (ssast/expert.py:127-131)."""
+        return min(self.ss_num_windows(n) * self.ss_t_dim, -(-n // (160 * self.ss_tstride))) if n > 0 else 0
 
     @property
     def downsample_rate(self) -> int:
@@ -277,6 +321,8 @@ class EncoderConfig:
             return 16000
         if self.family == "mae_ast":  # mae_ast/expert.py:57-58
             return self.ma_kt * 160
+        if self.family == "ssast":  # ssast/expert.py:82-83
+            return self.ss_tstride * 160
         r = 1
         for _, _, s in self.conv_layers:
             r *= s
@@ -300,6 +346,8 @@ class EncoderConfig:
             return -(-self.conv_lengths(n)[-1] // 2)
         if self.family == "mae_ast":  # time steps of kt frames; the frames behind the last whole step are dropped by nn.Unfold
             return self.conv_lengths(n)[-1] // self.ma_kt
+        if self.family == "ssast":
+            return self.ss_num_steps(n)
         if self.family == "byol_s":  # windows: frame_audio's loop (byol_s/serab_byols/utils.py:79-96)
             return n // self.conv_layers[0][2] + 1 if n >= 0 else 0
         if self.family == "byol_a":  # segments: len(range(0, n, stride)) (byol_a/expert.py:85)
@@ -322,6 +370,8 @@ class EncoderConfig:
             return 0
         if self.family == "mae_ast":  # forward_padding_mask (mae_ast.py:305-325): a step that is only partly real counts as real
             return min(T, max(-(-self.conv_lengths(length)[-1] // self.ma_kt), 0))
+        if self.family == "ssast":  # the wrapper's rule at the expert's rate; the rows behind it are the reference's values, not zeros
+            return min(T, max(-(-length // self.downsample_rate), 0))
         if self.family == "mockingjay" and self.mj_frontend == "mel":
             # preprocessor.py:204-205: batch-dependent, Python floats and Python's round; without CMVN no feature row is zero
             return min(T, max(round(length / (n_max / T)), 0)) if self.mj_cmvn else T
@@ -444,6 +494,8 @@ class EncoderConfig:
             return self._validate_mae_ast()
         if self.family == "byol_s":
             return self._validate_byol_s()
+        if self.family == "ssast":
+            return self._validate_ssast()
         if self.layer_type not in ("transformer", "conformer"):
             raise ValueError(f"unknown layer_type {self.layer_type!r}")
         if self.family == "lighthubert":
@@ -736,6 +788,45 @@ class EncoderConfig:
         """``kv_b = min(ceil(F_b / kt) * V, Ttok)`` of a batch (forward_padding_mask, mae_ast.py:305-325)."""
         V, Ttok = self.ma_tokens_per_step, self.num_frames(max(lengths)) * self.ma_tokens_per_step
         return [min(-(-self.conv_lengths(n)[-1] // self.ma_kt) * V, Ttok) for n in lengths]
+
+    def _validate_ssast(self) -> None:
+        """What the HIP path builds of SSAST; everything else is refused by name (s3enc_create_ssast repeats what it can see)."""
+        D, H = self.encoder_embed_dim, self.encoder_attention_heads
+        if not self.layer_norm_first:
+            raise ValueError("ssast blocks are pre-LN (layer_norm_first must be True)")
+        if H < 1 or D != 64 * H:
+            raise ValueError(f"ssast embed_dim / heads must be 64 (the attention kernel's head width), got {D} / {H}")
+        if self.encoder_layers < 1:
+            raise ValueError("ssast encoder_layers must be positive")
+        if self.encoder_ffn_embed_dim < 4 or self.encoder_ffn_embed_dim % 4:
+            raise ValueError("ssast ffn dim must be a multiple of 4")
+        if self.ss_fshape not in (16, 32, 64, 128):
+            raise ValueError(f"ssast fshape must be 16, 32, 64 or 128 (the strided patch kernel's set), got {self.ss_fshape}")
+        if not 1 <= self.ss_tshape <= 32:
+            raise ValueError(f"ssast tshape must be 1..32 (the strided patch kernel's set), got {self.ss_tshape}")
+        if self.ss_fstride < 2 or self.ss_fstride % 2 or self.ss_fstride > 128:
+            raise ValueError(f"ssast fstride must be even, 2..128 (a patch row starts 8-byte aligned), got {self.ss_fstride}")
+        if self.ss_tstride < 1:
+            raise ValueError("ssast tstride must be positive")
+        W = self.ss_window_samples
+        if W < 400 or W % 4:
+            raise ValueError(f"ssast window_secs={self.ss_window_secs!r} gives {W} samples: a window must be a multiple of 4 samples "
+                             "and hold at least one 400-sample analysis window")
+        if self.ss_target_length < self.ss_tshape:
+            raise ValueError(f"ssast window_secs={self.ss_window_secs!r} gives {self.ss_target_length} image rows, fewer than one patch "
+                             f"of {self.ss_tshape} frames")
+        if self.ss_f_dim * self.ss_t_dim + 2 > 8192:
+            raise ValueError("ssast windows of more than 8192 tokens are not built")
+        pf, pt = self.ss_pretrain_grid
+        if pf < 1 or pt < 1:
+            raise ValueError("ssast p_input_fdim / p_input_tdim are smaller than one patch")
+        if self.ss_f_dim < pf:
+            raise ValueError(f"ssast f_dim {self.ss_f_dim} < p_f_dim {pf}: the reference's frequency cut of the position rows slices with "
+                             "t_dim (ast_models.py:325-334) and is reached by neither released model; it is not built")
+        if not self.ss_ln_eps > 0:
+            raise ValueError("ssast ln_eps must be positive")
+        if list(self.conv_layers) != [(D, 400, 160)]:
+            raise ValueError("ssast: conv_layers carries the frame geometry as one (D, 400, 160) entry (ssast_config sets it)")
 
     def _validate_mae_ast(self) -> None:
         """What the HIP path builds of MAE-AST; everything else is refused by name (s3enc_create_mae_ast repeats what it can see)."""
@@ -1179,6 +1270,30 @@ def mae_ast_config(kt: int = 16, kc: int = 16, embed_dim: int = 768, layers: int
                         ma_stride_t=int(kt if stride_t is None else stride_t), ma_stride_c=int(kc if stride_c is None else stride_c),
                         ma_feature_dim=int(feature_dim), ma_sample_rate=int(sample_rate), ma_max_token_length=int(max_token_length),
                         **flags)
+    cfg.validate()
+    return cfg
+
+
+SSAST_SIZES = {"tiny": (192, 3), "small": (384, 6), "base": (768, 12)}  # timm's deit_{tiny,small,base}_distilled_patch16: D, heads
+SSAST_TYPES = {"p": (16, 16, 10, 10), "f": (128, 2, 128, 1)}            # fshape, tshape, fstride, tstride (ssast/expert.py:51-78)
+
+
+def ssast_config(model_type: str = "p", model_size: str = "base", window_secs: float = 1.0, embed_dim: int = None, heads: int = None,
+                 layers: int = 12, ffn: int = None, p_input_fdim: int = 128, p_input_tdim: int = 1024, **flags) -> EncoderConfig:
+    """An :class:`EncoderConfig` of family "ssast": ``model_type`` "p" (patch) or "f" (frame), ``model_size`` of SSAST_SIZES (or
+    ``embed_dim`` / ``heads`` given), ``window_secs`` the expert's constructor argument.  The defaults are ``ssast_patch_base``."""
+    if model_type not in SSAST_TYPES:
+        raise ValueError(f"ssast model type must be 'p' or 'f', got {model_type!r}")
+    if embed_dim is None:
+        if model_size not in SSAST_SIZES:
+            raise ValueError(f"ssast model size must be one of {sorted(SSAST_SIZES)}, got {model_size!r}")
+        embed_dim, heads = SSAST_SIZES[model_size]
+    fshape, tshape, fstride, tstride = SSAST_TYPES[model_type]
+    cfg = EncoderConfig(family="ssast", conv_layers=[(int(embed_dim), 400, 160)], encoder_layers=int(layers),
+                        encoder_embed_dim=int(embed_dim), encoder_ffn_embed_dim=int(4 * embed_dim if ffn is None else ffn),
+                        encoder_attention_heads=int(heads), layer_norm_first=True, ss_fshape=fshape, ss_tshape=tshape,
+                        ss_fstride=fstride, ss_tstride=tstride, ss_window_secs=float(window_secs), ss_p_input_fdim=int(p_input_fdim),
+                        ss_p_input_tdim=int(p_input_tdim), **flags)
     cfg.validate()
     return cfg
 

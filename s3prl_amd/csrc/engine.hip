@@ -143,7 +143,8 @@ namespace {
 // The families that come with a second configuration block (FamilyOps, engine_internal.h), in the order their entries were added:
 // the one list of them the engine has.
 const FamilyOps* const kFamilies[] = {&kWav2vecFamily, &kCpcFamily,    &kApcFamily,   &kMockingjayFamily, &kDecoarFamily,
-                                      &kNpcFamily,     &kVggishFamily, &kByolAFamily, &kMaeAstFamily,     &kByolSFamily};
+                                      &kNpcFamily,     &kVggishFamily, &kByolAFamily, &kMaeAstFamily,     &kByolSFamily,
+                                      &kSsastFamily};
 // DeCoAR 2.0's front end, the family's own constants (decoar2/audio.py:8-9,70-76, kaldi.fbank's defaults; CMVN eps :16)
 s3::FbankParams decoar2_fbank_params() {
     s3::FbankParams f;
@@ -190,7 +191,7 @@ void build_rel_table(const s3enc_config& c, const std::vector<float>& emb, int R
 }
 
 int check_config(const s3enc_config& c) {
-    if (c.family < 0 || c.family > S3ENC_DECOAR2) return fail("config: unknown family");
+    if (c.family < 0 || c.family > S3ENC_SSAST || c.family == S3ENC_DECOAR2 + 1) return fail("config: unknown family");  // (17 is not assigned)
     if (family_ops(c.family)) return 0;  // its record's own check runs on both configuration blocks (create_impl)
     if (c.family == S3ENC_MULTIRES) {
         if (c.mr_pairs < 1 || c.mr_pairs > S3ENC_MAX_RES - 1) return fail("config: mr_pairs out of range");
@@ -359,6 +360,10 @@ int s3enc_create_mae_ast(const s3enc_config* cfg, const s3enc_mae_ast_config* ma
 int s3enc_create_byol_s(const s3enc_config* cfg, const s3enc_byol_s_config* byol_s, const s3enc_tensor* tensors, int32_t n_tensors,
                         int32_t device, s3enc_handle* out) {
     return create_family(kByolSFamily, cfg, byol_s, tensors, n_tensors, device, out);
+}
+int s3enc_create_ssast(const s3enc_config* cfg, const s3enc_ssast_config* ssast, const s3enc_tensor* tensors, int32_t n_tensors,
+                       int32_t device, s3enc_handle* out) {
+    return create_family(kSsastFamily, cfg, ssast, tensors, n_tensors, device, out);
 }
 
 static int create_impl(const s3enc_config* cfg, int own, const void* block, const s3enc_tensor* tensors, int32_t n_tensors, int32_t device,

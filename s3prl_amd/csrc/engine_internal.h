@@ -16,6 +16,8 @@
 //   mae_ast.hip MAE-AST: per-utterance kaldi fbank, the fused patch embedding (patchembed.hip), pre- / post-LN layers of transformer.hip
 //   byol_s.hip  BYOL-S: centred windows -> hann(400) FFT log-mel -> whole-batch statistics -> ResNet on stem.hip + conv2d.hip (or BYOL-A's
 //               network) -> max + mean, the windows in chunks
+//   ssast.hip   SSAST: fixed windows -> window-wise hanning kaldi fbank -> the strided patch embedding (patchstrided.hip) -> timm pre-LN
+//               blocks of transformer.hip at eps 1e-6 -> a compacting emit per layer, the windows in chunks
 //   (a family file holds its configuration check, its weights, its forward schedule and its shape rules, and hands them to the engine
 //   as one FamilyOps record: nothing of the plumbing above)
 //   ops.hip       single-kernel entry points (s3enc_op_*), the weighted sum, fbank, tuning keys
@@ -495,6 +497,13 @@ struct MaeAstW {
     std::vector<LayerW> layers;
 };
 
+// SSAST (ssast.hip): the patch conv as (D, tshape * fshape) in [n][t][f] order with its bias, the two prefix rows (cls_token + pos[0],
+// dist_token + pos[1]), the patch tokens' position rows in the time-major order and the timm blocks
+struct SsastW {
+    DevBuf pw, pb, prefix, pos;
+    std::vector<LayerW> layers;
+};
+
 struct ProfRec {
     int kind;
     hipEvent_t a, b;
@@ -570,6 +579,8 @@ struct s3enc_encoder {
     s3enc_mae_ast_config mae_ast_cfg = {};  // ... and its second configuration block (s3enc_create_mae_ast)
     std::unique_ptr<ByolSW> byol_s;     // S3ENC_BYOL_S
     s3enc_byol_s_config byol_s_cfg = {};  // ... and its second configuration block (s3enc_create_byol_s)
+    std::unique_ptr<SsastW> ssast;      // S3ENC_SSAST
+    s3enc_ssast_config ssast_cfg = {};  // ... and its second configuration block (s3enc_create_ssast)
     const FamilyOps* ops = nullptr;     // the record of a family with a second configuration block (set at create time)
     float* aux_codewords = nullptr;     // s3enc_forward_aux: where the running forward writes the quantizer's outputs
     long long* aux_codeids = nullptr;
@@ -834,8 +845,9 @@ hipError_t upload_gemm_w_mx(s3enc_encoder* e, DevBuf& buf, const std::vector<flo
 // the tensor names of a layer under its prefix: fairseq's TransformerSentenceEncoderLayer, BERT's (Mockingjay)
 struct LayerNames {
     const char *qkv[3], *out, *ln1, *fc1, *fc2, *ln2;
+    const char* qkv_fused = nullptr;  // set: ONE (3 D, D) tensor with rows q | k | v under this name (timm's attn.qkv); qkv[] is not read
 };
-extern const LayerNames kFairseqLayer, kBertLayer;
+extern const LayerNames kFairseqLayer, kBertLayer, kTimmLayer;
 // the layer named `prefix` (ending in '.') in the handle's operand mode, the q rows and bias times `qscale`; gate: WavLM's grep tensors too
 int load_layer(s3enc_encoder* e, const Ckpt& ck, const std::string& prefix, const LayerNames& n, float qscale, bool gate, LayerW& L);
 
@@ -864,6 +876,8 @@ struct LayerRun {
     std::function<int()> ffn_exported;
     bool allow_ln1_fold = false;  // post-LN 16-bit: fc2's epilogue rebuilds LayerNorm 1's output where its shape class can (tuning key ln1_fold)
     bool ln1_inplace = false;     // post-LN: LayerNorm 1 overwrites tmp1 instead of writing tmp2 (tuning key ws_inplace)
+    float ln_eps = 0.f;           // 0: the LayerNorms at the engine's LN_EPS (launch_layernorm); > 0: at this eps through launch_layernorm_eps
+                                  // (fp32 handles, pre-LN, no fused Featurizer term / gate / row statistics)
     bool taps = false;            // keep the debug taps qkv0 / attn0
     int stop_after = 0;           // S3ENC_DEBUG_STOP 30..34: return LAYER_STOPPED behind q|k|v, attention, out_proj, LayerNorm 1 / 2, fc1
 };
@@ -927,7 +941,7 @@ struct FamilyOps {
 // (read-only, but not declared const: the compiler would emit a constant-initialised const object into the device code as well, where
 // the host functions it points to do not exist)
 extern FamilyOps kWav2vecFamily, kCpcFamily, kApcFamily, kMockingjayFamily, kDecoarFamily, kNpcFamily, kVggishFamily, kByolAFamily,
-    kMaeAstFamily, kByolSFamily;
+    kMaeAstFamily, kByolSFamily, kSsastFamily;
 
 // byol_a.hip, for byol_s.hip: AudioNTT2020's weights, its workspace (taken from `wb`; fails when a layer is not addressable with 32-bit
 // offsets), the network on nseg bordered (T + 2) x (64 + 2) images up to dst (nseg, D), and out = max_t relu(y) + mean_t relu(y)

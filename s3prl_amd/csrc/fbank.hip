@@ -74,8 +74,9 @@ hipError_t build_plan(FbankPlan& pl, int nmel, int size, int shift, double preem
     for (int i = 0; i < N; ++i)
         for (int j = 0; j < N; ++j) tmp[(size_t)i * N + j] = (i == j ? 1.0 : 0.0) - 1.0 / N;  // C
     for (int i = 0; i < N; ++i) {
-        const double w = window == 1 ? 0.54 - 0.46 * std::cos(2.0 * M_PI * i / (N - 1))             // hamming
-                                     : std::pow(0.5 - 0.5 * std::cos(2.0 * M_PI * i / (N - 1)), 0.85);  // povey
+        const double w = window == 1   ? 0.54 - 0.46 * std::cos(2.0 * M_PI * i / (N - 1))             // hamming
+                         : window == 2 ? 0.5 - 0.5 * std::cos(2.0 * M_PI * i / (N - 1))               // hanning
+                                       : std::pow(0.5 - 0.5 * std::cos(2.0 * M_PI * i / (N - 1)), 0.85);  // povey
         const int ip = i == 0 ? 0 : i - 1;
         for (int j = 0; j < N; ++j) D[(size_t)i * N + j] = w * (tmp[(size_t)i * N + j] - preemph * tmp[(size_t)ip * N + j]);
     }
@@ -95,7 +96,7 @@ hipError_t plan_for(const FbankParams& c, int dev, int size, int shift, FbankPla
 
 hipError_t fbank_operand(const FbankParams& c, FbankOperand* op) {
     const int size = (int)(c.sample_rate * c.frame_length_ms * 0.001), shift = (int)(c.sample_rate * c.frame_shift_ms * 0.001);
-    if (size <= 0 || shift <= 0 || (size & 3) || (shift & 3) || c.num_mel_bins <= 0 || c.window < 0 || c.window > 1)
+    if (size <= 0 || shift <= 0 || (size & 3) || (shift & 3) || c.num_mel_bins <= 0 || c.window < 0 || c.window > 2)
         return hipErrorInvalidValue;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -126,7 +127,7 @@ hipError_t launch_fbank(const FbankParams& c, const float* wav, long n, float* o
     const long T = fbank_num_frames(n, c);
     if (T <= 0) return hipSuccess;
     if (size <= 0 || shift <= 0 || (size & 3) || (shift & 3) || c.num_mel_bins <= 0 || c.delta_order < 0 || c.delta_order > 2 ||
-        c.window < 0 || c.window > 1)
+        c.window < 0 || c.window > 2)
         return hipErrorInvalidValue;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -246,6 +247,61 @@ hipError_t launch_fbank_batch(const FbankParams& c, const float* pcm, long row_s
                            Fmax * (long)ldo, (long)ldo, nullptr);
     }
     launch_cmvn(out, frames, (int)Fmax, pl.nmel, B, ldo, Fmax * (long)ldo, c.cmvn_eps, st);
+    return hipGetLastError();
+}
+
+// ---- the window-wise pass -----------------------------------------------------------------------------------------------------------
+namespace {
+struct LogFloorAffine {  // SSAST: (log(max(e, eps)) + add) / div, an fp32 add followed by an fp32 divide
+    float eps, add, div;
+    __device__ float operator()(float acc) const {
+#pragma clang fp contract(off)
+        return (logf(fmaxf(acc, eps)) + add) / div;
+    }
+};
+}  // namespace
+
+hipError_t launch_fbank_windows(const FbankParams& c, const float* pcm, long row_stride, int nwin, long F, float add, float div, float* out,
+                                long out_bs, int ldo, float* spec, size_t spec_bytes, size_t cap_bytes, hipStream_t st) {
+    const int size = (int)(c.sample_rate * c.frame_length_ms * 0.001), shift = (int)(c.sample_rate * c.frame_shift_ms * 0.001);
+    if (nwin <= 0 || F <= 0) return hipSuccess;
+    if (size <= 0 || shift <= 0 || (size & 3) || (shift & 3) || c.num_mel_bins <= 0 || c.delta_order != 0 || c.use_cmvn || c.window < 0 ||
+        c.window > 2 || (((uintptr_t)pcm) & 15) || (row_stride & 3) || row_stride < size + (F - 1) * shift || F > 0x7fffffffL ||
+        ldo < c.num_mel_bins || out_bs < F * (long)ldo || !(div != 0.f))
+        return hipErrorInvalidValue;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    FbankPlan* plan = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        e = plan_for(c, dev, size, shift, &plan);
+        if (e != hipSuccess) return e;
+    }
+    const FbankPlan& pl = *plan;  // (a plan is never rebuilt or freed: the pointer outlives the lock)
+    const int N2 = 2 * pl.nbin;
+    const int chunk = fbank_batch_chunk(nwin, F, pl.nbin, cap_bytes);
+    if (!spec || spec_bytes < (size_t)chunk * F * N2 * sizeof(float)) return hipErrorInvalidValue;
+    for (int w0 = 0; w0 < nwin; w0 += chunk) {
+        const int nb = nwin - w0 < chunk ? nwin - w0 : chunk;
+        GemmParams g{};
+        g.A = pcm + (long)w0 * row_stride;
+        g.lda = shift;  // overlapping rows: frame t of window w starts at sample w * row_stride + t * shift
+        g.a_bs = row_stride;
+        g.W = pl.dft;
+        g.M = (int)F;
+        g.N = N2;
+        g.K = size;
+        g.batches = nb;
+        g.out32 = spec;
+        g.ldo = N2;
+        g.o_bs = F * N2;
+        e = launch_gemm(F32, g, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((mel_rows_kernel<POWER, LogFloorAffine>), dim3((unsigned)((long)nb * F)), dim3(128), pl.nbin * sizeof(float), st,
+                           spec, pl.nbin, (int)F, pl.bank.bands, pl.bank.wts, pl.nmel, LogFloorAffine{FLT_EPSILON, add, div},
+                           out + (long)w0 * out_bs, out_bs, (long)ldo, nullptr);
+    }
     return hipGetLastError();
 }
 

@@ -100,6 +100,11 @@ struct Tuning {
     int patch_embed_fused = 1;  // patchembed.hip: 1 = the patch embedding as ONE implicit GEMM that reads the image in place, 0 = a gather kernel
                            // that writes the (B * tokens, kt * kc) rows, the tile GEMM, then the position add (the yardstick and a second
                            // implementation, held to the fixture bound; the A/B of profiles/mae_ast_fp32.md)
+    int patch_strided_fused = 1;  // patchstrided.hip: 1 = SSAST's overlapping patch embedding as ONE implicit GEMM that reads the image in place,
+                           // 0 = a gather kernel that writes the (windows * tokens, tshape * fshape) rows, the tile GEMM storing at the
+                           // sequence pitch, then the position add (the yardstick and a second implementation, held to the same bound)
+    int ssast_chunk = 65536;  // ssast.hip: tokens per pass of the embedding and the layers (whole windows, at least one); bounds the workspace,
+                           // never changes a row's bits
     int stem_fused = 0;    // byol_s.hip: 1 = the ResNet stem as one kernel (stem.hip: conv 7 x 7 + affine + ReLU + 3 x 3 / stride-2 pool, 2.25 x the
                            // multiply-adds, no un-pooled map), 0 = the un-pooled map and a pool kernel (bit-identical; measured 223.0
                            // against 222.2 ms per forward: profiles/byol_s_fp32.md)
@@ -321,6 +326,29 @@ hipError_t launch_patch_embed(const PatchEmbedParams& p, hipStream_t stream);
 // the two-step form: a gather into `rows` (patch_embed_rows_elems floats, 16-byte aligned), launch_gemm, the position add
 size_t patch_embed_rows_elems(const PatchEmbedParams& p);
 hipError_t launch_patch_embed_two_step(const PatchEmbedParams& p, float* rows, hipStream_t stream);
+
+// patchstrided.hip: exact-fp32 patch embedding with overlapping patches (SSAST's Conv2d(1, N, (fshape, tshape), stride (fstride,
+// tstride)) on the transpose of a (rows, 128) image) as an implicit GEMM over the tokens of all windows.  Token (ti, fi) of window w is
+// the tshape x fshape patch at image row ti * tstride, column fi * fstride, its content in (time, frequency) row-major order; it is row
+// 2 + ti * f_dim + fi of the window's sequence of 2 + f_dim * t_dim rows (time-major), behind the two prefix rows.
+struct PatchStridedParams {
+    const float* img;     // window w at img + w * img_bs: `rows` rows of 128 floats; nothing behind them is read
+    long img_bs;          // floats, a multiple of 4, at least rows * 128
+    const float* W;       // (N, tshape * fshape) row-major: the conv weight permuted to [n][t][f]
+    const float* bias;    // [N] or null
+    const float* pos;     // (f_dim * t_dim, N) in the time-major token order, or null
+    const float* prefix;  // (2, N): rows 0 and 1 of every sequence, or null (they are then left as they are)
+    int nwin, rows, fshape, tshape, fstride, tstride, N;
+    int f_dim, t_dim, sshift;  // (128 - fshape) / fstride + 1, (rows - tshape) / tstride + 1, log2(fshape / 16): patch_strided_geometry
+    float* out;           // (nwin, 2 + f_dim * t_dim, N) contiguous
+};
+void patch_strided_geometry(PatchStridedParams& p);              // f_dim / t_dim / sshift (0 where the geometry has none)
+const char* patch_strided_refusal(const PatchStridedParams& p);  // null, or why launch_patch_strided would refuse
+hipError_t launch_patch_strided(const PatchStridedParams& p, hipStream_t stream);
+hipError_t launch_patch_strided_tile(const PatchStridedParams& p, int tile_rows, hipStream_t stream);  // 64 | 128: the tile height named
+// the two-step form: a gather into `rows` (patch_strided_rows_elems floats, 16-byte aligned), launch_gemm per window, the position add
+size_t patch_strided_rows_elems(const PatchStridedParams& p);
+hipError_t launch_patch_strided_two_step(const PatchStridedParams& p, float* rows, hipStream_t stream);
 
 // ---- frontend.hip ---------------------------------------------------------------------------------------
 // Waveform table: wav b is `ptrs[b]` with `lens[b]` valid samples; reads beyond are zeros (the padding).
@@ -653,7 +681,8 @@ struct FbankParams {
     int delta_order = 2, delta_win = 5;
     int use_cmvn = 1;
     float cmvn_eps = 1e-10f;
-    int window = 0;  // 0 povey (hann ** 0.85), 1 hamming (0.54 - 0.46 cos(2 pi i / (N - 1))): kaldi's window_type
+    int window = 0;  // 0 povey (hann ** 0.85), 1 hamming (0.54 - 0.46 cos(2 pi i / (N - 1))), 2 hanning (0.5 - 0.5 cos(2 pi i / (N - 1))):
+                     // kaldi's window_type
 };
 long fbank_num_frames(long n_samples, const FbankParams& c);
 // one utterance: wav (device) -> out (device, frames x ldo), columns [0, num_mel_bins * (delta_order + 1))
@@ -668,6 +697,14 @@ int fbank_batch_chunk(int B, long Fmax, int nbin, size_t cap_bytes);
 size_t fbank_batch_workspace(const FbankParams& c, int B, long Fmax, size_t cap_bytes);
 hipError_t launch_fbank_batch(const FbankParams& c, const float* pcm, long row_stride, const int* frames, int B, long Fmax, float* out,
                               int ldo, float* spec, size_t spec_bytes, size_t cap_bytes, hipStream_t st);
+
+// The window-wise pass (delta_order 0, use_cmvn 0): `nwin` windows of one length, each its own kaldi fbank of F frames (snip_edges), in
+// one overlapping-row GEMM and one mel_rows launch whose epilogue is the affine (y + add) / div as two fp32 operations.  pcm: (nwin,
+// row_stride) device rows, 16-byte aligned, row_stride a multiple of 4 and at least size + (F - 1) * shift; out: window w's F rows at out
+// + w * out_bs + t * ldo, columns [0, nmel) — rows behind F are not touched (the caller's zeros).  spec: fbank_batch_workspace(c, nwin, F,
+// cap_bytes) bytes.  A frame's log-mel is launch_fbank's arithmetic on that window alone: the same operand, K order and band sums.
+hipError_t launch_fbank_windows(const FbankParams& c, const float* pcm, long row_stride, int nwin, long F, float add, float div, float* out,
+                                long out_bs, int ldo, float* spec, size_t spec_bytes, size_t cap_bytes, hipStream_t st);
 
 // ---- logmel.hip (OnlinePreprocessor: decibel scale, centred hann STFT on the padded batch, HTK mel, log, CMVN) --------
 long logmel_num_frames(long max_len);               // 1 + max_len / 160

@@ -29,6 +29,7 @@ int tuning_set(Tuning& t, const char* key, int value, const char** err) {
         {"rnn_split", &Tuning::rnn_split, -1, 8},           {"npc_skip_taps", &Tuning::npc_skip_taps, 0, 1},
         {"conv2d_n64", &Tuning::conv2d_n64, 0, 1},           {"melspec_fft", &Tuning::melspec_fft, 0, 1},
         {"patch_embed_fused", &Tuning::patch_embed_fused, 0, 1},
+        {"patch_strided_fused", &Tuning::patch_strided_fused, 0, 1}, {"ssast_chunk", &Tuning::ssast_chunk, 1, 1 << 22},
         {"stem_fused", &Tuning::stem_fused, 0, 1},           {"byol_s_chunk", &Tuning::byol_s_chunk, 1, 4096},
         {"gemm32_tail", &Tuning::gemm32_tail, 0, 2},         {"gemm32_tail_units", &Tuning::gemm32_tail_units, 0, 1 << 20},
     };
@@ -771,6 +772,44 @@ int s3enc_op_patch_embed(const float* img, int64_t img_bs, const float* w_host, 
     } else {
         HIP_TRY(rows.ensure(patch_embed_rows_elems(p) * 4 + 64));
         HIP_TRY(launch_patch_embed_two_step(p, (float*)rows.p, (hipStream_t)stream));
+    }
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the weights and the gathered rows are freed on return
+    return 0;
+}
+
+int s3enc_op_patch_embed_strided(const float* img, int64_t img_bs, const float* w_host, const float* bias, const float* pos,
+                                 const float* prefix, int32_t nwin, int32_t rows, int32_t fshape, int32_t tshape, int32_t fstride,
+                                 int32_t tstride, int32_t N, int32_t tile_rows, float* out, void* stream) {
+    if (!img || !w_host || !out) return fail("s3enc_op_patch_embed_strided: null argument");
+    if (nwin <= 0 || rows <= 0 || N <= 0) return fail("s3enc_op_patch_embed_strided: bad shape");
+    if (tile_rows != 0 && tile_rows != 64 && tile_rows != 128) return fail("s3enc_op_patch_embed_strided: tile_rows must be 0, 64 or 128");
+    PatchStridedParams p{};
+    p.img = img;
+    p.img_bs = img_bs;
+    p.bias = bias;
+    p.pos = pos;
+    p.prefix = prefix;
+    p.nwin = nwin;
+    p.rows = rows;
+    p.fshape = fshape;
+    p.tshape = tshape;
+    p.fstride = fstride;
+    p.tstride = tstride;
+    p.N = N;
+    p.out = out;
+    patch_strided_geometry(p);
+    alignas(16) static float stand_in[4];  // the checks that need no device memory first
+    p.W = stand_in;
+    if (const char* why = patch_strided_refusal(p)) return fail(std::string("s3enc_op_patch_embed_strided: ") + why);
+    std::vector<float> w(w_host, w_host + (size_t)N * tshape * fshape);
+    DevBuf dw, gathered;
+    HIP_TRY(upload_f32(dw, w));
+    p.W = (const float*)dw.p;
+    if (tuning().patch_strided_fused) {
+        HIP_TRY(tile_rows ? launch_patch_strided_tile(p, tile_rows, (hipStream_t)stream) : launch_patch_strided(p, (hipStream_t)stream));
+    } else {
+        HIP_TRY(gathered.ensure(patch_strided_rows_elems(p) * 4 + 64));
+        HIP_TRY(launch_patch_strided_two_step(p, (float*)gathered.p, (hipStream_t)stream));
     }
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the weights and the gathered rows are freed on return
     return 0;

@@ -56,6 +56,8 @@ const LayerNames kFairseqLayer = {{"self_attn.q_proj", "self_attn.k_proj", "self
                                   "fc1", "fc2", "final_layer_norm"};
 const LayerNames kBertLayer = {{"attention.self.query", "attention.self.key", "attention.self.value"}, "attention.output.dense",
                                "attention.output.LayerNorm", "intermediate.dense", "output.dense", "output.LayerNorm"};
+// timm's VisionTransformer Block (SSAST): one fused attn.qkv Linear, rows q | k | v
+const LayerNames kTimmLayer = {{nullptr, nullptr, nullptr}, "attn.proj", "norm1", "mlp.fc1", "mlp.fc2", "norm2", "attn.qkv"};
 
 hipError_t upload_gemm_w_mx(s3enc_encoder* e, DevBuf& buf, const std::vector<float>& v, long N, long K, int kind) {
     hipError_t err = upload_gemm_w(buf, v, N, K, e->dtype, e->x2);
@@ -77,7 +79,13 @@ int load_layer(s3enc_encoder* e, const Ckpt& ck, const std::string& p, const Lay
         UP(upload_f32(d, t));
         return 0;
     };
-    for (int s = 0; s < 3; ++s) {
+    if (n.qkv_fused) {  // q *= head_dim^-0.5 folded into the first D rows and their bias
+        GET(p + n.qkv_fused + ".weight", 3 * D * D, w);
+        GET(p + n.qkv_fused + ".bias", 3 * D, bb);
+        for (long i = 0; i < D * D; ++i) w[i] *= qscale;
+        for (long i = 0; i < D; ++i) bb[i] *= qscale;
+    }
+    for (int s = 0; s < 3 && !n.qkv_fused; ++s) {
         GET(p + n.qkv[s] + ".weight", D * D, t);
         GET(p + n.qkv[s] + ".bias", D, t2);
         const float sc = s == 0 ? qscale : 1.f;  // q *= head_dim^-0.5 folded into W_q, b_q
@@ -117,6 +125,18 @@ int encoder_layer(s3enc_encoder* e, hipStream_t st, const LayerW& Lw, const Laye
     auto ln = [&](const char* kind, int bytes, const float* x, const DevBuf& g, const DevBuf& b, float* out32, void* out16, const LnAcc& fa,
                   const LnGate& gt, float2* stats) -> hipError_t {
         Prof pr(e, st, kind, 0, gM * D * bytes);
+        if (r.ln_eps > 0.f) {  // the checkpoint's own eps: the eps-taking row LayerNorm (fp32 in, fp32 out, nothing fused)
+            if (!f32 || !prel || !out32 || out16 || fa.acc || gt.gate || stats) return hipErrorInvalidValue;
+            LnEpsParams q{};
+            q.x = x;
+            q.gamma = (const float*)g.p;
+            q.beta = (const float*)b.p;
+            q.eps = r.ln_eps;
+            q.rows = M;
+            q.C = D;
+            q.out = out32;
+            return launch_layernorm_eps(q, st);
+        }
         return launch_layernorm(dt, x, (const float*)g.p, (const float*)b.p, M, D, 0, out32, out16, st, fa, gt, stats);
     };
     const void* a_in = f32 ? (const void*)r.x : r.x16;  // operand of the q|k|v GEMM

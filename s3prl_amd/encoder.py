@@ -35,6 +35,10 @@ class HipEncoder:
             from .ckpt import mae_ast_hot_path
 
             weights = mae_ast_hot_path("the MAE-AST weights", cfg, weights)
+        if cfg.family == "ssast":  # the released module.v.* layout: cut / interpolated position rows, the permuted conv, the prefix fold
+            from .ckpt import ssast_hot_path
+
+            weights = ssast_hot_path("the SSAST weights", cfg, weights)
         if cfg.family == "lighthubert" and "encoder.pos_conv.0.weight_v" in weights:  # the supernet's state dict: cut to the subnet
             from .ckpt import lighthubert_slice
 
@@ -75,6 +79,8 @@ class HipEncoder:
         self.embed_dim = cfg.encoder_embed_dim
         if cfg.family == "mae_ast":  # a state row holds the V tokens of one time step (mae_ast/expert.py:94)
             self.embed_dim = cfg.ma_tokens_per_step * cfg.encoder_embed_dim
+        if cfg.family == "ssast":  # a state row holds the f_dim tokens of one time step (ssast/ast_models.py:385-391)
+            self.embed_dim = cfg.ss_f_dim * cfg.encoder_embed_dim
         self._forwards = 0   # forwards issued / the last one known to have been judged by check_finite (error messages name the range)
         self._checked = 0
 

@@ -31,6 +31,7 @@ from .upstream.audio_albert.hubconf import *  # noqa: F401,F403
 from .upstream.lighthubert.hubconf import *  # noqa: F401,F403
 from .upstream.log_stft.hubconf import *  # noqa: F401,F403
 from .upstream.decoar2.hubconf import *  # noqa: F401,F403
+from .upstream.ssast.hubconf import *  # noqa: F401,F403
 
 
 def options(only_registered_ckpt: bool = False):

@@ -42,6 +42,8 @@ def param_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
         return _mae_ast_shapes(cfg)
     if cfg.family == "lighthubert":
         return _lighthubert_shapes(cfg)
+    if cfg.family == "ssast":
+        return _ssast_shapes(cfg)
     s: Dict[str, tuple] = {}
     cin = 1
     d2 = cfg.family == "decoar2"  # its "conv stack" is the kaldi front end's geometry: no weights, no feature LayerNorm
@@ -324,6 +326,29 @@ def _mae_ast_shapes(cfg: EncoderConfig, full: bool = False) -> Dict[str, tuple]:
     return s
 
 
+def _ssast_shapes(cfg: EncoderConfig) -> Dict[str, tuple]:
+    """The released SSAST file's own key layout (upstream/ssast/ast_models.py:96-208: a DataParallel-wrapped pretraining ASTModel
+    around timm 0.4.5's distilled DeiT): ``module.v.*`` with the position table of the PRETRAINING grid, the pretraining input size as
+    two scalar parameters, and what the upstream never reads — ``v.norm``, the two classifier heads, ``cpredlayer``, ``gpredlayer``,
+    ``mask_embed``."""
+    D, F = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim
+    pf, pt = cfg.ss_pretrain_grid
+    s: Dict[str, tuple] = {"module.p_input_fdim": (), "module.p_input_tdim": (), "module.mask_embed": (1, 1, D),
+                           "module.v.cls_token": (1, 1, D), "module.v.dist_token": (1, 1, D), "module.v.pos_embed": (1, pf * pt + 2, D),
+                           "module.v.patch_embed.proj.weight": (D, 1, cfg.ss_fshape, cfg.ss_tshape), "module.v.patch_embed.proj.bias": (D,)}
+    for l in range(cfg.encoder_layers):
+        p = f"module.v.blocks.{l}"
+        for name, shape in (("norm1", (D,)), ("attn.qkv", (3 * D, D)), ("attn.proj", (D, D)), ("norm2", (D,)), ("mlp.fc1", (F, D)),
+                            ("mlp.fc2", (D, F))):
+            s[f"{p}.{name}.weight"], s[f"{p}.{name}.bias"] = shape, shape[:1]
+    s["module.v.norm.weight"], s["module.v.norm.bias"] = (D,), (D,)
+    for head in ("module.v.head", "module.v.head_dist"):
+        s[f"{head}.weight"], s[f"{head}.bias"] = (1000, D), (1000,)
+    for head in ("module.cpredlayer", "module.gpredlayer"):
+        s[f"{head}.0.weight"], s[f"{head}.0.bias"], s[f"{head}.2.weight"], s[f"{head}.2.bias"] = (D, D), (D,), (256, D), (256,)
+    return s
+
+
 def mae_ast_sine_table(rows: int, D: int) -> np.ndarray:
     """``SinusoidalPositionalEncoding.pe`` (mae_ast.py:802-812) by the reference's float32 formula: ``(1, rows, D)``."""
     import math
@@ -539,6 +564,13 @@ def _synthetic(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
                  "num_batches_tracked": lambda: np.full(shape, 1000.0)}[leaf]()
         elif name.endswith("_mask_emb"):
             w = rng.uniform(0.0, 1.0, size=shape)
+        elif name in ("module.p_input_fdim", "module.p_input_tdim"):  # the pretraining input size, saved as parameters
+            w = np.full(shape, cfg.ss_p_input_fdim if name.endswith("fdim") else cfg.ss_p_input_tdim)
+        elif name.startswith("module.") and name.endswith(("cls_token", "dist_token", "mask_embed", "pos_embed")):
+            # at the scale of the patch tokens (the released tables are trained: nothing like their 0.02 initialisation is left)
+            w = 0.3 * rng.standard_normal(shape)
+        elif name == "module.v.patch_embed.proj.weight":  # (D, 1, fshape, tshape) on a normalised log-mel image of RMS about 0.5
+            w = rng.standard_normal(shape) * (2.0 / np.sqrt(shape[2] * shape[3]))
         elif name.startswith("gEncoder.batchNorm"):  # ChannelNorm (1, C, 1): gains 1 + 0.1 N(0, 1), shifts 0.05 N(0, 1)
             w = (1.0 if leaf == "weight" else 0.0) + (0.1 if leaf == "weight" else 0.05) * rng.standard_normal(shape)
         elif name.startswith("gEncoder.conv") and leaf == "weight":  # (out, in, k): unit variance in front of the channel norm
@@ -881,6 +913,23 @@ def named_config(name: str) -> EncoderConfig:
         from .config import mae_ast_config
 
         return mae_ast_config(**mae_ast[name])
+    # SSAST: fixed windows, hanning kaldi log-mel, overlapping Conv2d patches behind cls / dist, pre-LN timm blocks
+    tiny_ss = dict(embed_dim=128, heads=2, layers=2, window_secs=0.5)
+    ssast = {
+        "ssast_patch_base": dict(model_type="p"), "ssast_frame_base": dict(model_type="f"),
+        "ssast_patch_base_l2": dict(model_type="p", layers=2), "ssast_frame_base_l2": dict(model_type="f", layers=2),
+        # 0.5 s windows: 50 image rows, 12 x 4 + 2 = 50 tokens (patch), 49 + 2 = 51 tokens (frame)
+        "tiny_ssast_patch": dict(model_type="p", **tiny_ss, p_input_tdim=1024),  # p_t_dim 64 > t_dim 4: the centre cut
+        "tiny_ssast_frame": dict(model_type="f", **tiny_ss, p_input_tdim=1024),  # p_t_dim 512 > t_dim 49: the centre cut
+        "tiny_ssast_patch_interp": dict(model_type="p", **tiny_ss, p_input_tdim=48),  # p_t_dim 3 < t_dim 4: the interpolation
+        "tiny_ssast_frame_interp": dict(model_type="f", **tiny_ss, p_input_tdim=60),  # p_t_dim 30 < t_dim 49
+        "tiny_ssast_patch_d192": dict(model_type="p", model_size="tiny", layers=2, window_secs=0.5),
+        "tiny_ssast_patch_w1": dict(model_type="p", embed_dim=128, heads=2, layers=2, window_secs=1.0),
+    }
+    if name in ssast:
+        from .config import ssast_config
+
+        return ssast_config(**ssast[name])
     # BYOL-S: centred windows, hann(400) log-mel, whole-batch statistics, AudioNTT2020 or a ResNet of BasicBlocks, mean + max
     byol_s = {
         "byol_s_default": dict(network="default"), "byol_s_resnetish34": dict(network="resnetish", blocks=(3, 4, 6, 3)),
@@ -916,7 +965,7 @@ def named_config(name: str) -> EncoderConfig:
 
         return mockingjay_config(**mj[name])
     if name not in table:
-        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(byol_a) + list(byol_s) + list(mae_ast) + list(mj))}")
+        raise KeyError(f"unknown config {name!r}; have {sorted(list(table) + list(w2v) + list(cpc) + list(apc) + list(decoar) + list(npc) + list(vggish) + list(byol_a) + list(byol_s) + list(mae_ast) + list(ssast) + list(mj))}")
     cfg = EncoderConfig(**table[name])
     cfg.validate()
     return cfg
